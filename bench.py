@@ -2,6 +2,7 @@
 """Benchmark of the MI355X-native YOLOv5-s training step (BASELINE.json metric: images/sec, 640 px).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR      (+ the last timed step's outputs as DIR/*.npy)
     python bench.py --gpus N ...                      (WORLD_SIZE unset: starts N fresh child processes itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -631,6 +632,47 @@ def family_table(prof):
     return rows
 
 
+DUMP_BUDGET = 64_000_000       # bytes of .npy payload --dump-outputs may write in all
+
+
+def dump_outputs(out_dir, net, total, parts):
+    """--dump-outputs: what the timed step handed its caller after the LAST timed step, as <out_dir>/<name>.npy - the
+    total loss, its three parts, and the model the step left behind (parameters after the SGD update, their gradients,
+    the BatchNorm running statistics), each flattened in named_parameters() / named_buffers() order.  An array that does
+    not fit in its share of DUMP_BUDGET is replaced by a fixed seeded sample of its elements (<name>.npy) plus the sampled
+    positions (<name>_index.npy), the same positions in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    small = {
+        "loss_total": total.detach().reshape(-1).double().cpu().numpy(),
+        "loss_parts": torch.stack([parts.localization.detach().reshape(()), parts.objectness.detach().reshape(()),
+                                   parts.classification.detach().reshape(())]).double().cpu().numpy(),
+        "bn_buffers": torch.cat([b.detach().reshape(-1).double() for _, b in net.named_buffers()]).cpu().numpy(),
+    }
+    params = list(net.parameters())
+    large = {
+        "params": torch.cat([p.detach().reshape(-1).float() for p in params]).cpu().numpy(),
+        "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                            for p in params]).cpu().numpy(),
+    }
+    written = {}
+    for name, a in small.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = a.nbytes
+    share = (DUMP_BUDGET - sum(written.values())) // len(large)
+    for name, a in large.items():
+        if a.nbytes > share:
+            k = share // (a.itemsize + 8)                 # sampled values + their float64 positions
+            idx = np.sort(np.random.default_rng(2023).choice(a.size, size=k, replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+            written[name + "_index"] = k * 8
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = a.nbytes
+    assert sum(written.values()) <= DUMP_BUDGET, written
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -654,7 +696,12 @@ def main():
     ap.add_argument("--loop-steps", type=int, default=30)
     ap.add_argument("--loop-mixup", type=float, default=None, help="mixup probability of the loop leg (default 0 at N=1, 0.1 at N>1)")
     ap.add_argument("--loop-in-process", action="store_true", help="loop leg: host side of the data protocol in this process (round 3)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss, updated parameters, gradients, "
+                         "BatchNorm statistics) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # decided before anything touches a GPU; the parent only starts and supervises the ranks (never re-executes itself)
     if "WORLD_SIZE" not in os.environ and (args.launch == "self" or (args.launch == "auto" and args.gpus > 1)):
@@ -729,6 +776,7 @@ def main():
 
     eng.sgd_step(lr, mom, wd, 1.0 / world)        # uploads the hyper-parameters to the device buffer
     params = list(net.parameters())
+    last_parts = [None]         # LossResult of the latest step() (under replay: the captured step's device tensors)
 
     def step():
         for p in params:
@@ -739,7 +787,8 @@ def main():
             total = B * (lr_.localization + lr_.classification + lr_.objectness)
             total.backward()
         else:
-            total, _ = net.train_step(x, loss_fn, shape, targets, float(B))
+            total, lr_ = net.train_step(x, loss_fn, shape, targets, float(B))
+        last_parts[0] = lr_
         eng.wait_grads()
         eng.sgd_step_device()
         return total
@@ -809,6 +858,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     _beat("timed region done")
+    if args.dump_outputs and rank == 0:        # before anything below runs the step again
+        dump_outputs(args.dump_outputs, net, last, last_parts[0])
     if eng.stamps_on:          # KODHIP_DEBUG_STAMPS=1: where the step's time goes, from device clock stamps
         stamp_report(eng, graph, step)
     # per-kernel durations of every family: one extra eager step with HIP events around each launch on its launch

@@ -19,8 +19,8 @@ import torch
 from oracle import ref_import as R
 from oracle import synth
 
-# `python -m oracle.gen_golden` rewrites tests/golden/ in place; KOD_GOLDEN_OUT=<dir> writes elsewhere (the CPU test
-# tests/test_oracle_golden.py::test_fixtures_regenerate_from_the_reference regenerates into a temp dir and diffs)
+# `python -m oracle.gen_golden` rewrites tests/golden/ in place; KOD_GOLDEN_OUT=<dir> writes elsewhere (build() regenerates
+# into oracle/_ref/golden/ - oracle/ref_build.py - and tests/test_oracle_golden.py::test_fixtures_regenerate_from_the_reference diffs)
 OUT = os.environ.get("KOD_GOLDEN_OUT") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 
 
@@ -488,6 +488,7 @@ def gen_sppf():
 def main():
     import sys
     assert R.available(), "reference checkout not found"
+    torch.set_num_threads(synth.GOLDEN_THREADS)
     os.makedirs(OUT, exist_ok=True)
     only = set(sys.argv[1:])                      # e.g. `python -m oracle.gen_golden gen_iou gen_samplers`
     for fn in (gen_iou, gen_assigner, gen_loss, gen_network, gen_decode_nms, gen_optim, gen_mosaic,

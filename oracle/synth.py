@@ -10,6 +10,11 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+# torch's CPU kernels split their work by the intra-op thread count, and with it the fp32 summation order and which
+# elements take the vectorised path: the golden fixtures are generated (oracle/gen_golden.py) and checked
+# (tests/test_oracle_golden.py) with this many threads, so that their bit-exact / few-ulp comparisons hold on any machine
+GOLDEN_THREADS = 8
+
 
 def zipf_pmf(nc: int, a: float = 1.01) -> np.ndarray:
     k = np.arange(1, nc + 1, dtype=np.float64)

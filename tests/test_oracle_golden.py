@@ -10,6 +10,16 @@ from oracle import datapath, detection as D, optim as O, synth
 from oracle.network import OracleYolov5, HeadOut, NetOut
 
 
+@pytest.fixture(autouse=True)
+def _golden_thread_count():
+    """Every comparison here runs with the intra-op thread count the fixtures were generated with (synth.GOLDEN_THREADS):
+    a different count changes torch's CPU summation order and vectorised/scalar split, i.e. the last ulps."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(synth.GOLDEN_THREADS)
+    yield
+    torch.set_num_threads(n)
+
+
 def _targets(tg):
     return [D.Target(b, l) for b, l in tg]
 
@@ -307,27 +317,27 @@ def test_sppf_forms_vs_reference(golden, case):
         np.testing.assert_allclose(v.grad.numpy(), g[p + "grad." + k], rtol=1e-5, atol=1e-6, err_msg=k)
 
 
-def test_fixtures_regenerate_from_the_reference(tmp_path):
+def test_fixtures_regenerate_from_the_reference():
     """The pinning recipe is ONE command: `python -m oracle.gen_golden` from a clean process with an empty output
     directory exits 0 and reproduces every committed fixture array for array (the generators used to
-    depend on their order - the reference binds albumentations' ToTensorV2 at import).  Needs the reference checkout
-    (build container only; skipped on the GPU box)."""
+    depend on their order - the reference binds albumentations' ToTensorV2 at import).  build() runs that command into
+    oracle/_ref/golden/ where the reference checkout is present (oracle/ref_build.py); this compares its output with
+    the committed fixtures.  Skipped where build() had no reference checkout (the GPU box)."""
     import os
-    import subprocess
-    import sys
-    from oracle import ref_import
-    if not ref_import.available():
-        pytest.skip("reference checkout not present")
+    from oracle import ref_build
+    st = ref_build.status()
+    if st is None:
+        pytest.skip("no fixtures regenerated by build(): the reference checkout was not present when it ran")
+    assert st["recipe_digest"] == ref_build.recipe_digest(), "oracle/ changed since build() regenerated the fixtures: re-run build()"
+    assert st["returncode"] == 0, st["output_tail"]
+    out = ref_build.GOLDEN_OUT
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = {**os.environ, "KOD_GOLDEN_OUT": str(tmp_path), "PYTHONDONTWRITEBYTECODE": "1"}
-    r = subprocess.run([sys.executable, "-m", "oracle.gen_golden"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    made = sorted(f for f in os.listdir(tmp_path) if f.endswith(".npz"))
+    made = sorted(f for f in os.listdir(out) if f.endswith(".npz"))
     assert made == ["affine.npz", "assigner.npz", "decode_nms.npz", "iou.npz", "loss.npz", "mosaic.npz", "network.npz",
                     "optim.npz", "protocol.npz", "samplers.npz", "sppf.npz"], made
     n = 0
     for f in made:
-        new, old = np.load(tmp_path / f, allow_pickle=False), np.load(os.path.join(root, "tests", "golden", f), allow_pickle=False)
+        new, old = np.load(os.path.join(out, f), allow_pickle=False), np.load(os.path.join(root, "tests", "golden", f), allow_pickle=False)
         assert sorted(new.files) == sorted(old.files), f
         for k in new.files:
             a, b = new[k], old[k]
