@@ -115,7 +115,7 @@ int kodhip_conv_dgrad_dual_bnred(const void* dy1, const void* w1, const void* dy
                                  int B, int H, int W, int ldx, int xcoff, int Cin, int N, int Kp, int ldy, int ycoff,
                                  int accumulate, void* dx_f32, const void* segments, int nseg, int slots, kodStream_t stream);
 int kodhip_conv_wgrad_splits(long M, int N, int Kp);     /* generic split-K kernel */
-/* split count of the kernel kodhip_conv_wgrad[_partial] picks for this geometry (3x3 / stride 1 / pad 1 layers with whole
+/* split count of the kernel kodhip_conv_wgrad picks for this geometry (3x3 / stride 1 / pad 1 layers with whole
  * 32-channel chunks take a form that stages dY once per block and every input row once per kernel row): size the slab
  * region with this one.  H, W: input dims; ldx / ldy: row strides of x / dy in elements. */
 int kodhip_conv_wgrad_splits_geo(int B, int H, int W, int ldx, int Cin, int N, int KH, int KW, int SH, int SW, int PH, int PW,
@@ -124,25 +124,6 @@ int kodhip_conv_wgrad(const void* x, const void* dy, float* partials, float* gra
                       int B, int H, int W, int ldx, int xcoff, int Cin,
                       int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
                       int ldy, int ycoff, int n_valid, int stem, float scale, kodStream_t stream);
-/* The two halves of kodhip_conv_wgrad apart: the split-K kernel alone (fp32 slabs partials[splits][N][Kp], a region of
- * its own per layer), and ONE launch that sums the slabs of many layers into their gradients (same fixed-order
- * arithmetic as the per-layer form: bit-identical) - a training step reduces a whole gradient bucket at a time instead
- * of launching ~60 small reductions. */
-int kodhip_conv_wgrad_partial(const void* x, const void* dy, float* partials,
-                              int B, int H, int W, int ldx, int xcoff, int Cin,
-                              int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
-                              int ldy, int ycoff, kodStream_t stream);
-typedef struct KodWgradReduceDesc {
-  long part_off, grad_off;      /* floats, relative to the `partials` / `grads` arguments */
-  int splits, Nfull, N, K, Kp, Cin /* stem: 8 */, KK /* KH*KW */, stem;
-  float scale;
-  int block_start;              /* first block of the layer; it owns kodhip_wgrad_reduce_blocks(N, K) blocks */
-} KodWgradReduceDesc;
-int kodhip_wgrad_reduce_desc_bytes(void);
-int kodhip_wgrad_reduce_blocks(int n_valid, int K);
-int kodhip_wgrad_reduce_batched(const float* partials, float* grads, const void* descs /* device KodWgradReduceDesc[n] */,
-                                int n_desc, int total_blocks, kodStream_t stream);
-
 /* Weight gradients of TWO pointwise layers with the same input (a CSP layer's main_conv and short_conv,
  * kod/nn/layers/csp.py:85-99) in one launch + one reduction: the shared input is streamed from HBM once.  dy1 / dy2:
  * [B*H*W][ldy] (+ycoff, N channels each); partials: kodhip_conv_wgrad_dual_splits(...) * 2N * Kp floats; grad1 / grad2: fp32
@@ -175,15 +156,6 @@ int kodhip_bn_finalize_partials(const float* partials, int T, double count, cons
                                 float* running_mean, float* running_var, float momentum, float eps,
                                 float* scale, float* shift, float* mean, float* rstd, int C, int update_running,
                                 kodStream_t stream);
-/* two units whose convolution ran as ONE launch with N = 2 * Ch columns - a CSP layer's main_conv + short_conv
- * (kod/nn/layers/csp.py:87-88: same input): partials [2][2 * Ch][T], unit h owns channels [h * Ch, (h + 1) * Ch); aff* =
- * scale | shift | mean | rstd.  view != NULL: SyncBN over the peer buffers (slot0 / slot1, count = pixels of all ranks) */
-int kodhip_bn_finalize_partials_pair(const float* partials, int T, double count, int Ch, float momentum, float eps,
-                                     int update_running,
-                                     const float* gamma0, const float* beta0, float* running_mean0, float* running_var0, float* aff0,
-                                     const float* gamma1, const float* beta1, float* running_mean1, float* running_var1, float* aff1,
-                                     const void* view /* host KodPeerView or NULL */, unsigned int slot0, unsigned int slot1,
-                                     kodStream_t stream);
 /* SyncBN forms of the two single launches: the rank's sums are exchanged through the peer buffers (kodhip_peer_*, below)
  * inside the kernel.  count = pixels of ALL ranks; view = host KodPeerView (copied into the launch); slot = first granule
  * of this exchange (it uses 4 * C).  Parameter gradients (dgamma, dbeta) keep the rank's own sums. */
@@ -207,12 +179,6 @@ int kodhip_bn_bwd_coeffs_partials(const float* partials, int T, double count, co
 int kodhip_bn_silu_apply(const void* y, int ldy /* row stride of y (>= C: y may be a channel slice) */, const float* scale, const float* shift,
                          const void* residual, int ldr, int rcoff,
                          void* out, int ldo, int ocoff, long M, int C, kodStream_t stream);
-/* the apply passes of two units whose pre-BN outputs are the channel halves of one tensor y[m][2 * Ch] (one convolution
- * launch for a CSP layer's main_conv + short_conv, csp.py:87-88), each half to its own destination slice */
-int kodhip_bn_silu_apply_pair(const void* y, int ldy, int Ch,
-                              const float* scale0, const float* shift0, void* out0, int ldo0, int ocoff0,
-                              const float* scale1, const float* shift1, void* out1, int ldo1, int ocoff1,
-                              long M, kodStream_t stream);
 int kodhip_bn_bwd_slots(long M, int C);
 int kodhip_bn_silu_bwd_reduce(const void* dA, int lda, int dacoff, const void* y, int ldy, const float* scale,
                               const float* shift, const float* mean, const float* rstd, float* partials,

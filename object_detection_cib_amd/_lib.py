@@ -56,19 +56,13 @@ SIGNATURES = {
     "kodhip_conv_wgrad_splits": (i32, [i64, i32, i32]),
     "kodhip_conv_wgrad_splits_geo": (i32, [i32] * 14),
     "kodhip_conv_wgrad": (i32, [vp, vp, vp, vp] + [i32] * 18 + [f32, vp]),
-    "kodhip_conv_wgrad_partial": (i32, [vp, vp, vp] + [i32] * 16 + [vp]),
     "kodhip_conv_wgrad_dual_splits": (i32, [i32] * 8),
     "kodhip_conv_wgrad_dual": (i32, [vp] * 6 + [i32] * 10 + [f32, vp]),
     "kodhip_stem_bwd_fused_blocks": (i32, [i32, i32, i32, i32]),
     "kodhip_stem_bwd_fused": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]),
-    "kodhip_wgrad_reduce_desc_bytes": (i32, []),
-    "kodhip_wgrad_reduce_blocks": (i32, [i32, i32]),
-    "kodhip_wgrad_reduce_batched": (i32, [vp, vp, vp, i32, i32, vp]),
     "kodhip_bn_reduce_partials": (i32, [vp, vp, i32, i32, vp]),
     "kodhip_bn_finalize": (i32, [vp, f64, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i32, i32, vp]),
     "kodhip_bn_finalize_partials": (i32, [vp, i32, f64, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i32, i32, vp]),
-    "kodhip_bn_finalize_partials_pair": (i32, [vp, i32, f64, i32, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, vp]),
-    "kodhip_bn_silu_apply_pair": (i32, [vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, i64, vp]),
     "kodhip_bn_bwd_coeffs_partials": (i32, [vp, i32, f64, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "kodhip_bn_bwd_coeffs_partials2": (i32, [vp, i32, f64, vp, vp, vp, vp, vp, vp, i32, i32] * 2 + [vp]),
     "kodhip_bn_finalize_partials_peer": (i32, [vp, i32, f64, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, i32, i32, vp, u32, vp]),

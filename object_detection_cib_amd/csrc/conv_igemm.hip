@@ -1178,22 +1178,16 @@ __global__ __launch_bounds__(256, 3) void conv_stem_fwd_kernel(ConvArgs a) {
 // and 1 taps - reductions of very different length - and the launch is a few rounds of resident blocks at most, so
 // blocks are dispatched longest class first (class 3, then 1 and 2, then 0): a long block never starts in the last
 // round behind short ones.  (The layers that still take this form are the deep ones, whose dY stays in L2 / MALL
-// whatever the order; `interleave` != 0 restores the round-1 order - blocks 8j .. 8j+31 = {XCD 0-7} x {class 0-3} -
-// for A/B.)
-struct ConvArgs4 { ConvArgs c[4]; int per_class, interleave; };
+// whatever the order.)
+struct ConvArgs4 { ConvArgs c[4]; int per_class; };
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int MODE, bool FAST, bool F32ACC = false>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (MODE == 2 /*HEAD*/ ? 2 : (FAST ? 4 : 3)))   /* waves per SIMD */
 void conv_igemm_x4_kernel(ConvArgs4 p) {
   const int bid = blockIdx.x;
-  if (p.interleave) {
-    const int cls = (bid >> 3) & 3;
-    conv_igemm_body<BM, BN, WAVES_M, WAVES_N, MODE, FAST, false, F32ACC>(p.c[cls], ((bid >> 5) << 3) | (bid & 7));
-  } else {
-    const int q = bid / p.per_class;                     // 0..3 in dispatch order
-    const int cls = q == 0 ? 3 : (q == 3 ? 0 : q);
-    conv_igemm_body<BM, BN, WAVES_M, WAVES_N, MODE, FAST, false, F32ACC>(p.c[cls], bid - q * p.per_class);
-  }
+  const int q = bid / p.per_class;                     // 0..3 in dispatch order
+  const int cls = q == 0 ? 3 : (q == 3 ? 0 : q);
+  conv_igemm_body<BM, BN, WAVES_M, WAVES_N, MODE, FAST, false, F32ACC>(p.c[cls], bid - q * p.per_class);
 }
 
 // ---- launch planning --------------------------------------------------------------------------------
@@ -1213,15 +1207,12 @@ constexpr int MAX_STATS_SLOTS = 1024;
 // Tile shape: the widest channel tile that fits N (or the next narrower one when that removes a badly quantised
 // last round).  256-pixel tiles (8 waves, 3-stage ring) when the reduction is long enough to amortise their deeper
 // pipeline fill (measured on gfx950: 3x3 layers with N >= 128 gain 15-25 %, short-K 1x1 layers lose ~5 %).
-Plan make_plan(long M, int N, int K, bool fast, bool row3 = false, int bn_cap = 0) {
+Plan make_plan(long M, int N, int K, bool fast, bool row3 = false) {
   static int force_bn = -1, force_bm = -1;
   if (force_bn < 0) { const char* e = getenv("KODHIP_FORCE_BN"); force_bn = e ? atoi(e) : 0; }
   if (force_bm < 0) { const char* e = getenv("KODHIP_FORCE_BM"); force_bm = e ? atoi(e) : 0; }
   // 64 < N < 128 (yv5m's 96): one 128-column tile (three quarters used) stages every pixel tile once, two 64-column tiles twice
-  static int wide96 = -1;                  // KODHIP_PLAN_WIDE96=0: A/B knob
-  if (wide96 < 0) { const char* e = getenv("KODHIP_PLAN_WIDE96"); wide96 = e ? atoi(e) : 1; }
-  int widest = (N >= 128 || (wide96 && N > 64)) ? 128 : (N > 32 ? 64 : 32);
-  if (bn_cap && widest > bn_cap) widest = bn_cap;
+  const int widest = N > 64 ? 128 : (N > 32 ? 64 : 32);
   const bool can256 = fast && widest >= 64 && M >= 256 * 64;       // 256 x 128 and 256 x 64 tiles
   const int bm = !row3 && can256 && (force_bm ? force_bm == 256 : K >= 512) ? 256 : 128;
   Plan best = {};
@@ -1263,20 +1254,9 @@ bool row3_eligible(const ConvArgs& a, bool fast) {
   return true;
 }
 
-// folded stride-2 data gradient: d2s_skip pays where the class boundary 2 * Cin falls on a tile boundary of the plan the
-// layer has anyway (Cin = 64: 170.7 -> 153.0 us); forcing 64-column tiles on Cin = 32 to get one costs more in
-// re-staging than the skipped taps save (236 -> 263 us), so no cap is applied (KODHIP_S2F_BN_CAP=64: the experiment)
-int fold_bn_cap(const ConvArgs& a) {
-  static int cap = -1;
-  if (cap < 0) { const char* e = getenv("KODHIP_S2F_BN_CAP"); cap = e ? atoi(e) : 0; }
-  return (cap && a.d2s_C != 0 && a.d2s_skip && 2 * a.d2s_C == cap) ? cap : 0;
-}
-
-Plan plan_conv(const ConvArgs& a, bool fast, bool& row3, int mode) {
-  static int modes = -1;                 // KODHIP_ROW3_MODES: bit per MODE (debug: 1 = forward, 2 = dgrad, 8 = dgrad + BN reduction)
-  if (modes < 0) { const char* e = getenv("KODHIP_ROW3_MODES"); modes = e ? atoi(e) : 0xF; }
-  row3 = row3_eligible(a, fast) && ((modes >> mode) & 1);
-  return make_plan(a.M, a.N, a.nk1 ? 2 * a.K : a.K, fast, row3, fold_bn_cap(a));
+Plan plan_conv(const ConvArgs& a, bool fast, bool& row3) {
+  row3 = row3_eligible(a, fast);
+  return make_plan(a.M, a.N, a.nk1 ? 2 * a.K : a.K, fast, row3);
 }
 
 template <int MODE, bool F32ACC = false>
@@ -1289,11 +1269,10 @@ int launch(const ConvArgs& a, hipStream_t stream) {
   const bool fast = fast_eligible(a);
   KOD_CHECK_ARG(fast || a.wide_px == 1, "conv: wide-pixel taps need the FAST path");
   args.x_bytes = (uint32_t)xb; args.w_bytes = (uint32_t)wb;
-  static const bool pw_on = !(getenv("KODHIP_POINTWISE") && getenv("KODHIP_POINTWISE")[0] == '0');     // A/B knob
-  args.pointwise = (pw_on && fast && a.KH == 1 && a.KW == 1 && a.mul_h == 1 && a.mul_w == 1 && a.add_h == 0 && a.add_w == 0 &&
+  args.pointwise = (fast && a.KH == 1 && a.KW == 1 && a.mul_h == 1 && a.mul_w == 1 && a.add_h == 0 && a.add_w == 0 &&
                     a.Ho == a.Hs && a.Wo == a.Ws && a.wide_px == 1 && (a.sh_shift | a.sw_shift) == 0) ? 1 : 0;
   bool row3;
-  const Plan p = plan_conv(a, fast, row3, MODE);
+  const Plan p = plan_conv(a, fast, row3);
   args.tiles_n = p.tiles_n; args.tiles_m = p.tiles_m; args.groups_m = p.groups_m;
   if (MODE == MODE_RAW) {
     KOD_CHECK_ARG(a.stats_slots >= p.groups_m, "conv: stats buffer has %d slots, launch needs %d", a.stats_slots, p.groups_m);
@@ -1305,12 +1284,11 @@ int launch(const ConvArgs& a, hipStream_t stream) {
   }
   dim3 g(p.grid);
   if constexpr (MODE == MODE_RAW) {
-    // the stem's wide-pixel form (KODHIP_STEM_ROW=0: the generic per-tap staging, for A/B)
-    static const bool stem_row = !(getenv("KODHIP_STEM_ROW") && getenv("KODHIP_STEM_ROW")[0] == '0');
-    if (stem_row && fast && !row3 && a.wide_px == 4 && a.KW == 1 && a.mul_w == 1 && a.add_w == -1 && a.ldx == 8 && a.xcoff == 0 &&
+    // the stem's wide-pixel form
+    if (fast && !row3 && a.wide_px == 4 && a.KW == 1 && a.mul_w == 1 && a.add_w == -1 && a.ldx == 8 && a.xcoff == 0 &&
         p.bm == 128 && (p.bn == 32 || p.bn == 64) && (long)a.M + 256 < (1l << 31)) {
-      // KODHIP_STEM_ROW: 1 = row-shared staging inside the generic body, default = the dedicated kernel (N <= 32)
-      if (p.bn == 32 && a.N <= 32 && a.KH == 6 && a.ycoff % 8 == 0 && !(getenv("KODHIP_STEM_ROW") && getenv("KODHIP_STEM_ROW")[0] == '1')) {
+      // the dedicated kernel for N <= 32, else row-shared staging inside the generic body
+      if (p.bn == 32 && a.N <= 32 && a.KH == 6 && a.ycoff % 8 == 0) {
         int blocks = p.tiles_m < 768 ? p.tiles_m : 768;             // 3 resident blocks per CU (48 KB of LDS each)
         if (blocks > a.stats_slots) blocks = a.stats_slots;
         hipLaunchKernelGGL(conv_stem_fwd_kernel, dim3(blocks), dim3(256), 0, stream, args);
@@ -1371,8 +1349,7 @@ int launch_x4(ConvArgs c[4], hipStream_t stream) {
       p.c[i].slot_base = i * pl.groups_m; p.c[i].slot_used = 4 * pl.groups_m;
     }
   }
-  static const bool interleave = getenv("KODHIP_S2_INTERLEAVE") != nullptr;
-  p.per_class = pl.grid; p.interleave = interleave;
+  p.per_class = pl.grid;
   dim3 g(pl.grid * 4);
   if (pl.bm == 256 && pl.bn == 64) hipLaunchKernelGGL((conv_igemm_x4_kernel<256, 64, 4, 2, MODE, true, F32ACC>), g, dim3(512), 0, stream, p);
   else if (pl.bm == 256) hipLaunchKernelGGL((conv_igemm_x4_kernel<256, 128, 4, 2, MODE, true, F32ACC>), g, dim3(512), 0, stream, p);
@@ -1555,8 +1532,7 @@ int prep_dgrad_s2f(ConvArgs& a, const void* dy, const void* w_fold, void* dx, in
   if (int rc2 = set_f32(a, accumulate, dx_f32)) return rc2;
   a.mul_h = 1; a.mul_w = 1; a.add_h = 0; a.add_w = 0; a.tap_sign = 1; a.sh_shift = 0; a.sw_shift = 0;
   a.out_mul = 2; a.out_off_y = 0; a.out_off_x = 0; a.out_H = H; a.out_W = W; a.d2s_C = Cin;
-  static const bool skip = !(getenv("KODHIP_S2F_SKIP") && getenv("KODHIP_S2F_SKIP")[0] == '0');      // A/B knob
-  a.d2s_skip = skip ? 1 : 0;
+  a.d2s_skip = 1;
   KOD_CHECK_ARG(fast_eligible(a), "conv_dgrad_s2f: needs the LDS-DMA path (operands within a 32-bit buffer range)");
   return KOD_OK;
 }
@@ -1617,7 +1593,7 @@ int kodhip_conv_dgrad_s2f_bnred_slots(int B, int H, int W, int Cin, int N, int l
   if (getenv("KODHIP_NO_BNRED")) return 0;
   ConvArgs a;
   if (prep_dgrad_s2f(a, fake, fake, (void*)fake, B, H, W, Cin, 0, Cin, N, ldy, 0, 0)) return 0;
-  return 4 * make_plan(a.M, a.N, a.K, true, false, fold_bn_cap(a)).groups_m;
+  return 4 * make_plan(a.M, a.N, a.K, true).groups_m;
 }
 
 int kodhip_conv_dgrad_s2f_bnred(const void* dy, const void* w_fold, void* dx,
@@ -1652,7 +1628,7 @@ int kodhip_conv_dgrad_bnred_slots(int B, int H, int W, int Cin, int N, int KH, i
   const int Kp = KH * KW * ((N + 31) / 32 * 32);
   if (prep_dgrad(a, fake, fake, (void*)fake, B, H, W, Cin, 0, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, 0, 0) || !fast_eligible(a)) return 0;
   bool row3;
-  return plan_conv(a, true, row3, MODE_PLAIN_BN).groups_m;
+  return plan_conv(a, true, row3).groups_m;
 }
 
 int kodhip_conv_dgrad_bnred(const void* dy, const void* w_dgrad, void* dx,

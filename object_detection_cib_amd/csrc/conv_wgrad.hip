@@ -53,9 +53,7 @@ __device__ __forceinline__ bool wg_map(const WgradArgs& a, int bid, int tiles, i
 }
 __host__ inline int wg_grid(WgradArgs& a) {
   const int tiles = a.tiles_n * a.tiles_k;
-  static int mode = -1;               // KODHIP_WGRAD_LINEAR=0: A/B knob
-  if (mode < 0) { const char* e = getenv("KODHIP_WGRAD_LINEAR"); mode = e ? atoi(e) : 1; }
-  a.linear_map = (mode && a.splits % 8 != 0 && a.splits < 64) ? 1 : 0;
+  a.linear_map = (a.splits % 8 != 0 && a.splits < 64) ? 1 : 0;
   return a.linear_map ? tiles * a.splits : cdiv(a.splits, 8) * 8 * tiles;
 }
 
@@ -797,7 +795,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* part, fl
 // The same reduction with 16-byte accesses: a thread owns FOUR consecutive k of one slab row (K and Kp are multiples of 4, so
 // a quad never crosses rows) for its split lane; per (n, k) the additions and their order are exactly wgrad_reduce_kernel's
 // (four chains over the lane's splits, (s0 + s1) + (s2 + s3), then the eight lanes in order) => bit-identical gradients,
-// a quarter of the load instructions and 4 x the bytes in flight per thread.  KODHIP_WGRAD_REDUCE_V4=0: the scalar kernel.
+// a quarter of the load instructions and 4 x the bytes in flight per thread.  Unaligned operands take the scalar kernel.
 constexpr int RED_Q = 32;                // k quads per block (128 consecutive k)
 __global__ __launch_bounds__(256) void wgrad_reduce_v4_kernel(const float* part, float* grad, int splits, int Nfull,
                                                               int N, int K, int Kp, int Cin, int KK, int stem,
@@ -852,9 +850,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_v4_kernel(const float* part,
 
 static int launch_wgrad_reduce(const float* part, float* grad, int splits, int Nfull, int N, int K, int Kp, int Cin, int KK,
                                int stem, float scale, float* grad2, int n_first, hipStream_t stream) {
-  static int v4 = -1;
-  if (v4 < 0) { const char* e = getenv("KODHIP_WGRAD_REDUCE_V4"); v4 = e ? atoi(e) : 1; }
-  if (v4 && K % 4 == 0 && Kp % 4 == 0 && (reinterpret_cast<uintptr_t>(part) & 15) == 0)
+  if (K % 4 == 0 && Kp % 4 == 0 && (reinterpret_cast<uintptr_t>(part) & 15) == 0)
     hipLaunchKernelGGL(wgrad_reduce_v4_kernel, dim3(cdiv((long)N * (K >> 2), RED_Q)), dim3(256), 0, stream, part, grad, splits, Nfull, N, K,
                        Kp, Cin, KK, stem, scale, grad2, n_first);
   else
@@ -862,69 +858,6 @@ static int launch_wgrad_reduce(const float* part, float* grad, int splits, int N
                        KK, stem, scale, grad2, n_first);
   KOD_LAUNCH_CHECK("wgrad_reduce");
   return KOD_OK;
-}
-
-// ---- the same reduction for MANY layers in one launch.  A training step has ~60 weight gradients; their slab
-// reductions are 5-30 us kernels of a few hundred blocks each (1.0 ms per step as separate launches, mostly launch
-// ramps and tails).  Every layer keeps its own slab region, and ONE launch per gradient bucket reduces them all: block
-// -> layer by binary search over a small descriptor table, then exactly wgrad_reduce_kernel's arithmetic (same
-// fixed-order sums => bit-identical gradients).
-struct ReduceDesc {
-  long part_off, grad_off;      // in floats, relative to the partials / gradient arenas
-  int splits, Nfull, N, K, Kp, Cin, KK, stem;
-  float scale;
-  int block_start;              // first block of this layer; blocks = cdiv(N * K, RED_K)
-};
-
-__global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(const float* parts, float* grads, const ReduceDesc* descs,
-                                                                   int n_desc) {
-  __shared__ float sm[RED_L][RED_K + 1];
-  int lo = 0, hi = n_desc - 1;
-  const int bid = blockIdx.x;
-  while (lo < hi) {             // last descriptor whose block_start <= bid (block-uniform: scalar loads)
-    const int mid = (lo + hi + 1) >> 1;
-    if (descs[mid].block_start <= bid) lo = mid; else hi = mid - 1;
-  }
-  const ReduceDesc d = descs[lo];
-  const float* part = parts + d.part_off;
-  float* grad = grads + d.grad_off;
-  const int kx = threadIdx.x % RED_K, sl = threadIdx.x / RED_K;
-  const long idx = (long)(bid - d.block_start) * RED_K + kx;
-  const long total = (long)d.N * d.K;
-  float s = 0.f;
-  int n = 0, k = 0;
-  if (idx < total) {
-    n = (int)(idx / d.K);
-    k = (int)(idx - (long)n * d.K);
-    const float* p = part + (size_t)n * d.Kp + k;
-    const size_t slab = (size_t)d.Nfull * d.Kp;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int i = sl;
-    for (; i + 3 * RED_L < d.splits; i += 4 * RED_L) {
-      s0 += p[(size_t)i * slab];
-      s1 += p[(size_t)(i + RED_L) * slab];
-      s2 += p[(size_t)(i + 2 * RED_L) * slab];
-      s3 += p[(size_t)(i + 3 * RED_L) * slab];
-    }
-    for (; i < d.splits; i += RED_L) s0 += p[(size_t)i * slab];
-    s = (s0 + s1) + (s2 + s3);
-  }
-  sm[sl][kx] = s;
-  __syncthreads();
-  if (sl == 0 && idx < total) {
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < RED_L; ++i) t += sm[i][kx];
-    if (d.stem) {
-      int c = k & 3, dx = (k >> 2) & 1, tt = k >> 3;
-      int kh = tt / 3, kwp = tt - kh * 3;
-      if (c < 3) grad[(size_t)n * 108 + c * 36 + kh * 6 + 2 * kwp + dx] = t * d.scale;
-    } else {
-      int tap = k / d.Cin;
-      int ci = k - tap * d.Cin;
-      grad[(size_t)n * d.Cin * d.KK + ci * d.KK + tap] = t * d.scale;
-    }
-  }
 }
 
 #ifndef WG_NST
@@ -1202,12 +1135,10 @@ int launch_row3(WgradArgs a, hipStream_t stream) {
 
 void tile_shape(int N, int Kp, int* tn, int* tk) {
   *tn = N > 64 ? 128 : (N > 32 ? 64 : 32);
-  // yv5m widths: N = 192 as three 64-row tiles (all used) instead of two 128-row tiles (a quarter idle); KODHIP_WGRAD_TN192: A/B knob
+  // yv5m widths: N = 192 as three 64-row tiles (all used) instead of two 128-row tiles (a quarter idle)
   // (measured, profiles/r04_convbench_yv5m_tiles.txt: 192 -> 192 3x3 @40 234 -> 191 us, 96 -> 192 s2 431 -> 337, 384 -> 192 1x1 49 -> 34)
   // (N = 96 as three 32-row tiles instead of one 128-row tile: 198 -> 296 us, not taken)
-  static int tn192 = -1;
-  if (tn192 < 0) { const char* e = getenv("KODHIP_WGRAD_TN192"); tn192 = e ? atoi(e) : 64; }
-  if (N > 128 && N <= 192 && tn192 == 64) *tn = 64;
+  if (N > 128 && N <= 192) *tn = 64;
   *tk = Kp > 64 ? 128 : (Kp > 32 ? 64 : 32);
   // narrow outputs: let one block cover all of K so dY is streamed once
   if (*tn == 32 && (Kp == 160 || Kp == 288)) *tk = Kp;
@@ -1322,16 +1253,6 @@ int kodhip_conv_wgrad(const void* x, const void* dy, float* partials, float* gra
   if (int rc = wgrad_partial(a, x, dy, partials, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff, stream)) return rc;
   return launch_wgrad_reduce((const float*)partials, grad, a.splits, N, n_valid, a.K, Kp, stem ? 8 : Cin, KH * KW, stem, scale,
                              nullptr, 1 << 30, stream);
-}
-
-// The split-K half alone: fp32 slabs partials[kodhip_conv_wgrad_splits(M, N, Kp)][N][Kp]; kodhip_wgrad_reduce_batched
-// turns the slabs of many layers into gradients with one launch.
-int kodhip_conv_wgrad_partial(const void* x, const void* dy, float* partials,
-                              int B, int H, int W, int ldx, int xcoff, int Cin,
-                              int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
-                              int ldy, int ycoff, hipStream_t stream) {
-  WgradArgs a;
-  return wgrad_partial(a, x, dy, partials, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff, stream);
 }
 
 // Weight gradients of TWO pointwise (1x1 / stride 1) layers that read the same input - a CSP layer's main_conv and
@@ -1449,20 +1370,6 @@ int kodhip_stem_bwd_fused(const void* x, const void* dA, int lda, int dacoff, co
   else hipLaunchKernelGGL((conv_stem_bwd_fused_kernel<80, 1>), dim3(blocks), dim3(320), 0, stream, a);
   KOD_LAUNCH_CHECK("stem_bwd_fused");
   return launch_wgrad_reduce((const float*)partials, grad, blocks, N > 32 ? 64 : 32, N, 144, 160, 8, 18, 1, gscale, nullptr, 1 << 30, stream);
-}
-
-int kodhip_wgrad_reduce_desc_bytes(void) { return (int)sizeof(ReduceDesc); }
-int kodhip_wgrad_reduce_blocks(int n_valid, int K) { return cdiv(n_valid * K, RED_K); }
-
-// descs: DEVICE array of n_desc KodWgradReduceDesc sorted by block_start (block_start[0] = 0, each layer owning
-// kodhip_wgrad_reduce_blocks(N, K) consecutive blocks, total_blocks in all); offsets relative to partials / grads.
-int kodhip_wgrad_reduce_batched(const float* partials, float* grads, const void* descs, int n_desc, int total_blocks,
-                                hipStream_t stream) {
-  KOD_CHECK_ARG(partials && grads && descs && n_desc > 0 && total_blocks > 0, "wgrad_reduce_batched: bad args");
-  hipLaunchKernelGGL(wgrad_reduce_batched_kernel, dim3(total_blocks), dim3(256), 0, stream, partials, grads,
-                     (const ReduceDesc*)descs, n_desc);
-  KOD_LAUNCH_CHECK("wgrad_reduce_batched");
-  return KOD_OK;
 }
 
 }  // extern "C"

@@ -19,26 +19,6 @@ from .graph import Graph, ConvUnit, HeadUnit, View, Buf, head_param
 from .ddp import plan_buckets, launch_bucket
 
 
-def _cu_masked_stream(device):
-    """Probe (LOG round 6): KODHIP_WG_CUMASK=<hex word>[:<words>] confines the weight-gradient stream
-    to a CU subset (hipExtStreamCreateWithCUMask; the 32-bit word is repeated over the chip's 256 CU bits).  None = unset."""
-    import os
-    spec = os.environ.get("KODHIP_WG_CUMASK")
-    if not spec:
-        return None
-    import ctypes
-    word, _, n = spec.partition(":")
-    words = int(n) if n else 8
-    mask = (ctypes.c_uint32 * words)(*([int(word, 16)] * words))
-    hip = ctypes.CDLL("libamdhip64.so")
-    st = ctypes.c_void_p()
-    with torch.cuda.device(device):
-        rc = hip.hipExtStreamCreateWithCUMask(ctypes.byref(st), ctypes.c_uint32(words), mask)
-    if rc != 0 or not st.value:
-        raise RuntimeError(f"hipExtStreamCreateWithCUMask failed ({rc})")
-    return torch.cuda.ExternalStream(st.value, device=device)
-
-
 class BackwardMixin:
     # ------------------------------------------------------------------ backward
     def backward(self, head_grads: List[torch.Tensor], out_grads: Optional[List[torch.Tensor]] = None):
@@ -63,13 +43,8 @@ class BackwardMixin:
         wg = None
         if self.wgrad_overlap:
             if self.wg_stream is None:
-                self.wg_stream = _cu_masked_stream(self.device) or torch.cuda.Stream(device=self.device)
-                self.wg_more = [torch.cuda.Stream(device=self.device) for _ in range(self._wg_streams - 1)]
+                self.wg_stream = torch.cuda.Stream(device=self.device)
             wg = self.wg_stream
-        # further weight-gradient streams (EngineOptions.wgrad_streams): the launches rotate over them, each stream with its
-        # own slab scratch; stream 0 is the one the gradient buckets ride on
-        wgs = [wg] + (self.wg_more if (wg is not None and self.wgrad_fork != "legacy") else []) if wg is not None else []
-        rr = [0]
 
         def join_main():
             """the weight-gradient stream (where the gradient buckets ride) waits for what the main stream has queued"""
@@ -79,48 +54,32 @@ class BackwardMixin:
                 wg.wait_event(ev)
         self._join_main = join_main
 
-        def join_wg():
-            """stream 0 waits for everything queued on the other weight-gradient streams"""
-            for o in wgs[1:]:
-                ev = torch.cuda.Event()
-                ev.record(o)
-                wg.wait_event(ev)
-
         # How a weight gradient joins the side stream matters in the captured graph: this stack's graph executor keeps a
         # node's FIRST captured successor on the node's queue and hands the later ones to other queues (~11 us per
         # hand-over).  So a weight gradient takes its dependency where dY is ready (an event right after
         # bn_silu_bwd_apply / head_bwd_prep - it then runs beside the same unit's data gradient, both reading dY) but
         # is launched, i.e. captured, only after the main stream's next kernel (the data gradient): the critical chain
         # apply -> dgrad -> next unit's coefficients -> ... stays on one queue and only the off-path weight gradients
-        # pay the hand-over.  KODHIP_WGRAD_FORK=legacy: wait_stream at the call site, behind the data gradient (round 1).
+        # pay the hand-over.
         deferred = []                  # [(event, name, nbytes, args)]
-        defer = wg is not None and self.wgrad_fork != "legacy"
 
         def fork_point(stream=None):
             """call right after the kernel that completes dY (on `stream`, default the main stream)"""
-            if defer:
+            if wg is not None:
                 self._fork_ev = torch.cuda.Event()
                 self._fork_ev.record(stream or main)
         self._fork_point = fork_point
 
-        batched = self.opt.wgrad_reduce_batched     # slab reductions: one launch per bucket (default) | per layer
-
         def launch_wgrad(name, nbytes, args, stream_obj):
-            """args = kodhip_conv_wgrad's (x, dy, slab region, grad, geometry ..., n_valid, stem, scale), or
-            ("stem", region offset in bytes, kodhip_stem_bwd_fused's arguments with the region base in place 9)"""
+            """args = kodhip_conv_wgrad's (x, dy, slab scratch, grad, geometry ..., n_valid, stem, scale), or ("stem",
+            kodhip_stem_bwd_fused's arguments) or ("dual", kodhip_conv_wgrad_dual's arguments)"""
             e0 = self._t0(stream_obj)
             sid = stream_obj.cuda_stream if stream_obj is not None else s
             self._stamp("wg:" + name, stream_obj)
             if args[0] == "stem":
-                fa = list(args[2:])
-                fa[9] += args[1]
-                chk(lib.kodhip_stem_bwd_fused(*fa, sid), name + ".bwd_fused")
-            elif args[0] == "dual":           # ("dual", region offset, kodhip_conv_wgrad_dual's arguments)
-                fa = list(args[2:])
-                fa[3] += args[1]
-                chk(lib.kodhip_conv_wgrad_dual(*fa, sid), name + ".wgrad2")
-            elif batched:
-                chk(lib.kodhip_conv_wgrad_partial(*args[:3], *args[4:-3], sid), name + ".wgrad")
+                chk(lib.kodhip_stem_bwd_fused(*args[1:], sid), name + ".bwd_fused")
+            elif args[0] == "dual":
+                chk(lib.kodhip_conv_wgrad_dual(*args[1:], sid), name + ".wgrad2")
             else:
                 chk(lib.kodhip_conv_wgrad(*args, sid), name + ".wgrad")
             self._t1(e0, "wgrad", nbytes, stream_obj, name=name)
@@ -128,13 +87,8 @@ class BackwardMixin:
         def flush_wgrads():
             """call after the main stream's next kernel has been launched"""
             for ev, name, nbytes, args in deferred:
-                k = rr[0] % len(wgs)
-                rr[0] += 1
-                if k:
-                    args = list(args)
-                    args[1 if isinstance(args[0], str) else 2] += 4 * k * self._wg_region
-                wgs[k].wait_event(ev)
-                launch_wgrad(name, nbytes, args, wgs[k])
+                wg.wait_event(ev)
+                launch_wgrad(name, nbytes, args, wg)
             deferred.clear()
             if due and not hold[0]:
                 self._launch_due()
@@ -144,16 +98,14 @@ class BackwardMixin:
         self._wg_hold = hold
 
         def timed_wgrad(name, nbytes, *args):
-            if defer:
-                ev, self._fork_ev = self._fork_ev, None
-                if ev is None:
-                    ev = torch.cuda.Event()
-                    ev.record(main)
-                deferred.append((ev, name, nbytes, args))
+            if wg is None:
+                launch_wgrad(name, nbytes, args, None)
                 return
-            if wg is not None:
-                wg.wait_stream(main)
-            launch_wgrad(name, nbytes, args, wg)
+            ev, self._fork_ev = self._fork_ev, None
+            if ev is None:
+                ev = torch.cuda.Event()
+                ev.record(main)
+            deferred.append((ev, name, nbytes, args))
 
         # gradient buffers last written on a side stream (the P3 / P4 heads' data gradients): buffer -> event the main
         # stream must wait for before it reads or accumulates into the buffer
@@ -202,8 +154,6 @@ class BackwardMixin:
                 if t is not None:
                     self.gact[name][..., v.coff:v.coff + v.C].copy_(t.permute(0, 2, 3, 1))
         self._pending = []
-        if self._red_bucket_bytes != self.bucket_bytes:      # the reductions follow the all-reduce buckets
-            self._plan_wgrad_reduce()
         buckets = {}
         if self.collectives:
             buckets = {trig: (lo, hi) for trig, lo, hi in plan_buckets(self.unit_starts, self.n_arena,
@@ -218,23 +168,15 @@ class BackwardMixin:
 
         def launch_due():
             for idx in due:
-                if batched and idx in self.red_groups:       # (KODHIP_WGRAD_REDUCE=bucket) reduce all the bucket's slabs at once
-                    tab, n_desc, blocks = self.red_groups[idx]
-                    e0 = self._t0(wg)
-                    chk(lib.kodhip_wgrad_reduce_batched(wgp, gp, tab.data_ptr(), n_desc, blocks,
-                                                        wg.cuda_stream if wg is not None else s), "wgrad_reduce_batched")
-                    self._t1(e0, "wgrad", 0.0, wg)
-                if idx in buckets:
-                    lo, hi = buckets[idx]
-                    cs = self._comm_stream()
-                    join_wg()
-                    # overlapped buckets use their own communicator: SyncBN sums (main stream) and buckets (side stream)
-                    # never interleave on one communicator from two streams
-                    bc = self.comm_buckets if (cs is not None and self.comm_buckets is not None) else self.comm
-                    # on the weight-gradient stream the bucket's last weight gradient has already waited for an event
-                    # recorded behind every BatchNorm / bias gradient of the bucket (fork_point): no new edge from the main chain
-                    self._pending.append(launch_bucket(ga, lo, hi, self.process_group, cs, bc, also_after=wg,
-                                                       wait_caller=not (cs is not None and cs is wg and defer)))
+                lo, hi = buckets[idx]
+                cs = self._comm_stream()
+                # overlapped buckets use their own communicator: SyncBN sums (main stream) and buckets (side stream)
+                # never interleave on one communicator from two streams
+                bc = self.comm_buckets if (cs is not None and self.comm_buckets is not None) else self.comm
+                # on the weight-gradient stream the bucket's last weight gradient has already waited for an event
+                # recorded behind every BatchNorm / bias gradient of the bucket (fork_point): no new edge from the main chain
+                self._pending.append(launch_bucket(ga, lo, hi, self.process_group, cs, bc, also_after=wg,
+                                                   wait_caller=not (cs is not None and cs is wg)))
             due.clear()
         self._launch_due = launch_due
 
@@ -246,7 +188,7 @@ class BackwardMixin:
             bucket's sake moves the main chain to another queue in the replayed graph (measured: -11 % step rate)."""
             nonlocal unit_i
             unit_i -= 1
-            if (batched and unit_i in self.red_groups) or unit_i in buckets:
+            if unit_i in buckets:
                 due.append(unit_i)
                 if not deferred and not hold[0]:
                     launch_due()
@@ -310,7 +252,7 @@ class BackwardMixin:
             self._t1(e0, "bn_bwd_coeffs", sum(8.0 * u.cout * self.ustate[u.name].T2 for u in group), name="+".join(u.name for u in group))
 
         # (with every collective on the main stream - KODHIP_COMM_OVERLAP=0, RCCL SyncBN - the head chains stay there too)
-        heads_side = (wg is not None and defer and self.branch_overlap and self.profile is None and
+        heads_side = (wg is not None and self.branch_overlap and self.profile is None and
                       (not self.collectives or (self._comm_stream() is not None and not rccl_sync)))
         self._stamp("bwd_begin")
         bwd_start = torch.cuda.Event()
@@ -358,7 +300,7 @@ class BackwardMixin:
                     ev.record(hstream)
                     grad_events[src.buf.name] = ev
                 timed_wgrad(hu.name, 2.0 * hs["M"] * (hu.cin + self.head_npad),
-                            self._ptr(src), hs["dy"].data_ptr(), wgp + 4 * hs["wg_off"], gp + 4 * hs["w_off"],
+                            self._ptr(src), hs["dy"].data_ptr(), wgp, gp + 4 * hs["w_off"],
                             B, hs["H"], hs["W"], src.buf.C, src.coff, hu.cin,
                             self.head_npad, 1, 1, 1, 1, 0, 0, hs["Kp"], self.head_npad, 0, A * (5 + nc), 0, 1.0)
                 flush_wgrads()
@@ -400,8 +342,8 @@ class BackwardMixin:
             self._stamp("wg_end", wg)
         for name in list(grad_events):
             sync_grad(name)
-        for o in wgs:
-            main.wait_stream(o)
+        if wg is not None:
+            main.wait_stream(wg)
         self._stamp("bwd_end")
         self._publish_grads()
         if self.g.inputs:
@@ -438,7 +380,7 @@ class BackwardMixin:
                 self._join_main()          # a gradient bucket on the weight-gradient stream must see this gradient
                 return
             self._fork_point()
-            timed_wgrad(u.name, nb, "stem", 0, *fargs, wgp + 4 * st.wg_off, gp + 4 * st.w_off, B, st.H, st.W, C_, 1.0)
+            timed_wgrad(u.name, nb, "stem", *fargs, wgp, gp + 4 * st.w_off, B, st.H, st.W, C_, 1.0)
             self._flush_wgrads()
             return
         racc = acc_flag(res) if res else 0
@@ -461,7 +403,7 @@ class BackwardMixin:
                 return
             if dgrad == "skip":
                 timed_wgrad(u.name, 2.0 * (B * st.H * st.W * u.cin + st.M * C_),
-                            self._ptr(u.src), st.raw.data_ptr(), wgp + 4 * st.wg_off, gp + 4 * st.w_off,
+                            self._ptr(u.src), st.raw.data_ptr(), wgp, gp + 4 * st.w_off,
                             *geo, st.Kp, st.raw_ld, 0, C_, 0, 1.0)
                 return
             fm, fptr = self._f32("dgrad", u.name, u.src)
@@ -496,7 +438,7 @@ class BackwardMixin:
             ps = self.ustate[partner.name]
             self._wg_hold[0] = False
             timed_wgrad(u.name + "+" + partner.name, 2.0 * (B * st.H * st.W * u.cin + 2 * st.M * C_),
-                        "dual", 0, self._ptr(u.src), st.raw.data_ptr(), ps.raw.data_ptr(), wgp + 4 * st.wg_off,
+                        "dual", self._ptr(u.src), st.raw.data_ptr(), ps.raw.data_ptr(), wgp,
                         gp + 4 * st.w_off, gp + 4 * ps.w_off, B, st.H, st.W, u.src.buf.C, u.src.coff, u.cin, C_, st.Kp,
                         st.raw_ld, 0, 1.0)
             self._flush_wgrads()
@@ -504,7 +446,7 @@ class BackwardMixin:
         cin_true = 3 if u.stem else u.cin
         in_px_w = B * H * W if u.stem else B * st.H * st.W
         timed_wgrad(u.name, 2.0 * (in_px_w * cin_true + st.M * C_),
-                    self._ptr(u.src), st.raw.data_ptr(), wgp + 4 * st.wg_off, gp + 4 * st.w_off,
+                    self._ptr(u.src), st.raw.data_ptr(), wgp, gp + 4 * st.w_off,
                     *geo, st.Kp, st.raw_ld, 0, C_, 1 if u.stem else 0, 1.0)
         self._flush_wgrads()           # this unit's - and a fused short_conv partner's - weight gradients: after the dgrad
 

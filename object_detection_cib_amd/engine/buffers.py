@@ -11,33 +11,29 @@ from __future__ import annotations
 import ctypes as C
 from typing import Dict, List, Optional
 
-import numpy as np
-
 import torch
 
 from .. import _lib
 from .graph import Graph, ConvUnit, HeadUnit, View, Buf
 from .arenas import _pad
-from .ddp import plan_buckets
 from .plan import backward_writes, plan_f32_accumulation, plan_dual_dgrads, plan_bn_reduce_fusion
 
 
 class BufferMixin:
     # ------------------------------------------------------------------ activations
     _UNIT_FIELDS = ("stats", "T", "sums", "aff", "bsums", "bsums_g", "bpart", "T2", "coef", "raw", "M", "H", "W", "Ho",
-                    "Wo", "fused_red", "segs", "seg_slots", "raw_ld", "wg_splits", "wg_off", "stem_fused", "wg_dual", "pair", "pair_raw")
-    _HEAD_FIELDS = ("H", "W", "M", "dy", "ws", "wg_splits", "wg_off")
+                    "Wo", "fused_red", "segs", "seg_slots", "raw_ld", "stem_fused", "wg_dual")
+    _HEAD_FIELDS = ("H", "W", "M", "dy", "ws")
 
     def _export_set(self) -> dict:
         return dict(act=self.act, gact=self.gact, gact32=self.gact32, wg_part=self.wg_part, pool_idx=self.pool_idx,
-                    red_groups=self.red_groups, wg_region=self._wg_region, stem_part=getattr(self, "stem_part", None),
+                    stem_part=getattr(self, "stem_part", None),
                     units={n: {f: getattr(st, f) for f in self._UNIT_FIELDS} for n, st in self.ustate.items()},
                     heads={n: {f: hs[f] for f in self._HEAD_FIELDS} for n, hs in self.hstate.items()})
 
     def _import_set(self, d: dict):
         self.act, self.gact, self.wg_part, self.pool_idx = d["act"], d["gact"], d["wg_part"], d["pool_idx"]
-        self.gact32, self.red_groups, self._wg_region = d["gact32"], d["red_groups"], d["wg_region"]
-        self.stem_part = d["stem_part"]
+        self.gact32, self.stem_part = d["gact32"], d["stem_part"]
         for n, fields in d["units"].items():
             st = self.ustate[n]
             for f, v in fields.items():
@@ -85,7 +81,6 @@ class BufferMixin:
             if b.name != "image":
                 self.gact[b.name] = torch.empty(shp, dtype=torch.bfloat16, device=dev)
         max_part = 0
-        own = self.opt.wgrad_reduce_batched        # slab regions: one per layer (batched reduction) or one shared scratch
         for u in self.exec_units:
             st = self.ustate[u.name]
             if u.stem:
@@ -108,57 +103,20 @@ class BufferMixin:
             st.coef = torch.empty(3 * u.cout, dtype=torch.float32, device=dev)
             wgeo = (B, st.H, st.W, 8, 8, u.cout, 6, 3, 2, 1, 2, 1) if u.stem else \
                 (B, st.H, st.W, u.src.buf.C, u.cin, u.cout, u.k, u.k, u.s, u.s, u.p, u.p)
-            st.wg_splits = lib.kodhip_conv_wgrad_splits_geo(*wgeo, st.Kp, u.cout)
-            nslab = st.wg_splits * u.cout * st.Kp
+            nslab = lib.kodhip_conv_wgrad_splits_geo(*wgeo, st.Kp, u.cout) * u.cout * st.Kp
             # the stem's backward as one kernel (kodhip_stem_bwd_fused): a slab per block, 32 (cout <= 32) or 64 rows
-            st.stem_fused = bool(u.stem and u.cout <= 64 and self.opt.stem_bwd_fused and not own)
+            st.stem_fused = bool(u.stem and u.cout <= 64 and self.opt.stem_bwd_fused)
             if st.stem_fused:
-                st.wg_splits = lib.kodhip_stem_bwd_fused_blocks(B, st.H, st.W, u.cout)
-                nslab = st.wg_splits * (32 if u.cout <= 32 else 64) * 160
+                nslab = lib.kodhip_stem_bwd_fused_blocks(B, st.H, st.W, u.cout) * (32 if u.cout <= 32 else 64) * 160
                 self.stem_part = torch.empty(nslab, dtype=torch.float32, device=dev)    # (it runs on the main stream)
-            # slab region [splits][cout][Kp] (floats): ONE scratch shared by all layers (reduced right after each weight
-            # gradient, while it is still in the 256 MB Infinity Cache) - or, for the per-bucket reduction, a region each
-            st.wg_off = max_part if own else 0
-            max_part = max_part + _pad(nslab) if own else max(max_part, nslab)
-        # A CSP layer's main_conv and short_conv (kod/nn/layers/csp.py:87-88: the same input through two pointwise convs)
-        # run forward as ONE convolution with N = 2 * mid columns: their packed weights are adjacent (arena order = forward
-        # order), their pre-BN outputs are the two channel halves of one tensor (row stride 2 * mid: every later kernel takes
-        # the half as a (pointer, row stride) slice) and their statistic slots are one [2][2 * mid][T] block.
-        units_by_name = {u.name: u for u in self.exec_units}
-        for u in self.exec_units:
-            self.ustate[u.name].pair, self.ustate[u.name].pair_raw = None, None
-        if self.opt.pair_fwd:
-            from .plan import plan_dual_dgrads as _pairs
-            for mname, sname in _pairs(self.g).items():
-                mu, su = units_by_name[mname], units_by_name[sname]
-                mst, sst = self.ustate[mname], self.ustate[sname]
-                if mu.residual is not None or su.residual is not None or sst.f_off != mst.f_off + mu.cout * mst.Kp_f:
-                    continue
-                mid = mu.cout
-                # + a zeroed tail that nobody writes: a data gradient whose channel count is not a multiple of 32 reads up to 16
-                # channels past its slice against zero weights (padded-tap K axis); for the short_conv
-                # half of the LAST row that is past the tensor, and the launcher's buffer range (rows x row stride from the
-                # half's own base pointer) no longer ends where the allocation does
-                flat = torch.empty(mst.M * 2 * mid + 512, dtype=torch.bfloat16, device=dev)
-                flat[mst.M * 2 * mid:].zero_()
-                both = flat[:mst.M * 2 * mid].view(B, mst.Ho, mst.Wo, 2 * mid)
-                mst.pair_raw = sst.pair_raw = both
-                mst.raw, sst.raw = both[..., :mid], both[..., mid:]
-                mst.raw_ld = sst.raw_ld = 2 * mid
-                mst.T = sst.T = lib.kodhip_conv_stats_slots(mst.M, 2 * mid)
-                # (the short_conv keeps its own slots for the two-launch form: RCCL SyncBN, KODHIP_NO_PAIR_FWD)
-                mst.stats = torch.empty(2 * 2 * mid * mst.T, dtype=torch.float32, device=dev)
-                mst.pair, sst.pair = ("main", sname), ("short", mname)
-                for st_, u_ in ((mst, mu), (sst, su)):          # (the row stride enters the launcher's 32-bit range test)
-                    st_.wg_splits = lib.kodhip_conv_wgrad_splits_geo(B, st_.H, st_.W, u_.src.buf.C, u_.cin, u_.cout, 1, 1, 1, 1, 0, 0,
-                                                                     st_.Kp, st_.raw_ld)
-                    if not own:
-                        max_part = max(max_part, st_.wg_splits * u_.cout * st_.Kp)
+            # slab region [splits][cout][Kp] (floats): ONE scratch shared by all layers, reduced right after each weight
+            # gradient, while it is still in the 256 MB Infinity Cache
+            max_part = max(max_part, nslab)
         self._plan_bn_fusion(B)
         # a dual pair's weight gradients as one launch (kodhip_conv_wgrad_dual): slab rows for both layers
         for u in self.exec_units:
             self.ustate[u.name].wg_dual = 0
-        if self.opt.dual_wgrad and not own:
+        if self.opt.dual_wgrad:
             for mname in self._dual:
                 st = self.ustate[mname]
                 u = st.u
@@ -174,55 +132,16 @@ class BufferMixin:
             hs.update(H=hh, W=ww, M=B * hh * ww)
             hs["dy"] = torch.empty((B * hh * ww, self.head_npad), dtype=torch.bfloat16, device=dev)
             hs["ws"] = torch.empty(2048 * self.head_npad, dtype=torch.float32, device=dev)
-            hs["wg_splits"] = lib.kodhip_conv_wgrad_splits_geo(B, hh, ww, h.src.buf.C, h.cin, self.head_npad, 1, 1, 1, 1, 0, 0,
-                                                               hs["Kp"], self.head_npad)
-            hs["wg_off"] = max_part if own else 0
-            nslab = hs["wg_splits"] * self.head_npad * hs["Kp"]
-            max_part = max_part + _pad(nslab) if own else max(max_part, nslab)
-        # shared scratch: one region per weight-gradient stream (engine/backward.py)
-        self._wg_region = _pad(max_part)
-        self.wg_part = torch.empty(max_part if own else self._wg_region * self._wg_regions, dtype=torch.float32, device=dev)
-        self._plan_wgrad_reduce()
+            splits = lib.kodhip_conv_wgrad_splits_geo(B, hh, ww, h.src.buf.C, h.cin, self.head_npad, 1, 1, 1, 1, 0, 0,
+                                                      hs["Kp"], self.head_npad)
+            max_part = max(max_part, splits * self.head_npad * hs["Kp"])
+        self.wg_part = torch.empty(_pad(max_part), dtype=torch.float32, device=dev)
         # SPPF argmax indices
         self.pool_idx = []
         for op in self.g.ops:
             if op.kind == "pool":
                 h, w = H // op.src.stride, W // op.src.stride
                 self.pool_idx.append(torch.empty((B, h, w, op.src.C), dtype=torch.uint8, device=dev))
-
-    def _plan_wgrad_reduce(self):
-        """Weight-gradient slab reductions, one launch per gradient bucket (csrc/conv_wgrad.hip: wgrad_reduce_batched):
-        {trigger unit index: (device descriptor table, n, total blocks)} - the bucket's layers in arena order.  The
-        buckets are the all-reduce buckets of the data-parallel path (engine/ddp.py), planned the same way on one GPU."""
-        lib = self.lib
-        dt = np.dtype([("part_off", "<i8"), ("grad_off", "<i8"), ("splits", "<i4"), ("Nfull", "<i4"), ("N", "<i4"), ("K", "<i4"),
-                       ("Kp", "<i4"), ("Cin", "<i4"), ("KK", "<i4"), ("stem", "<i4"), ("scale", "<f4"), ("block_start", "<i4")])
-        assert dt.itemsize == lib.kodhip_wgrad_reduce_desc_bytes()
-        A, nc = self.g.num_anchors, self.g.num_classes
-        layers = []                   # arena order = forward execution order: (weight offset, descriptor fields)
-        for u in self.exec_units:
-            st = self.ustate[u.name]
-            K = 144 if u.stem else u.k * u.k * u.cin
-            layers.append((st.w_off, dict(part_off=st.wg_off, grad_off=st.w_off, splits=st.wg_splits, Nfull=u.cout, N=u.cout, K=K,
-                                          Kp=st.Kp, Cin=8 if u.stem else u.cin, KK=18 if u.stem else u.k * u.k,
-                                          stem=1 if u.stem else 0, scale=1.0)))
-        for h in self.g.heads:
-            hs = self.hstate[h.name]
-            layers.append((hs["w_off"], dict(part_off=hs["wg_off"], grad_off=hs["w_off"], splits=hs["wg_splits"], Nfull=self.head_npad,
-                                             N=A * (5 + nc), K=h.cin, Kp=hs["Kp"], Cin=h.cin, KK=1, stem=0, scale=1.0)))
-        self.red_groups = {}
-        self._red_bucket_bytes = self.bucket_bytes
-        for trig, lo, hi in plan_buckets(self.unit_starts, self.n_arena, max(self.bucket_bytes // 4, 1)):
-            rows, blk = [], 0
-            for off, d in layers:
-                if lo <= off < hi:
-                    d = dict(d, block_start=blk)
-                    blk += lib.kodhip_wgrad_reduce_blocks(d["N"], d["K"])
-                    rows.append(tuple(d[k] for k in dt.names))
-            if rows:
-                arr = np.array(rows, dtype=dt)
-                tab = torch.from_numpy(arr.view(np.uint8).reshape(-1).copy()).to(self.device)
-                self.red_groups[trig] = (tab, len(rows), blk)
 
     def _check_equal_local_batch(self, key):
         """SyncBN here divides the all-reduced sums by M_local * world_size (torch's SyncBatchNorm all-gathers the

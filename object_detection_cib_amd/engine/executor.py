@@ -54,12 +54,7 @@ class Engine(ArenaMixin, BufferMixin, ForwardMixin, BackwardMixin):
         self.process_group = None
         self.world_size = 1
         self.wg_stream = None          # side stream of the weight-gradient kernels (see backward)
-        self.wg_more = []              # further weight-gradient streams (EngineOptions.wgrad_streams)
         self.wgrad_overlap = self.opt.wgrad_overlap
-        # regions of the slab scratch = weight-gradient streams (the per-bucket reduction keeps a region per layer: one stream)
-        self._wg_streams = 1 if self.opt.wgrad_reduce_batched else max(1, int(self.opt.wgrad_streams))
-        self._wg_regions = self._wg_streams
-        self.wgrad_fork = self.opt.wgrad_fork     # see backward(): deferred capture of the wgrad launches
         self.comm = None               # RcclComm when the process group is RCCL-backed (the product path)
         self.comm_buckets = None       # second communicator: gradient buckets on the weight-gradient stream (comm_overlap)
         self.comm_overlap = self.opt.comm_overlap
@@ -87,8 +82,8 @@ class Engine(ArenaMixin, BufferMixin, ForwardMixin, BackwardMixin):
     def set_activation(self, kind: int, slope: float = 0.0):
         """The conv units' activation (nn/graph_module.activation_code), to be set before the arenas are built.  Anything but
         SiLU runs on the plain elementwise passes (kodhip_bn_act_*): the fused forms that carry SiLU's arithmetic - the
-        BatchNorm-backward reduction in the data gradients' epilogue, the fused stem backward, the pair apply - are off."""
+        BatchNorm-backward reduction in the data gradients' epilogue, the fused stem backward - are off."""
         import dataclasses
         self.act_kind, self.act_slope = int(kind), float(slope)
         if self.act_kind != 0:
-            self.opt = dataclasses.replace(self.opt, bn_reduce_fused=False, stem_bwd_fused=False, pair_fwd=0)
+            self.opt = dataclasses.replace(self.opt, bn_reduce_fused=False, stem_bwd_fused=False)

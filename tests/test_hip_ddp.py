@@ -42,11 +42,10 @@ def _run(net, loss, x, tg, size):
     return total.item()
 
 
-def _worker(rank, world, port, size, out, syncbn="rccl", pair_fwd=False):
+def _worker(rank, world, port, size, out, syncbn="rccl"):
     import torch.distributed as dist
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     os.environ["KODHIP_SYNCBN"] = syncbn             # "rccl": collectives of the group (gloo here); "peer": IPC peer buffers
-    os.environ["KODHIP_PAIR_FWD"] = "1" if pair_fwd else "0"      # a CSP layer's main_conv + short_conv forward as one launch / two
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         torch.cuda.set_device(0)
@@ -69,7 +68,7 @@ def _worker(rank, world, port, size, out, syncbn="rccl", pair_fwd=False):
         dist.destroy_process_group()
 
 
-def test_two_rank_ddp_syncbn_equals_single_process(tmp_path):
+def test_two_rank_ddp_syncbn_transports_agree_and_equal_single_process(tmp_path):
     """256 px: every layer's per-rank row count (2 images) is then a multiple of the 128-row conv tile, so the fp32
     per-tile statistic partials of the single-process run coincide with the ranks' and only their fp64 combination
     order differs - the forward passes agree bit for bit.  (At 128 px the deepest maps hold 32 rows per rank: the split
@@ -81,44 +80,34 @@ def test_two_rank_ddp_syncbn_equals_single_process(tmp_path):
     ctx = mp.get_context("spawn")
     res = {}
     # SyncBN statistics through the group's collectives, and through IPC-mapped peer buffers (two processes mapping
-    # each other's exchange buffer on the one GPU): the two transports must agree bit for bit.  The third run is the
-    # KODHIP_PAIR_FWD=1 form of the peer route (a CSP layer's main_conv + short_conv as one convolution launch and one
-    # exchange kernel for both units' sums - kodhip_bn_finalize_partials_pair with a peer view): it is the one the
-    # single-process comparison below uses, so that form of the exchange is covered too.
-    for mode, pair in (("rccl", False), ("peer", False), ("peer", True)):
+    # each other's exchange buffer on the one GPU): the two transports must agree bit for bit.
+    for mode in ("rccl", "peer"):
         with socket.socket() as s:
             s.bind(("127.0.0.1", 0))
             port = s.getsockname()[1]
-        out = str(tmp_path / f"ddp_{mode}_{int(pair)}.pt")
-        procs = [ctx.Process(target=_worker, args=(r, 2, port, size, out, mode, pair)) for r in range(2)]
+        out = str(tmp_path / f"ddp_{mode}.pt")
+        procs = [ctx.Process(target=_worker, args=(r, 2, port, size, out, mode)) for r in range(2)]
         for p in procs:
             p.start()
         for p in procs:
             p.join(300)
             assert p.exitcode == 0, mode
-        res[(mode, pair)] = torch.load(out)
+        res[mode] = torch.load(out)
     for k in ("g", "rm", "p"):
-        assert torch.equal(res[("peer", False)][k], res[("rccl", False)][k]), k
-    # single process on all 4 images, in the same forward form as the ranks (another form groups the fp32 statistic
-    # partials differently: last-ulp differences that this 4-image random-init network amplifies, see the docstring)
-    from object_detection_cib_amd.engine.options import EngineOptions
+        assert torch.equal(res["peer"][k], res["rccl"][k]), k
+    # single process on all 4 images against the peer route
     rel = lambda a, b: ((a.double() - b.double()).norm() / b.double().norm()).item()
-    for pair in (False, True):
-        got = res[("peer", pair)]
-        net, loss = _build(5)
-        opts = EngineOptions.from_env()
-        opts.pair_fwd = 1 if pair else 0
-        net.engine_options = opts
-        x, tg = _data(size)
-        _run(net, loss, x, tg, size)
-        assert (net.engine().ustate["backbone.stages.stage1.blocks.1.main_conv"].pair is not None) == pair
-        g1 = torch.cat([p.grad.flatten() for p in net.parameters()]).cpu()
-        # summed DDP gradients = sum of per-rank gradients; single-process total = 4*(...) = 2x each rank's scaling
-        assert rel(got["g"], g1) < 2e-2, (pair, rel(got["g"], g1))
-        assert rel(got["rm"], net.engine().rm_arena.cpu()) < 1e-3
-        net.engine().sgd_step((0.1, 0.01, 0.01), (0.8, 0.8, 0.8), (0.0, 5e-4, 0.0), 0.5)
-        p1 = torch.cat([q.detach().flatten() for q in net.parameters()]).cpu()
-        assert rel(got["p"], p1) < 1e-4, pair
+    got = res["peer"]
+    net, loss = _build(5)
+    x, tg = _data(size)
+    _run(net, loss, x, tg, size)
+    g1 = torch.cat([p.grad.flatten() for p in net.parameters()]).cpu()
+    # summed DDP gradients = sum of per-rank gradients; single-process total = 4*(...) = 2x each rank's scaling
+    assert rel(got["g"], g1) < 2e-2, rel(got["g"], g1)
+    assert rel(got["rm"], net.engine().rm_arena.cpu()) < 1e-3
+    net.engine().sgd_step((0.1, 0.01, 0.01), (0.8, 0.8, 0.8), (0.0, 5e-4, 0.0), 0.5)
+    p1 = torch.cat([q.detach().flatten() for q in net.parameters()]).cpu()
+    assert rel(got["p"], p1) < 1e-4
 
 
 def _native_worker(port, size, out):

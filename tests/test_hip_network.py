@@ -585,7 +585,7 @@ def test_train_step_without_autograd_equals_autograd_route(pos_weight):
 def test_side_stream_scheduling_does_not_change_results(size, B):
     """Where a kernel runs must not matter: the default schedule (weight gradients forked by event at bn_silu_bwd_apply,
     CSP short branches / P3-P4 heads / label assignment on side streams, head chains of the backward pass aside) against
-    the round-1 fork and against everything on one stream - eagerly and as a replayed hipGraph: losses and every
+    everything on one stream - eagerly and as a replayed hipGraph: losses and every
     parameter gradient bit for bit (a missing dependency shows up as a difference, at least some of the time)."""
     nc = 10
     x, _ = synth.batch(B, size, nc, 21)
@@ -594,8 +594,7 @@ def test_side_stream_scheduling_does_not_change_results(size, B):
     shape = FeatureShape(width=size, height=size)
     xc = x.cuda()
     results = {}
-    for name, cfg in (("default", {}), ("legacy fork", dict(wgrad_fork="legacy")),
-                      ("one stream", dict(wgrad_overlap=False, branch_overlap=False)), ("default, graph", {})):
+    for name, cfg in (("default", {}), ("one stream", dict(wgrad_overlap=False, branch_overlap=False)), ("default, graph", {})):
         torch.manual_seed(3)
         net = Yolov5Network(3, nc, widen_factor=0.5, deepen_factor=0.33).cuda().train()
         loss = _loss()
@@ -748,38 +747,8 @@ def test_multi_producer_dx_b64_640_vs_fp32_torch():
         assert d["fp32"] <= 1.02 * d["bf16"], (buf, d)
 
 
-def test_batched_wgrad_reduction_equals_per_layer_reduction():
-    """Weight gradients: one slab-reduction launch per gradient bucket (KODHIP_WGRAD_REDUCE=bucket; measured slower than the
-    default, DESIGN 4: the per-layer scratch stays in the Infinity Cache, per-layer regions do not) must give, bit for bit,
-    what one reduction per layer gives - same slabs, same fixed-order sums, only the launch granularity differs.  Two bucket
-    sizes (several buckets / one) at a size where every layer really splits its reduction."""
-    from object_detection_cib_amd.engine.options import EngineOptions
-    widen, deepen, nc, B, size, seed = 0.5, 0.33, 10, 4, 320, 7
-    x, tg = synth.batch(B, size, nc, seed)
-    got = {}
-    for tag, batched, mb in (("layer", False, 8.0), ("bucket8", True, 8.0), ("bucket1", True, 1.0), ("one", True, 1e3)):
-        torch.manual_seed(seed)
-        net = Yolov5Network(3, nc, widen_factor=widen, deepen_factor=deepen)
-        opts = EngineOptions.from_env()
-        opts.wgrad_reduce_batched, opts.bucket_mb = batched, mb
-        opts.stem_bwd_fused = False       # (the batched form keeps the stem's two-launch backward: compare like with like)
-        net.engine_options = opts
-        net = net.cuda().train()
-        _step(net, x.cuda(), tg, size, B)
-        eng = net.engine()
-        assert eng.opt.wgrad_reduce_batched == batched
-        if batched:
-            assert len(eng.red_groups) == {8.0: 4, 1.0: 19, 1e3: 1}.get(mb, len(eng.red_groups)) or mb == 1.0
-        got[tag] = torch.cat([p.grad.flatten() for p in net.parameters()]).clone()
-    assert torch.isfinite(got["layer"]).all() and got["layer"].abs().sum() > 0
-    for tag in ("bucket8", "bucket1", "one"):
-        assert torch.equal(got[tag], got["layer"]), tag
-
-
 def test_schedule_switches_keep_the_gradients():
     """Launch-schedule switches of the backward program against the default, one training step at 320 px:
-    * EngineOptions.wgrad_streams = 2 (weight gradients rotating over two side streams, a slab scratch each; measured slower,
-      DESIGN 4) - same kernels, same slabs: bit-identical gradients;
     * EngineOptions.stem_bwd_fused = False (the stem's BatchNorm/SiLU backward as its own pass + the generic weight gradient
       instead of kodhip_stem_bwd_fused) and the fused kernel on the weight-gradient stream instead of the main stream: only
       the stem's weight gradient may differ, by fp32 summation order (same bf16 dY);
@@ -788,12 +757,10 @@ def test_schedule_switches_keep_the_gradients():
     widen, deepen, nc, B, size, seed = 0.5, 0.33, 10, 4, 320, 11
     x, tg = synth.batch(B, size, nc, seed)
     got = {}
-    for tag in ("default", "streams2", "unfused", "fused_wg", "single_wgrads"):
+    for tag in ("default", "unfused", "fused_wg", "single_wgrads"):
         torch.manual_seed(seed)
         net = Yolov5Network(3, nc, widen_factor=widen, deepen_factor=deepen)
         opts = EngineOptions.from_env()
-        if tag == "streams2":
-            opts.wgrad_streams = 2
         if tag == "unfused":
             opts.stem_bwd_fused = False
         if tag == "fused_wg":
@@ -810,7 +777,6 @@ def test_schedule_switches_keep_the_gradients():
         got[tag] = {k: p.grad.detach().clone() for k, p in net.named_parameters()}
     for k, g in got["default"].items():
         assert torch.isfinite(g).all()
-        assert torch.equal(got["streams2"][k], g), k
         assert torch.equal(got["fused_wg"][k], g), k
         if k == "backbone.stem.0.weight":
             top = g.abs().max().item()
@@ -824,55 +790,6 @@ def test_schedule_switches_keep_the_gradients():
             assert (got["single_wgrads"][k] - g).abs().max().item() <= 1e-4 * top + 1e-7, k
         else:
             assert torch.equal(got["single_wgrads"][k], g), k
-
-
-def test_pair_forward_switch_matches_two_launch_form():
-    """EngineOptions.pair_fwd (KODHIP_PAIR_FWD=1 | 2; off by default - measured slower): a CSP layer's main_conv +
-    short_conv (kod/nn/layers/csp.py:87-88, the same input) as ONE convolution launch with N = 2 * mid columns, their
-    pre-BN outputs the two channel halves of one tensor, one launch for both units' BatchNorm constants
-    (kodhip_bn_finalize_partials_pair) and one apply pass (kodhip_bn_silu_apply_pair; 2: the short half's apply on the side
-    stream).  The first pair of the network sees identical inputs in every form: its pre-BN outputs must be bit-identical
-    (the K order of an output element does not depend on the n tile), its batch statistics equal to fp32 rounding of a
-    different partial grouping; the loss and the weight gradients of the step stay within the bars of a changed summation
-    order; yv5m widths (mid = 48: slices at 96-byte offsets, padded-tap over-read into the zeroed tail) included."""
-    from object_detection_cib_amd.engine.options import EngineOptions
-    for widen, deepen in ((0.5, 0.33), (0.75, 0.67)):
-        nc, B, size, seed = 10, 4, 256, 13
-        x, tg = synth.batch(B, size, nc, seed)
-        got = {}
-        for mode in (0, 1, 2):
-            torch.manual_seed(seed)
-            net = Yolov5Network(3, nc, widen_factor=widen, deepen_factor=deepen)
-            opts = EngineOptions.from_env()
-            opts.pair_fwd = mode
-            net.engine_options = opts
-            net = net.cuda().train()
-            with torch.no_grad():
-                net.forward_raw(x.cuda())
-            eng = net.engine()
-            first = next(u for u in eng.exec_units if u.sibling is not None)
-            pair = (first, first.sibling)
-            assert (eng.ustate[first.name].pair is not None) == (mode != 0)
-            rec = {"raw": [eng.ustate[u.name].raw.float().cpu().clone() for u in pair],
-                   "aff": [eng.ustate[u.name].aff.cpu().clone() for u in pair],
-                   "act": [eng.act[u.dst.buf.name][..., u.dst.coff:u.dst.coff + u.cout].float().cpu().clone() for u in pair]}
-            for p in net.parameters():
-                p.grad = None
-            _, lr, tot = _step(net, x.cuda(), tg, size, B)
-            rec["loss"] = tot.item()
-            rec["grads"] = torch.cat([p.grad.flatten() for p in net.parameters()]).cpu()
-            rec["first_w"] = [dict(net.named_parameters())[u.name + ".0.weight"].grad.cpu().clone() for u in pair]
-            got[mode] = rec
-        ref = got[0]
-        for mode in (1, 2):
-            g = got[mode]
-            for k in range(2):
-                assert torch.equal(g["raw"][k], ref["raw"][k]), (widen, mode, k)
-                assert _rel(g["aff"][k], ref["aff"][k]) <= 1e-6, (widen, mode, k, _rel(g["aff"][k], ref["aff"][k]))
-                assert _rel(g["act"][k], ref["act"][k]) <= 1e-3, (widen, mode, k)
-            assert np.isfinite(g["loss"]) and abs(g["loss"] - ref["loss"]) <= 2e-2 * abs(ref["loss"]), (widen, mode, g["loss"], ref["loss"])
-            assert torch.isfinite(g["grads"]).all()
-        assert torch.equal(got[1]["grads"], got[2]["grads"])          # the same kernels on another stream
 
 
 def test_yv5m_bench_geometry_b64_640_deterministic_and_teacher_forced():

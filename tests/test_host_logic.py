@@ -221,7 +221,7 @@ def test_bench_self_launch_fails_loudly_when_a_rank_fails():
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
 
 
-def test_engine_options_from_env(monkeypatch):
+def test_engine_options_parse_env(monkeypatch):
     from object_detection_cib_amd.engine.options import EngineOptions
     for k in ("KODHIP_COMM_OVERLAP", "KODHIP_NO_DUAL", "KODHIP_FORCE_BM"):
         monkeypatch.delenv(k, raising=False)
@@ -234,16 +234,40 @@ def test_engine_options_from_env(monkeypatch):
     assert not o.comm_overlap and not o.dual_dgrad and o.native == {"KODHIP_FORCE_BM": "256"}
     assert o.as_dict()["native"]["KODHIP_FORCE_BM"] == "256"
     # the round-3 schedule switches: defaults and their environment spellings
-    for k in ("KODHIP_NO_DUAL_WGRAD", "KODHIP_STEM_BWD_FUSED", "KODHIP_WGRAD_STREAMS", "KODHIP_STEM_BWD_STREAM"):
+    for k in ("KODHIP_NO_DUAL_WGRAD", "KODHIP_STEM_BWD_FUSED", "KODHIP_STEM_BWD_STREAM"):
         monkeypatch.delenv(k, raising=False)
     o = EngineOptions.from_env()
-    assert o.dual_wgrad and o.stem_bwd_fused and o.wgrad_streams == 1 and not o.wgrad_reduce_batched
+    assert o.dual_wgrad and o.stem_bwd_fused
     monkeypatch.setenv("KODHIP_NO_DUAL_WGRAD", "1")
     monkeypatch.setenv("KODHIP_STEM_BWD_FUSED", "0")
-    monkeypatch.setenv("KODHIP_WGRAD_STREAMS", "2")
     monkeypatch.setenv("KODHIP_STEM_BWD_STREAM", "wg")
     o = EngineOptions.from_env()
-    assert not o.dual_wgrad and not o.stem_bwd_fused and o.wgrad_streams == 2 and o.native["KODHIP_STEM_BWD_STREAM"] == "wg"
+    assert not o.dual_wgrad and not o.stem_bwd_fused and o.native["KODHIP_STEM_BWD_STREAM"] == "wg"
+
+
+def test_native_knob_record_is_complete_and_current():
+    """EngineOptions.native records every knob the library reads, so a bench line can be attributed: (a) every KODHIP_*
+    name that csrc/ reads from the environment (getenv, and bn_knob in bn_act.hip) is in NATIVE_KNOBS - except the env
+    spelling of an EngineOptions field; (b) every NATIVE_KNOBS entry is still read somewhere in the package outside
+    options.py (csrc/, or Python: os.environ / EngineOptions.native)."""
+    import glob
+    import re
+    from object_detection_cib_amd.engine import options
+    pkg = os.path.dirname(os.path.dirname(os.path.abspath(options.__file__)))
+    native_src = glob.glob(os.path.join(pkg, "csrc", "*.hip")) + glob.glob(os.path.join(pkg, "csrc", "*.h"))
+    py_src = [p for p in glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True)
+              if os.path.abspath(p) != os.path.abspath(options.__file__)]
+    read_native = set()
+    for path in native_src:
+        read_native |= set(re.findall(r'\b(?:getenv|bn_knob)\(\s*"(KODHIP_\w+)"', open(path).read()))
+    read_py = set()
+    for path in py_src:
+        read_py |= set(re.findall(r'\b(?:environ\.get|environ\[|native\.get)\(?\s*"(KODHIP_\w+)"', open(path).read()))
+    assert "KODHIP_NO_FAST" in read_native and "KODHIP_LIB" in read_py        # (the patterns do find the readers)
+    opt_src = open(options.__file__).read()
+    field_env = set(re.findall(r'"(KODHIP_\w+)"', opt_src[opt_src.index("def from_env"):]))
+    assert sorted(read_native - field_env - set(options.NATIVE_KNOBS)) == []
+    assert sorted(set(options.NATIVE_KNOBS) - read_native - read_py) == []
 
 
 def test_backward_write_plan_and_fp32_accumulation_modes():

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of the replayed training step under environment switches, alternating in ONE session on ONE box (boxes differ
-# by +-1.5 %): tools/ab_bench.sh "KODHIP_WGRAD_FORK=legacy" "KODHIP_BRANCH_OVERLAP=0" ...   ("" = defaults)
+# by +-1.5 %): tools/ab_bench.sh "KODHIP_NO_DUAL_WGRAD=1" "KODHIP_BRANCH_OVERLAP=0" ...   ("" = defaults)
 set -o pipefail
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
