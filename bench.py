@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps 20 --warmup 5
     python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR      (+ the last timed step's outputs as DIR/*.npy)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full   (+ everything measured beside the headline, see below)
     python bench.py --gpus N ...                      (WORLD_SIZE unset: starts N fresh child processes itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -10,6 +11,11 @@
 One "step" = forward + target assignment + loss + backward + (gradient all-reduce) + Nesterov-SGD on a
 synthetic batch that is already resident in HBM (BASELINE configs[1]: yv5s, coco-zipf-like targets,
 batch 64 per GPU, 640 px, bf16 storage / fp32 accumulate).  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, (dump the outputs,) print the line.
+--full adds what runs of its own measure: the per-family kernel table and its roofline (eager profiling steps), the
+device clock stamps (KODHIP_DEBUG_STAMPS=1), the training-loop leg, the validation-loop and yv5m legs and the CPU
+baseline (--no-loop / --no-extra / --no-cpu-baseline leave parts of that out).
 """
 from __future__ import annotations
 
@@ -681,7 +687,11 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="images per GPU")
     ap.add_argument("--size", type=int, default=640)
     ap.add_argument("--variant", default="yv5s", choices=sorted(VARIANTS), help="network scale (yv5m = BASELINE configs[4])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: per-family kernel table and "
+                         "roofline, device clock stamps (KODHIP_DEBUG_STAMPS=1), training-loop, validation-loop and yv5m "
+                         "legs, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-sync-bn", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured hipGraph")
     ap.add_argument("--autograd", action="store_true",
@@ -691,8 +701,8 @@ def main():
     ap.add_argument("--timeout", type=float, default=900.0, help="self-launch: seconds before a hung job is stopped")
     ap.add_argument("--allow-fallback", action="store_true",
                     help=f"a result measured down the fallback ladder (\"degraded\": true) exits 0 instead of {EXIT_DEGRADED}")
-    ap.add_argument("--no-loop", action="store_true", help="skip the training-loop leg (device data pipeline -> captured step)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the validation-loop and yv5m legs")
+    ap.add_argument("--no-loop", action="store_true", help="--full: skip the training-loop leg (device data pipeline -> captured step)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the validation-loop and yv5m legs")
     ap.add_argument("--loop-steps", type=int, default=30)
     ap.add_argument("--loop-mixup", type=float, default=None, help="mixup probability of the loop leg (default 0 at N=1, 0.1 at N>1)")
     ap.add_argument("--loop-in-process", action="store_true", help="loop leg: host side of the data protocol in this process (round 3)")
@@ -860,12 +870,12 @@ def main():
     _beat("timed region done")
     if args.dump_outputs and rank == 0:        # before anything below runs the step again
         dump_outputs(args.dump_outputs, net, last, last_parts[0])
-    if eng.stamps_on:          # KODHIP_DEBUG_STAMPS=1: where the step's time goes, from device clock stamps
+    if args.full and eng.stamps_on:          # KODHIP_DEBUG_STAMPS=1: where the step's time goes, from device clock stamps
         stamp_report(eng, graph, step)
-    # per-kernel durations of every family: one extra eager step with HIP events around each launch on its launch
+    # --full: per-kernel durations of every family: one extra eager step with HIP events around each launch on its launch
     # stream, outside the timed region (events cannot be read back from inside a replayed graph); weight gradients
     # on the main stream for this step so that the families do not overlap each other
-    prof = profile_step(eng, step)
+    prof = profile_step(eng, step) if args.full else None
     if eng.peer is not None and eng.peer.timed_out():
         raise SystemExit(f"[bench rank {rank}] a SyncBN peer exchange gave up waiting for another rank: the run is invalid")
     per_rank = [round(B * args.steps / dt, 1)]
@@ -878,7 +888,7 @@ def main():
     loop = None
     _beat("profile step done")
     # (with collectives in the step every rank runs the leg - its replays contain the same RCCL calls - fed by its own producer)
-    if not args.no_loop and not args.autograd and graph is not None:
+    if args.full and not args.no_loop and not args.autograd and graph is not None:
         mix_p = args.loop_mixup if args.loop_mixup is not None else (0.1 if world > 1 else 0.0)      # configs[2]: "mosaic+mixup"
         barrier()
         try:            # (a leg that fails is reported as its error, the measured line stands - like the extra legs below)
@@ -895,11 +905,11 @@ def main():
                 loop["value"] = round(world * B / (max(lts) * 1e-3), 1)
             elif "error" not in loop:
                 loop = {"error": "the loop leg failed on another rank", "per_rank_ms_per_step": lts}
-    # further legs of the default single-GPU run (each reported beside `value`, none inside the timed region; a leg that
+    # further legs of the --full single-GPU run (each reported beside `value`, none inside the timed region; a leg that
     # fails is reported as its error, the line itself stands): the validation loop and the yv5m scale
     extra = {}
     _beat("loop leg done")
-    if world == 1 and not use_dist and not (args.no_extra or args.no_loop) and not args.autograd and use_graph and args.variant == "yv5s":
+    if args.full and world == 1 and not use_dist and not (args.no_extra or args.no_loop) and not args.autograd and use_graph and args.variant == "yv5s":
         for name, fn in (("validation", lambda: validation_leg(net, loss_fn, B, S, nc, device)),
                          ("yv5m", lambda: variant_leg("yv5m", B, S, nc, device))):
             try:
@@ -910,10 +920,6 @@ def main():
 
     if rank == 0:
         ips = world * B * args.steps / dt
-        # roofline: the kernel family with the largest share of the step (event-timed, see above)
-        table = family_table(prof)
-        top = table[0]
-        n_launch = max(top["launches"], 1)
         out = {
             "metric": f"images/sec YOLOv5{args.variant[-1]} {S}px train", "value": round(ips, 2), "unit": "images/sec",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -941,18 +947,23 @@ def main():
                               "achieved": round(ips / world * algo_bytes / 1e9, 1), "peak": HBM_PEAK / 1e9,
                               "unit": "GB/s", "frac": round(ips / world * algo_bytes / HBM_PEAK, 4),
                               "tflops": round(ips / world * algo_flop / 1e12, 1)},
-            "roofline": {"kernel": FAMILY_KERNELS.get(top["family"], top["family"]), "family": top["family"], "bound": "hbm",
-                         "achieved": top["GB/s"], "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": top["frac"],
-                         "traffic": pmc_traffic(top["family"], B, S) if args.variant == "yv5s" else None,
-                         "avg_launch_us": round(1e3 * top["ms"] / n_launch, 2), "launches": top["launches"],
-                         "algorithmic_bytes_per_launch_avg": round(1e6 * top["algorithmic_MB"] / n_launch),
-                         "share_of_step": top["share_of_step"]},
-            "families": table,
         }
+        if prof is not None:
+            # roofline: the kernel family with the largest share of the step (event-timed, see above)
+            table = family_table(prof)
+            top = table[0]
+            n_launch = max(top["launches"], 1)
+            out["roofline"] = {"kernel": FAMILY_KERNELS.get(top["family"], top["family"]), "family": top["family"], "bound": "hbm",
+                               "achieved": top["GB/s"], "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": top["frac"],
+                               "traffic": pmc_traffic(top["family"], B, S) if args.variant == "yv5s" else None,
+                               "avg_launch_us": round(1e3 * top["ms"] / n_launch, 2), "launches": top["launches"],
+                               "algorithmic_bytes_per_launch_avg": round(1e6 * top["algorithmic_MB"] / n_launch),
+                               "share_of_step": top["share_of_step"]}
+            out["families"] = table
         if loop is not None:
             out["loop"] = loop
         out.update(extra)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if dist is not None:

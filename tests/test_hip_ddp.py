@@ -215,7 +215,8 @@ def test_native_rccl_comm_and_captured_step(tmp_path):
 def test_bench_self_launch_runs_the_collective_path():
     """`python bench.py --gpus N` with WORLD_SIZE unset (the driver's plain command) starts the ranks itself.  Rehearsed
     here with one rank and KODHIP_FORCE_COLLECTIVES=1: a fresh child process, its own RCCL communicators, SyncBN sums +
-    gradient buckets (overlapped with backward, the default) inside the replayed hipGraph; ONE JSON line comes back."""
+    gradient buckets (overlapped with backward, the default) inside the replayed hipGraph; ONE JSON line comes back
+    (--full: with the family table and the training-loop leg, which run the collective path too)."""
     import json
     import subprocess
     import sys
@@ -223,7 +224,7 @@ def test_bench_self_launch_runs_the_collective_path():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["KODHIP_FORCE_COLLECTIVES"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--launch", "self", "--steps", "3",
-                        "--warmup", "2", "--batch", "8", "--size", "320", "--no-cpu-baseline", "--timeout", "400"],
+                        "--warmup", "2", "--batch", "8", "--size", "320", "--full", "--no-cpu-baseline", "--timeout", "400"],
                        capture_output=True, text=True, timeout=500, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
