@@ -231,6 +231,10 @@ int kodhip_sgd_nesterov(float* params, const float* grads, float* momentum_buf, 
                                                       flags = nesterov (smart_sgd.yaml: 1) + 2 maximize + 4 first step
                                                       (only read when dampening != 0), dampening */,
                         kodStream_t stream);
+/* kodhip_sgd_nesterov over the elements whose keep_mask byte (device, n bytes) is non-zero; the others (frozen tensors,
+   engine/freeze.py) are not touched: no weight decay, no momentum, no update */
+int kodhip_sgd_nesterov_masked(float* params, const float* grads, float* momentum_buf, const void* group_ids,
+                               const void* keep_mask, long n, const float* hyper, kodStream_t stream);
 int kodhip_fill_u32(void* p, uint32_t value, long n, kodStream_t stream);
 /* dst (device) <- src (PINNED host memory), bytes % 16 == 0, both 16-byte aligned: a kernel pulling the bytes through the
  * host memory's device mapping - the small per-step tables of the data path (kod/data/detection.py's per-sample results)

@@ -83,6 +83,7 @@ SIGNATURES = {
     "kodhip_upsample2x_bwd": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "kodhip_head_bwd_prep": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "kodhip_sgd_nesterov": (i32, [vp, vp, vp, vp, i64, vp, vp]),
+    "kodhip_sgd_nesterov_masked": (i32, [vp, vp, vp, vp, vp, i64, vp, vp]),
     "kodhip_fill_u32": (i32, [vp, u32, i64, vp]),
     "kodhip_pull_from_host": (i32, [vp, vp, i64, vp]),
     "kodhip_debug_stamp": (i32, [vp, vp]),

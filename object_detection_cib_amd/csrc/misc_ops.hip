@@ -622,6 +622,39 @@ __global__ void sgd_nesterov_kernel(float* p, const float* g, float* buf, const 
   *reinterpret_cast<f32x4*>(buf + i) = bv;
 }
 
+// sgd_nesterov_kernel for a freeze plan (engine/freeze.py): keep[i] == 0 marks an element of a frozen tensor, which no
+// weight decay, momentum or update touches (torch.optim.SGD skips a parameter whose .grad is None).  Per element: the
+// three head weights / biases share 64-element chunks.  Trainable elements compute exactly what the unmasked kernel does.
+__global__ void sgd_nesterov_masked_kernel(float* p, const float* g, float* buf, const unsigned char* gid,
+                                           const unsigned char* keep, long n, const float* hyper) {
+  long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i >= n) return;
+  unsigned char grp = gid[i >> 6];
+  if (grp > 2) return;
+  const uchar4 kv = *reinterpret_cast<const uchar4*>(keep + i);
+  const unsigned char kk[4] = {kv.x, kv.y, kv.z, kv.w};
+  if ((kk[0] | kk[1] | kk[2] | kk[3]) == 0) return;
+  const float lr = hyper[grp], mu = hyper[3 + grp], wd = hyper[6 + grp], gscale = hyper[9];
+  const int flags = (int)hyper[10];
+  const bool nesterov = (flags & 1) != 0, maximize = (flags & 2) != 0, first = (flags & 4) != 0;
+  const float undamped = 1.0f - hyper[11];
+  f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);
+  f32x4 gv = kod_load_once<f32x4>(g + i);
+  f32x4 bv = *reinterpret_cast<const f32x4*>(buf + i);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (!kk[e]) continue;
+    float gg = gv[e] * gscale;
+    if (maximize) gg = -gg;
+    if (wd != 0.f) gg = gg + wd * pv[e];
+    float b = (first || mu == 0.f) ? gg : mu * bv[e] + undamped * gg;
+    bv[e] = b;
+    pv[e] = pv[e] - lr * (nesterov ? gg + mu * b : b);
+  }
+  *reinterpret_cast<f32x4*>(p + i) = pv;
+  *reinterpret_cast<f32x4*>(buf + i) = bv;
+}
+
 __global__ void fill_u32_kernel(uint32_t* p, uint32_t v, long n) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
@@ -761,6 +794,16 @@ int kodhip_sgd_nesterov(float* params, const float* grads, float* momentum_buf, 
   hipLaunchKernelGGL(sgd_nesterov_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, stream, params, grads, momentum_buf,
                      (const unsigned char*)group_ids, n, hyper);
   KOD_LAUNCH_CHECK("sgd_nesterov");
+  return KOD_OK;
+}
+
+int kodhip_sgd_nesterov_masked(float* params, const float* grads, float* momentum_buf, const void* group_ids,
+                               const void* keep_mask, long n, const float* hyper, hipStream_t stream) {
+  KOD_CHECK_ARG(params && grads && momentum_buf && group_ids && keep_mask && hyper && n > 0 && n % 64 == 0,
+                "sgd_nesterov_masked: bad args");
+  hipLaunchKernelGGL(sgd_nesterov_masked_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, stream, params, grads, momentum_buf,
+                     (const unsigned char*)group_ids, (const unsigned char*)keep_mask, n, hyper);
+  KOD_LAUNCH_CHECK("sgd_nesterov_masked");
   return KOD_OK;
 }
 

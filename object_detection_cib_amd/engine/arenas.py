@@ -23,6 +23,37 @@ def _pad(n: int, a: int = 64) -> int:
     return (n + a - 1) // a * a
 
 
+def arena_layout(g: Graph, numel: Dict[str, int]):
+    """The flat parameter arena (pure host logic): parameters in forward execution order, each set padded to 64 elements.
+    Returns (name -> (offset, numel), optimizer group per 64-element chunk, arena size, offset where each exec unit's
+    parameters begin - conv units, then heads)."""
+    off = 0
+    layout = {}                   # name -> (offset, numel)
+    gid = []
+
+    def place(names, group):
+        nonlocal off
+        start = off
+        for n in names:
+            layout[n] = (off, numel[n])
+            off += numel[n]
+        end = _pad(off)
+        gid.extend([group] * ((end - start) // 64))
+        off = end
+
+    exec_units = [op.unit for op in g.ops if op.kind == "conv"]
+    for u in exec_units:
+        place([u.name + ".0.weight"], 1)
+        place([u.name + ".1.weight"], 2)
+        place([u.name + ".1.bias"], 0)
+    for h in g.heads:
+        place([head_param(h, k, "weight") for k in ("box", "obj", "cls")], 1)
+        place([head_param(h, k, "bias") for k in ("box", "obj", "cls")], 0)
+    unit_starts = ([layout[u.name + '.0.weight'][0] for u in exec_units]
+                   + [layout[head_param(h, 'box', 'weight')][0] for h in g.heads])
+    return layout, gid, off, unit_starts
+
+
 class _UnitState:
     """Per conv unit: arena offsets (set once) and the current shape set's buffers / launch state."""
     __slots__ = ("u", "w_off", "g_off", "b_off", "f_off", "d_off", "Kp", "Kdp", "rs_off", "stats", "T",
@@ -34,35 +65,11 @@ class ArenaMixin:
     # ------------------------------------------------------------------ arenas
     def _build_arenas(self, device):
         g = self.g
-        order = []                    # (param name, group) in forward execution order, packed sets
         self.ustate: Dict[str, _UnitState] = {}
-        off = 0
-        layout = {}                   # name -> (offset, numel)
-        gid = []
-
-        def place(names, group):
-            nonlocal off
-            start = off
-            for n in names:
-                p = self.params[n]
-                layout[n] = (off, p.numel())
-                off += p.numel()
-            end = _pad(off)
-            gid.extend([group] * ((end - start) // 64))
-            off = end
-
+        layout, gid, off, self.unit_starts = arena_layout(g, {n: p.numel() for n, p in self.params.items()})
         exec_units = [op.unit for op in g.ops if op.kind == "conv"]
-        for u in exec_units:
-            place([u.name + ".0.weight"], 1)
-            place([u.name + ".1.weight"], 2)
-            place([u.name + ".1.bias"], 0)
-        for h in g.heads:
-            place([head_param(h, k, "weight") for k in ("box", "obj", "cls")], 1)
-            place([head_param(h, k, "bias") for k in ("box", "obj", "cls")], 0)
         self.n_arena = off
         self.layout = layout
-        self.unit_starts = ([layout[u.name + '.0.weight'][0] for u in exec_units]
-                            + [layout[head_param(h, 'box', 'weight')][0] for h in g.heads])
         self.p_arena = torch.zeros(off, dtype=torch.float32, device=device)
         self.g_arena = [torch.zeros(off, dtype=torch.float32, device=device) for _ in range(2)]
         self.g_cur = 0
@@ -159,6 +166,14 @@ class ArenaMixin:
         self.sgd_nesterov = True          # FusedSGD(nesterov=...): smart_sgd.yaml's default, kod/configs/nn/optimizers/smart_sgd.yaml
         self.sgd_dampening, self.sgd_maximize = 0.0, False      # torch.optim.SGD(dampening=, maximize=) through FusedSGD
         self.sgd_steps = 0                # optimizer steps taken (torch's first step copies the gradient into the momentum buffer)
+        self.freeze = None                # engine/freeze.py FreezePlan of the last training forward (None: never read)
+        self.keep_mask = None             # u8 per arena element: 0 = frozen (masked SGD), only for a non-default plan
+        self.stepped = None               # names with a momentum buffer when not all of them (see note_sgd_step)
+        self._freeze_params = None        # parameters in arena order (freeze_flags)
+        self._freeze_flags = None
+        self._keep_masks = {}             # freeze key -> keep mask
+        self._f32_frozen = {}             # freeze key -> F32Plan over the writes backward still issues
+        self._stepped_key = None
         self._hyper_args = None
         # pinned staging ring: the H2D copy is asynchronous, so a slot is not rewritten for the next 15 uploads
         self._hyper_host = [torch.zeros(12, dtype=torch.float32).pin_memory() for _ in range(16)]
@@ -179,21 +194,108 @@ class ArenaMixin:
         self._packed_version = self.param_version
 
     def _publish_grads(self):
-        """Expose the arena slices as .grad (accumulating into an existing .grad like autograd would)."""
+        """Expose the arena slices as .grad (accumulating into an existing .grad like autograd would).  Under a freeze plan
+        (engine/freeze.py) a frozen tensor keeps .grad = None, as torch leaves it."""
         cur = self.g_arena[self.g_cur]
         other = self.g_arena[self.g_cur ^ 1]
-        first = next(iter(self.layout))
+        fz = self.freeze_active()
+        names = self.layout if fz is None else fz.trainable
+        if not names:                            # (a sub-network with every parameter frozen: only input gradients)
+            for n in self.layout:
+                self.params[n].grad = None
+            self.g_cur ^= 1
+            return
+        first = next(iter(names))
         existing = self.params[first].grad
         if existing is not None and existing.data_ptr() == self._grad_view(first, other).data_ptr():
             self.wait_grads()
             other.add_(cur)                      # gradient accumulation across backward() calls
             return
-        for n in self.layout:
+        for n in names:
             p = self.params[n]
             if p.grad is not None and p.grad.data_ptr() != self._grad_view(n, cur).data_ptr():
                 raise RuntimeError("mixed external .grad tensors are not supported; call zero_grad(set_to_none=True)")
             p.grad = self._grad_view(n, cur)
+        if fz is not None:
+            for n in fz.frozen:
+                self.params[n].grad = None
         self.g_cur ^= 1
+
+    # ------------------------------------------------------------------ freezing (engine/freeze.py)
+    def freeze_flags(self):
+        """requires_grad of every parameter, in arena order"""
+        if self._freeze_params is None:
+            self._freeze_params = [self.params[n] for n in self.layout]
+        return tuple(p.requires_grad for p in self._freeze_params)
+
+    def sync_freeze(self):
+        """Read requires_grad and rebuild the freeze plan when it moved.  Called at every training forward; the common case
+        is one tuple of flags compared with the last one."""
+        flags = self.freeze_flags()
+        if flags == self._freeze_flags:
+            return self.freeze
+        from .freeze import build_freeze_plan
+        plan = build_freeze_plan(self.g, dict(zip(self.layout, flags)))
+        if self.freeze is None or self.freeze.key != plan.key:
+            self._on_freeze_change(plan)           # (raises on a rank mismatch before the plan is adopted)
+        self._freeze_flags, self.freeze = flags, plan
+        return plan
+
+    def freeze_active(self):
+        """The freeze plan when it differs from the default (everything trainable), else None: the default runs the
+        program that has no freeze logic in it."""
+        fz = self.freeze
+        return None if (fz is None or fz.is_default) else fz
+
+    def _on_freeze_change(self, plan):
+        if self.collectives and self.world_size > 1:
+            # every rank must run the same backward program (the same collectives): the freeze set is compared across
+            # the group whenever it changes - so every rank changes it at the same step, as a training script does
+            import torch.distributed as dist
+            keys = [None] * self.world_size
+            dist.all_gather_object(keys, plan.key, group=self.process_group)
+            if any(k != plan.key for k in keys):
+                raise RuntimeError("the ranks disagree on which parameters are frozen (requires_grad): every rank must "
+                                   "freeze the same set")
+        if plan.is_default:
+            self.keep_mask = None
+            return
+        # one mask per freeze set, kept for the engine's lifetime: a captured step bakes the mask's address in
+        keep = self._keep_masks.get(plan.key)
+        if keep is None:
+            keep = torch.ones(self.n_arena, dtype=torch.uint8, device=self.device)
+            for n in plan.frozen:
+                o, k = self.layout[n]
+                keep[o:o + k] = 0
+            self._keep_masks[plan.key] = keep
+        self.keep_mask = keep
+
+    def _frozen_f32plan(self, fz):
+        """EngineOptions.dx_accum_fp32 under a freeze plan: the fp32-accumulation modes planned over the gradient writes
+        that backward still issues (engine/plan.py; skipped writers change who is first / last of a buffer)."""
+        from .plan import backward_writes, plan_f32_accumulation
+        cached = self._f32_frozen.get(fz.key)
+        if cached is None:
+            ws, _ = backward_writes(self.g, {v.name for v in self._dual.values()})
+            kept = []
+            for w in ws:
+                kind, ident = w.key
+                if kind == "dgrad":
+                    ok = fz.units[ident].needs_in_grad
+                elif kind == "res":
+                    ok = fz.units[ident].res_grad
+                elif kind == "head":
+                    ok = fz.heads[ident].needs_in_grad
+                else:
+                    ok = fz.op_in_grad[ident]
+                if ok:
+                    kept.append(w)
+            cached = plan_f32_accumulation(kept, {b.name: b.C for b in self.g.bufs})
+            self._f32_frozen[fz.key] = cached
+        for name in cached.shadow_bufs:           # (a buffer that needs a shadow only with fewer writers)
+            if name not in self.gact32:
+                self.gact32[name] = torch.empty(self.gact[name].shape, dtype=torch.float32, device=self.device)
+        return cached
 
     def current_grad_arena(self):
         """Arena holding the gradients published by the last backward()."""
@@ -228,9 +330,15 @@ class ArenaMixin:
 
     def sgd_step_device(self):
         """SGD with whatever is in self.hyper (device, 12 floats) - the graph-capturable form."""
-        _lib.check(self.lib.kodhip_sgd_nesterov(self.p_arena.data_ptr(), self.current_grad_arena().data_ptr(),
-                                                self.m_arena.data_ptr(), self.gid.data_ptr(), self.n_arena,
-                                                self.hyper.data_ptr(), self._stream()), "sgd")
+        if self.freeze_active() is None:
+            _lib.check(self.lib.kodhip_sgd_nesterov(self.p_arena.data_ptr(), self.current_grad_arena().data_ptr(),
+                                                    self.m_arena.data_ptr(), self.gid.data_ptr(), self.n_arena,
+                                                    self.hyper.data_ptr(), self._stream()), "sgd")
+        else:       # frozen tensors: no weight decay, no momentum, no update (torch.optim.SGD skips p.grad is None)
+            _lib.check(self.lib.kodhip_sgd_nesterov_masked(self.p_arena.data_ptr(), self.current_grad_arena().data_ptr(),
+                                                           self.m_arena.data_ptr(), self.gid.data_ptr(),
+                                                           self.keep_mask.data_ptr(), self.n_arena,
+                                                           self.hyper.data_ptr(), self._stream()), "sgd_masked")
         self.param_version += 1
         self.note_sgd_step()
 
@@ -238,6 +346,15 @@ class ArenaMixin:
         """one optimizer step has run (eagerly, or inside a replayed graph): with dampening the first step's flag must leave
         the device block before the next one"""
         self.sgd_steps += 1
+        # which tensors own a momentum buffer (torch's optimizer state has one only for tensors stepped at least once):
+        # None = all of them
+        fz = self.freeze_active()
+        if fz is None:
+            self.stepped, self._stepped_key = None, None
+        elif fz.key != self._stepped_key:
+            self._stepped_key = fz.key
+            if self.sgd_steps == 1 or self.stepped is not None:
+                self.stepped = (self.stepped or set()) | set(fz.trainable)
         if self.sgd_dampening != 0.0 and self.sgd_steps == 1 and self._hyper_args is not None:
             self.set_hyper(*self._hyper_args)
 

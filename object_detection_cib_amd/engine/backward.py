@@ -17,6 +17,7 @@ import torch
 from .. import _lib
 from .graph import Graph, ConvUnit, HeadUnit, View, Buf, head_param
 from .ddp import plan_buckets, launch_bucket
+from .freeze import trainable_span
 
 
 class BackwardMixin:
@@ -36,6 +37,12 @@ class BackwardMixin:
         pa = self.p_arena.data_ptr()
         wgp = self.wg_part.data_ptr()
         touched = set()            # grad buffers already holding a (partial) sum
+        # freeze plan (engine/freeze.py), None when everything is trainable: then this is the program without any freeze
+        # logic.  With one: nothing for units in the no-grad region, no data gradient that no trainable tensor needs,
+        # no weight gradient of a frozen weight
+        fz = self.freeze_active()
+        if fz is not None:
+            fz.require_trainable()
         # Weight gradients run on a side stream: dW of a layer is off the critical path (bn-bwd -> dgrad -> next
         # layer), so it fills the tails of the small kernels on the main stream and, under SyncBN, the latency of
         # the per-layer statistic all-reduce.  All wgrads share one stream (and the split-K scratch) => ordered.
@@ -133,11 +140,13 @@ class BackwardMixin:
 
         op_index = {id(o): i for i, o in enumerate(self.g.ops)}
 
+        f32plan = self._f32plan if (fz is None or self._f32plan is None) else self._frozen_f32plan(fz)
+
         def f32(kind, ident, v: View):
             """(bits 8.. of the `accumulate` argument, fp32 shadow pointer) of one gradient-buffer write (engine/plan.py)"""
-            if self._f32plan is None:
+            if f32plan is None:
                 return 0, None
-            mode = self._f32plan.modes.get((kind, op_index[id(ident)] if kind in ("up", "pool") else ident), 0)
+            mode = f32plan.modes.get((kind, op_index[id(ident)] if kind in ("up", "pool") else ident), 0)
             sh = self.gact32.get(v.buf.name)
             return mode << 8, (sh.data_ptr() if (sh is not None and mode in (1, 2, 3)) else None)
         self._f32 = f32
@@ -156,8 +165,9 @@ class BackwardMixin:
         self._pending = []
         buckets = {}
         if self.collectives:
+            first = 0 if fz is None else trainable_span(self.unit_starts, fz, self.layout)
             buckets = {trig: (lo, hi) for trig, lo, hi in plan_buckets(self.unit_starts, self.n_arena,
-                                                                        max(self.bucket_bytes // 4, 1))}
+                                                                        max(self.bucket_bytes // 4, 1), first)}
         unit_i = len(self.unit_starts)
         pool_i = len(self.pool_idx)
         head_i = len(self.g.heads)
@@ -175,8 +185,9 @@ class BackwardMixin:
                 bc = self.comm_buckets if (cs is not None and self.comm_buckets is not None) else self.comm
                 # on the weight-gradient stream the bucket's last weight gradient has already waited for an event
                 # recorded behind every BatchNorm / bias gradient of the bucket (fork_point): no new edge from the main chain
+                # (under a freeze plan the bucket's last unit may launch no weight gradient: wait for the main stream)
                 self._pending.append(launch_bucket(ga, lo, hi, self.process_group, cs, bc, also_after=wg,
-                                                   wait_caller=not (cs is not None and cs is wg)))
+                                                   wait_caller=not (cs is not None and cs is wg) or fz is not None))
             due.clear()
         self._launch_due = launch_due
 
@@ -266,6 +277,10 @@ class BackwardMixin:
             if op.kind == "head":
                 head_i -= 1
                 hu: HeadUnit = op.unit
+                hf = fz.heads[hu.name] if fz is not None else None
+                if hf is not None and not hf.needs_out_grad:
+                    bucket_tick()
+                    continue
                 hs = self.hstate[hu.name]
                 gten = head_grads[head_i].contiguous()
                 assert gten.shape == (B, A, hs["H"], hs["W"], 5 + nc) and gten.dtype == torch.float32
@@ -287,23 +302,34 @@ class BackwardMixin:
                                              gp + 4 * offs[0], gp + 4 * offs[1], gp + 4 * offs[2],
                                              B, hs["H"] * hs["W"], A, nc, self.head_npad, hs_), hu.name)
                 fork_point(hstream)
-                acc = acc_flag(src)
-                fm, fptr = f32("head", hu.name, src)
-                e0 = self._t0()
-                chk(lib.kodhip_conv_dgrad(hs["dy"].data_ptr(), dp + 2 * hs["d_off"], self._ptr(src, True),
-                                          B, hs["H"], hs["W"], src.buf.C, src.coff, hu.cin,
-                                          self.head_npad, 1, 1, 1, 1, 0, 0, hs["Kdp"], self.head_npad, 0,
-                                          acc | fm, fptr, hs_), hu.name + ".dgrad")
-                self._t1(e0, "dgrad", 2.0 * hs["M"] * (self.head_npad + hu.cin), name=hu.name)
-                if side:
+                if hf is None or hf.needs_in_grad:
+                    acc = acc_flag(src)
+                    fm, fptr = f32("head", hu.name, src)
+                    e0 = self._t0()
+                    chk(lib.kodhip_conv_dgrad(hs["dy"].data_ptr(), dp + 2 * hs["d_off"], self._ptr(src, True),
+                                              B, hs["H"], hs["W"], src.buf.C, src.coff, hu.cin,
+                                              self.head_npad, 1, 1, 1, 1, 0, 0, hs["Kdp"], self.head_npad, 0,
+                                              acc | fm, fptr, hs_), hu.name + ".dgrad")
+                    self._t1(e0, "dgrad", 2.0 * hs["M"] * (self.head_npad + hu.cin), name=hu.name)
+                    if side:
+                        ev = torch.cuda.Event()
+                        ev.record(hstream)
+                        grad_events[src.buf.name] = ev
+                elif side:                 # (the bias gradients of the side chain: joined before they are published)
                     ev = torch.cuda.Event()
                     ev.record(hstream)
-                    grad_events[src.buf.name] = ev
-                timed_wgrad(hu.name, 2.0 * hs["M"] * (hu.cin + self.head_npad),
-                            self._ptr(src), hs["dy"].data_ptr(), wgp, gp + 4 * hs["w_off"],
-                            B, hs["H"], hs["W"], src.buf.C, src.coff, hu.cin,
-                            self.head_npad, 1, 1, 1, 1, 0, 0, hs["Kp"], self.head_npad, 0, A * (5 + nc), 0, 1.0)
+                    grad_events["head:" + hu.name] = ev
+                if hf is None or any(hf.w_trainable):
+                    timed_wgrad(hu.name, 2.0 * hs["M"] * (hu.cin + self.head_npad),
+                                self._ptr(src), hs["dy"].data_ptr(), wgp, gp + 4 * hs["w_off"],
+                                B, hs["H"], hs["W"], src.buf.C, src.coff, hu.cin,
+                                self.head_npad, 1, 1, 1, 1, 0, 0, hs["Kp"], self.head_npad, 0, A * (5 + nc), 0, 1.0)
+                else:
+                    self._fork_ev = None
                 flush_wgrads()
+            elif fz is not None and op.kind in ("up", "pool") and not fz.op_in_grad[len(rops) - ri]:
+                if op.kind == "pool":          # nothing upstream of this pass-through needs its gradient
+                    pool_i -= 1
             elif op.kind == "up":
                 h, w = H // op.src.stride, W // op.src.stride
                 chk(lib.kodhip_upsample2x_bwd(self._ptr(op.dst, True), op.dst.buf.C, op.dst.coff,
@@ -324,6 +350,10 @@ class BackwardMixin:
                         (rccl_sync or rops[ri].unit.name in self._dual):
                     group.append(rops[ri].unit)
                     ri += 1
+                if fz is not None:
+                    self._bwd_group_frozen(fz, group, bn_bwd_stats, bucket_tick, B, H, W, s, gp, pa, dp, wgp, acc_flag,
+                                           timed_wgrad)
+                    continue
                 bn_bwd_stats(group)
                 dual = len(group) == 2 and group[1].name in self._dual          # [short, main]: one data-gradient launch
                 for u in group:
@@ -350,10 +380,43 @@ class BackwardMixin:
             return [self.gact[v.buf.name][..., v.coff:v.coff + v.C].permute(0, 3, 1, 2).float() if v.buf.name in touched
                     else torch.zeros((B, v.C, H // v.stride, W // v.stride), device=self.device) for v in self.g.inputs]
 
-    def _bwd_unit(self, u, B, H, W, s, gp, pa, dp, wgp, acc_flag, timed_wgrad, dgrad="own", partner=None, dual_w=False):
+    def _bwd_group_frozen(self, fz, group, bn_bwd_stats, bucket_tick, B, H, W, s, gp, pa, dp, wgp, acc_flag, timed_wgrad):
+        """_bwd_unit over a unit group ([unit] or [short_conv, main_conv]) under a freeze plan (engine/freeze.py): units
+        outside the plan's grad region are skipped (their bucket tick stays, in order), the pair's dual forms are used only
+        when both partners run them - one data gradient when the shared input needs a gradient, one weight gradient when
+        both weights are trainable - and fall back to the single forms otherwise."""
+        runs = [u for u in group if fz.unit_runs(u)]
+        if len(runs) == 2:
+            din = fz.units[runs[0].name].needs_in_grad
+            dual = din and runs[1].name in self._dual
+            dual_w = dual and self.ustate[runs[1].name].wg_dual > 0 and \
+                fz.units[runs[0].name].w_trainable and fz.units[runs[1].name].w_trainable
+        else:
+            dual = dual_w = False
+            if len(group) == 2 and len(runs) == 1:
+                # a CSP entry pair reads one full buffer: the partner outside the grad region means it needs no data gradient
+                assert not fz.units[runs[0].name].needs_in_grad, (group[0].name, group[1].name)
+        if runs:
+            bn_bwd_stats(runs)
+        for u in group:
+            if u in runs:
+                f = fz.units[u.name]
+                if dual:
+                    mode = "skip" if u is runs[0] else "dual"
+                else:
+                    mode = "own" if f.needs_in_grad else "none"
+                self._bwd_unit(u, B, H, W, s, gp, pa, dp, wgp, acc_flag, timed_wgrad, dgrad=mode,
+                               partner=runs[0] if (dual and u is runs[1]) else None, dual_w=dual_w,
+                               w_grad=f.w_trainable, res_grad=f.res_grad)
+            bucket_tick()
+
+    def _bwd_unit(self, u, B, H, W, s, gp, pa, dp, wgp, acc_flag, timed_wgrad, dgrad="own", partner=None, dual_w=False,
+                  w_grad=True, res_grad=True):
         """bn/silu backward apply -> data gradient -> weight gradient of one conv unit (coefficients already in st.coef).
         dgrad: "own" = this unit's launch; "skip" = none (a fused short_conv: its main_conv's launch covers it);
-        "dual" = one launch for this unit and `partner` (kodhip_conv_dgrad_dual)."""
+        "dual" = one launch for this unit and `partner` (kodhip_conv_dgrad_dual); "none" = no data gradient (freeze plan:
+        nothing upstream needs it).  w_grad / res_grad (freeze plan): the weight gradient / the residual pass-through is
+        needed."""
         lib, chk = self.lib, _lib.check
         st = self.ustate[u.name]
         C_ = u.cout
@@ -361,6 +424,11 @@ class BackwardMixin:
         dA = u.dst
         res = u.residual
         self._stamp("m:" + u.name)
+        if not res_grad:
+            res = None
+        if not (w_grad or res is not None or dgrad != "none"):
+            self._flush_wgrads()               # (only the BatchNorm affine gradients, written by the coefficient kernel)
+            return
         if st.stem_fused and res is None:
             # the stem has no data gradient: dY = f(dA, y) is formed inside its weight gradient and never written
             # (csrc/conv_wgrad.hip conv_stem_bwd_fused_kernel); the launch joins the weight-gradient stream behind the
@@ -402,38 +470,40 @@ class BackwardMixin:
                 self._wg_hold[0] = True
                 return
             if dgrad == "skip":
-                timed_wgrad(u.name, 2.0 * (B * st.H * st.W * u.cin + st.M * C_),
-                            self._ptr(u.src), st.raw.data_ptr(), wgp, gp + 4 * st.w_off,
-                            *geo, st.Kp, st.raw_ld, 0, C_, 0, 1.0)
+                if w_grad:
+                    timed_wgrad(u.name, 2.0 * (B * st.H * st.W * u.cin + st.M * C_),
+                                self._ptr(u.src), st.raw.data_ptr(), wgp, gp + 4 * st.w_off,
+                                *geo, st.Kp, st.raw_ld, 0, C_, 0, 1.0)
                 return
-            fm, fptr = self._f32("dgrad", u.name, u.src)
-            acc_src = acc_flag(u.src) | fm
-            in_px = B * st.H * st.W
-            # dY read once, dX written once (+ read when accumulating), + the re-read of the producers' pre-BN
-            # tensors when this launch carries their BatchNorm-backward reduction
-            nb = 2.0 * st.M * C_ + (4.0 if acc_src & 1 else 2.0) * in_px * u.cin
-            if st.segs is not None:
-                nb += 2.0 * in_px * sum(sg.ch_count for sg in st.segs)
-            e0 = self._t0()
-            if dgrad == "dual":
-                ps = self.ustate[partner.name]
-                nb += 2.0 * ps.M * partner.cout
-                fn = lib.kodhip_conv_dgrad_dual if st.segs is None else lib.kodhip_conv_dgrad_dual_bnred
-                chk(fn(st.raw.data_ptr(), dp + 2 * st.d_off, ps.raw.data_ptr(), dp + 2 * ps.d_off, self._ptr(u.src, True),
-                       B, st.H, st.W, u.src.buf.C, u.src.coff, u.cin, C_, st.Kdp, st.raw_ld, 0, acc_src, fptr, *fz, s), u.name + ".dgrad2")
-            elif u.k == 3 and u.s == 2 and u.p == 1:
-                if st.s2_fold:
-                    fn = lib.kodhip_conv_dgrad_s2f if st.segs is None else lib.kodhip_conv_dgrad_s2f_bnred
+            if dgrad != "none":
+                fm, fptr = self._f32("dgrad", u.name, u.src)
+                acc_src = acc_flag(u.src) | fm
+                in_px = B * st.H * st.W
+                # dY read once, dX written once (+ read when accumulating), + the re-read of the producers' pre-BN
+                # tensors when this launch carries their BatchNorm-backward reduction
+                nb = 2.0 * st.M * C_ + (4.0 if acc_src & 1 else 2.0) * in_px * u.cin
+                if st.segs is not None:
+                    nb += 2.0 * in_px * sum(sg.ch_count for sg in st.segs)
+                e0 = self._t0()
+                if dgrad == "dual":
+                    ps = self.ustate[partner.name]
+                    nb += 2.0 * ps.M * partner.cout
+                    fn = lib.kodhip_conv_dgrad_dual if st.segs is None else lib.kodhip_conv_dgrad_dual_bnred
+                    chk(fn(st.raw.data_ptr(), dp + 2 * st.d_off, ps.raw.data_ptr(), dp + 2 * ps.d_off, self._ptr(u.src, True),
+                           B, st.H, st.W, u.src.buf.C, u.src.coff, u.cin, C_, st.Kdp, st.raw_ld, 0, acc_src, fptr, *fz, s), u.name + ".dgrad2")
+                elif u.k == 3 and u.s == 2 and u.p == 1:
+                    if st.s2_fold:
+                        fn = lib.kodhip_conv_dgrad_s2f if st.segs is None else lib.kodhip_conv_dgrad_s2f_bnred
+                    else:
+                        fn = lib.kodhip_conv_dgrad_s2 if st.segs is None else lib.kodhip_conv_dgrad_s2_bnred
+                    chk(fn(st.raw.data_ptr(), dp + 2 * st.d_off, self._ptr(u.src, True),
+                           B, st.H, st.W, u.src.buf.C, u.src.coff, u.cin, C_, st.raw_ld, 0,
+                           acc_src, fptr, *fz, s), u.name + ".dgrad")
                 else:
-                    fn = lib.kodhip_conv_dgrad_s2 if st.segs is None else lib.kodhip_conv_dgrad_s2_bnred
-                chk(fn(st.raw.data_ptr(), dp + 2 * st.d_off, self._ptr(u.src, True),
-                       B, st.H, st.W, u.src.buf.C, u.src.coff, u.cin, C_, st.raw_ld, 0,
-                       acc_src, fptr, *fz, s), u.name + ".dgrad")
-            else:
-                fn = lib.kodhip_conv_dgrad if st.segs is None else lib.kodhip_conv_dgrad_bnred
-                chk(fn(st.raw.data_ptr(), dp + 2 * st.d_off, self._ptr(u.src, True),
-                       *geo, st.Kdp, st.raw_ld, 0, acc_src, fptr, *fz, s), u.name + ".dgrad")
-            self._t1(e0, "dgrad" if st.segs is None else "dgrad+bn_reduce", nb, name=u.name + ("+" + partner.name if dgrad == "dual" else ""))
+                    fn = lib.kodhip_conv_dgrad if st.segs is None else lib.kodhip_conv_dgrad_bnred
+                    chk(fn(st.raw.data_ptr(), dp + 2 * st.d_off, self._ptr(u.src, True),
+                           *geo, st.Kdp, st.raw_ld, 0, acc_src, fptr, *fz, s), u.name + ".dgrad")
+                self._t1(e0, "dgrad" if st.segs is None else "dgrad+bn_reduce", nb, name=u.name + ("+" + partner.name if dgrad == "dual" else ""))
         if dgrad == "dual" and dual_w:
             ps = self.ustate[partner.name]
             self._wg_hold[0] = False
@@ -445,9 +515,10 @@ class BackwardMixin:
             return
         cin_true = 3 if u.stem else u.cin
         in_px_w = B * H * W if u.stem else B * st.H * st.W
-        timed_wgrad(u.name, 2.0 * (in_px_w * cin_true + st.M * C_),
-                    self._ptr(u.src), st.raw.data_ptr(), wgp, gp + 4 * st.w_off,
-                    *geo, st.Kp, st.raw_ld, 0, C_, 1 if u.stem else 0, 1.0)
+        if w_grad:
+            timed_wgrad(u.name, 2.0 * (in_px_w * cin_true + st.M * C_),
+                        self._ptr(u.src), st.raw.data_ptr(), wgp, gp + 4 * st.w_off,
+                        *geo, st.Kp, st.raw_ld, 0, C_, 1 if u.stem else 0, 1.0)
         self._flush_wgrads()           # this unit's - and a fused short_conv partner's - weight gradients: after the dgrad
 
 

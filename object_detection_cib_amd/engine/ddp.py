@@ -11,20 +11,22 @@ from typing import List, Sequence, Tuple
 import torch
 
 
-def plan_buckets(unit_starts: Sequence[int], n_arena: int, bucket_elems: int) -> List[Tuple[int, int, int]]:
+def plan_buckets(unit_starts: Sequence[int], n_arena: int, bucket_elems: int, first_unit: int = 0) -> List[Tuple[int, int, int]]:
     """unit_starts[i] = arena offset where exec unit i's parameters begin (forward order, ascending).
 
     Gradients complete back-to-front.  Returns [(trigger_unit_index, lo, hi)]: once unit `trigger`'s wgrad has
-    been enqueued, arena[lo:hi] is final and can be all-reduced.  Buckets tile [0, n_arena) exactly."""
+    been enqueued, arena[lo:hi] is final and can be all-reduced.  Buckets tile [0, n_arena) exactly; with
+    first_unit > 0 (a frozen prefix, engine/freeze.py trainable_span) they tile [unit_starts[first_unit], n_arena)."""
     out = []
     hi = n_arena
-    for i in range(len(unit_starts) - 1, -1, -1):
+    base = unit_starts[first_unit] if first_unit > 0 else 0
+    for i in range(len(unit_starts) - 1, first_unit - 1, -1):
         lo = unit_starts[i]
-        if hi - lo >= bucket_elems or i == 0:
-            lo = 0 if i == 0 else lo
+        if hi - lo >= bucket_elems or i == first_unit:
+            lo = base if i == first_unit else lo
             out.append((i, lo, hi))
             hi = lo
-    assert hi == 0
+    assert hi == base
     return out
 
 

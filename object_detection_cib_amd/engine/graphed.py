@@ -47,6 +47,7 @@ class GraphedTrainStep:
         self.shape = FeatureShape(width=width, height=height)
         self.params = list(net.parameters())
         self.graph = None
+        self._freeze_flags, self._keep_mask = None, None
         self.total = None
         self.parts = None
         self._host = []
@@ -143,6 +144,8 @@ class GraphedTrainStep:
                 self._step()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        # the freeze set the graph's backward program and masked SGD were captured for (the mask stays alive with it)
+        self._freeze_flags, self._keep_mask = eng.freeze_flags(), eng.keep_mask
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.total, self.parts = self._step()
@@ -159,6 +162,10 @@ class GraphedTrainStep:
         overwrites (clone to keep)."""
         if self.graph is None:
             raise RuntimeError("call capture() first")
+        if self.eng.freeze_flags() != self._freeze_flags:
+            # the graph replays the backward program of the freeze set it was captured with
+            raise RuntimeError("requires_grad changed after capture(): the captured step would train the old freeze set; "
+                               "build a new GraphedTrainStep and capture() again")
         if lr is not None:
             self.eng.set_hyper(lr, momentum, weight_decay, grad_scale)
         if self.eng.peer is not None:

@@ -52,7 +52,7 @@ def optimizer_state_dict(net, optimizer) -> Dict:
     for names, g in zip(groups, optimizer.param_groups):
         ids = []
         for n in names:
-            if eng is not None:
+            if eng is not None and (eng.stepped is None or n in eng.stepped):      # (torch: frozen = never stepped, no state)
                 off, numel = eng.layout[n]
                 state[idx] = {"momentum_buffer": eng.m_arena[off:off + numel].view(params[n].shape).detach().clone().cpu()}
             ids.append(idx)
@@ -85,6 +85,11 @@ def load_optimizer_state_dict(net, optimizer, sd: Dict):
             eng.m_arena[off:off + numel].copy_(buf.reshape(-1).to(eng.m_arena.device, torch.float32))
             loaded += 1
     optimizer.steps_taken = 1 if loaded else 0
+    keys = [n for names in groups for n in names]
+    got = {n for names, g_saved in zip(groups, sd["param_groups"]) for n, i in zip(names, g_saved["params"])
+           if (sd["state"].get(i, sd["state"].get(str(i))) or {}).get("momentum_buffer") is not None}
+    eng.stepped = None if len(got) == len(keys) else got        # the same state layout is written back
+    eng._stepped_key = None
     return loaded
 
 

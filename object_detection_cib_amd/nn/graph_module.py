@@ -156,6 +156,12 @@ class GraphModule(nn.Module):
             self._engine, self._engine_device = eng, dev
         return self._engine
 
+    def _freeze_anchor(self, eng):
+        """Freeze plan from requires_grad (engine/freeze.py); a trainable tensor for the autograd node, None when every
+        parameter is frozen (see Yolov5Network._freeze_anchor)."""
+        plan = eng.sync_freeze()
+        return eng.params[plan.trainable[0]] if plan.trainable else None
+
     def _engine_params(self):
         """engine parameter path -> tensor (the module's own parameters; a piece of a fused head adds the absent pieces)"""
         return dict(self.named_parameters())
@@ -171,8 +177,10 @@ class GraphModule(nn.Module):
         eng = self.engine()
         xs = [x.float().contiguous() for x in xs]
         nh = len(self.graph.heads)
-        if self.training and torch.is_grad_enabled():
-            anchor = next(self.parameters())
+        anchor = self._freeze_anchor(eng) if (self.training and torch.is_grad_enabled()) else None
+        if anchor is None and self.training and torch.is_grad_enabled() and any(x.requires_grad for x in xs):
+            anchor = xs[0]            # every parameter frozen: only the inputs' gradient is asked for
+        if anchor is not None:
             outs = _GraphFn.apply(self, nh, anchor, *xs)
             self._last_heads = tuple(outs[:nh])
         else:

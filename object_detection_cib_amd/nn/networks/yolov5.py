@@ -202,10 +202,18 @@ class Yolov5Network(nn.Module):
             x = x.float()
         x = x.contiguous()
         if self.training and torch.is_grad_enabled():
-            anchor = next(self.parameters())
-            return _NetFn.apply(self, x, anchor)
+            anchor = self._freeze_anchor(eng)
+            if anchor is not None:
+                return _NetFn.apply(self, x, anchor)
         with torch.no_grad():
             return tuple(eng.forward(x, training=self.training))
+
+    def _freeze_anchor(self, eng):
+        """Reads requires_grad into the engine's freeze plan (engine/freeze.py) and returns a trainable tensor for the
+        autograd node to hang on (None: everything is frozen - outputs without grad_fn, as torch gives them).  Not the
+        first parameter: that is the stem weight, the first thing a user freezes."""
+        plan = eng.sync_freeze()
+        return eng.params[plan.trainable[0]] if plan.trainable else None
 
     def train_step(self, x: torch.Tensor, loss, image_feature_shape, targets, scale: float, image_ready: bool = False):
         """forward -> assigner + loss -> backward of `scale * (localization + classification + objectness)` (the
@@ -217,6 +225,7 @@ class Yolov5Network(nn.Module):
         image_ready: the batch already sits in the engine's input buffer (Engine.image_buffer), x carries only the shape."""
         eng = self.engine()
         assert self.training, "train_step() needs train mode"
+        self._freeze_anchor(eng)
         if x.dtype != torch.float32:
             x = x.float()
         with torch.no_grad():
