@@ -176,6 +176,25 @@ int kodhip_bn_bwd_coeffs_partials(const float* partials, int T, double count, co
                                   const float* rstd, float* dgamma, float* dbeta, float* coef, int C,
                                   int raw_moment /* 1: partials[1] = sum dz*y (kodhip_conv_dgrad_bnred) */,
                                   kodStream_t stream);
+/* eval-mode BatchNorm inside a training network (the module's training flag is off): mean / rstd hold the running
+ * statistics' constants (kodhip_bn_eval_constants); dgamma / dbeta are reduced as above, coef = (gamma*rstd, 0, 0) - the
+ * plain eval-mode data gradient; no cross-rank exchange.  The two-unit form takes a mode per job (eval_k = 0: the
+ * train-mode coefficients of kodhip_bn_bwd_coeffs_partials2, count_k is then required). */
+int kodhip_bn_bwd_coeffs_eval_partials(const float* partials, int T, const float* gamma, const float* mean,
+                                       const float* rstd, float* dgamma, float* dbeta, float* coef, int C,
+                                       int raw_moment, kodStream_t stream);
+int kodhip_bn_bwd_coeffs_eval_partials2(const float* partials0, int T0, double count0, const float* gamma0,
+                                        const float* mean0, const float* rstd0, float* dgamma0, float* dbeta0,
+                                        float* coef0, int C0, int raw_moment0, int eval0,
+                                        const float* partials1, int T1, double count1, const float* gamma1,
+                                        const float* mean1, const float* rstd1, float* dgamma1, float* dbeta1,
+                                        float* coef1, int C1, int raw_moment1, int eval1, kodStream_t stream);
+/* eval-mode constants of n_units units in one launch.  desc: DEVICE table of n_units descriptors of
+ * kodhip_bn_eval_desc_bytes() bytes each: {gamma, beta, running_mean, running_var, aff, coef (or null), C, 0} as 64-bit
+ * words.  Writes aff = scale | shift | mean | rstd (C floats each) from the running statistics, and with coef the
+ * eval-mode backward coefficients (gamma*rstd, 0, 0); no running statistic is written. */
+int kodhip_bn_eval_constants(const void* desc, int n_units, float eps, kodStream_t stream);
+int kodhip_bn_eval_desc_bytes(void);
 int kodhip_bn_silu_apply(const void* y, int ldy /* row stride of y (>= C: y may be a channel slice) */, const float* scale, const float* shift,
                          const void* residual, int ldr, int rcoff,
                          void* out, int ldo, int ocoff, long M, int C, kodStream_t stream);

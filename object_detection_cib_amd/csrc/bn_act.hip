@@ -168,7 +168,10 @@ __global__ void bn_finalize_fused_kernel(const float* part, int T, double count,
 
 // raw_moment: the second partial is sum dz*y (produced by the data-gradient epilogue, conv_igemm.hip MODE_PLAIN_BN)
 // instead of sum dz*xhat; xhat = (y - mean)*rstd  =>  sum dz*xhat = rstd * (sum dz*y - mean * sum dz), in fp64.
-template <bool PEER = false>
+// EVAL: an eval-mode BatchNorm inside a training network (normalised with its running statistics, which `mean` / `rstd`
+// then hold): the parameter gradients are reduced as above, the data gradient is the plain dX = gamma*rstd*dZ - no terms
+// through the batch moments, no cross-rank exchange.
+template <bool PEER = false, bool EVAL = false>
 __device__ __forceinline__ void bn_bwd_coeffs_channel(const float* part, int T, double count, const float* gamma,
                                                       const float* mean, const float* rstd, float* dgamma, float* dbeta,
                                                       float* coef, int C, int raw_moment, int c, int lane,
@@ -182,6 +185,15 @@ __device__ __forceinline__ void bn_bwd_coeffs_channel(const float* part, int T, 
   if (lane == 0) {          // parameter gradients keep the rank's own sums (the gradient all-reduce adds the ranks later)
     dbeta[c] = (float)s0;
     dgamma[c] = (float)s1;
+  }
+  if constexpr (EVAL) {
+    static_assert(!PEER, "an eval-mode unit exchanges nothing");
+    if (lane == 0) {
+      coef[c] = (float)((double)g_ * (double)rs_);
+      coef[C + c] = 0.f;
+      coef[2 * C + c] = 0.f;
+    }
+    return;
   }
   if constexpr (PEER) peer_allreduce2(*pv, slot, c, C + c, lane, s0, s1);   // dX uses the sums over ALL ranks' pixels
   if (lane != 0) return;
@@ -218,6 +230,58 @@ __global__ void bn_bwd_coeffs_fused2_kernel(CoefJob j0, CoefJob j1) {
   if (c >= j.C) return;
   bn_bwd_coeffs_channel(j.part, j.T, j.count, j.gamma, j.mean, j.rstd, j.dgamma, j.dbeta, j.coef, j.C, j.raw_moment, c,
                         threadIdx.x & 63);
+}
+
+// eval-mode units (see bn_bwd_coeffs_channel's EVAL); the two-unit form takes a mode per job - a CSP layer's sibling
+// pair may be one eval-mode and one train-mode unit
+__global__ void bn_bwd_coeffs_eval_kernel(const float* part, int T, const float* gamma, const float* mean,
+                                          const float* rstd, float* dgamma, float* dbeta, float* coef, int C,
+                                          int raw_moment) {
+  int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (c >= C) return;
+  bn_bwd_coeffs_channel<false, true>(part, T, 1.0, gamma, mean, rstd, dgamma, dbeta, coef, C, raw_moment, c,
+                                     threadIdx.x & 63);
+}
+
+__global__ void bn_bwd_coeffs_mode2_kernel(CoefJob j0, CoefJob j1, int eval0, int eval1) {
+  const CoefJob& j = blockIdx.y == 0 ? j0 : j1;
+  int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (c >= j.C) return;
+  if (blockIdx.y == 0 ? eval0 : eval1)
+    bn_bwd_coeffs_channel<false, true>(j.part, j.T, j.count, j.gamma, j.mean, j.rstd, j.dgamma, j.dbeta, j.coef, j.C,
+                                       j.raw_moment, c, threadIdx.x & 63);
+  else
+    bn_bwd_coeffs_channel(j.part, j.T, j.count, j.gamma, j.mean, j.rstd, j.dgamma, j.dbeta, j.coef, j.C, j.raw_moment,
+                          c, threadIdx.x & 63);
+}
+
+// ---------------------------------------------------------------- eval-mode constants of many units, one launch
+// One descriptor per unit (block); one thread per channel.  Writes the four vectors the training path keeps in `aff`
+// (scale | shift | mean | rstd) from the running statistics, rstd in fp64 as bn_finalize_kernel forms it; never writes a
+// running statistic.  coef != null (gamma and beta both frozen: no coefficient kernel runs in backward): also the
+// eval-mode backward coefficients (gamma*rstd, 0, 0).
+struct BnEvalDesc {
+  const float* gamma; const float* beta; const float* running_mean; const float* running_var;
+  float* aff; float* coef; long long C; long long reserved;
+};
+
+__global__ __launch_bounds__(256) void bn_eval_constants_kernel(const BnEvalDesc* desc, float eps) {
+  const BnEvalDesc d = desc[blockIdx.x];
+  const int C = (int)d.C;
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    const float g = d.gamma[c], b = d.beta[c], rm = d.running_mean[c];
+    const float rstd = (float)(1.0 / sqrt((double)d.running_var[c] + (double)eps));
+    const float sc = g * rstd;
+    d.aff[c] = sc;
+    d.aff[C + c] = b - rm * sc;
+    d.aff[2 * C + c] = rm;
+    d.aff[3 * C + c] = rstd;
+    if (d.coef != nullptr) {
+      d.coef[c] = (float)((double)g * (double)rstd);
+      d.coef[C + c] = 0.f;
+      d.coef[2 * C + c] = 0.f;
+    }
+  }
 }
 
 // The elementwise passes are pure HBM streams: each thread keeps U rows (U x 16 B per operand) in flight before it
@@ -717,6 +781,44 @@ int kodhip_bn_bwd_coeffs_partials2(const float* partials0, int T0, double count0
   KOD_LAUNCH_CHECK("bn_bwd_coeffs_partials2");
   return KOD_OK;
 }
+
+int kodhip_bn_bwd_coeffs_eval_partials(const float* partials, int T, const float* gamma, const float* mean,
+                                       const float* rstd, float* dgamma, float* dbeta, float* coef, int C,
+                                       int raw_moment, hipStream_t stream) {
+  KOD_CHECK_ARG(partials && gamma && mean && rstd && dgamma && dbeta && coef && C > 0 && T > 0,
+                "bn_bwd_coeffs_eval_partials: bad args");
+  hipLaunchKernelGGL(bn_bwd_coeffs_eval_kernel, dim3(cdiv(C, 4)), dim3(256), 0, stream, partials, T, gamma, mean, rstd,
+                     dgamma, dbeta, coef, C, raw_moment);
+  KOD_LAUNCH_CHECK("bn_bwd_coeffs_eval_partials");
+  return KOD_OK;
+}
+
+int kodhip_bn_bwd_coeffs_eval_partials2(const float* partials0, int T0, double count0, const float* gamma0,
+                                        const float* mean0, const float* rstd0, float* dgamma0, float* dbeta0,
+                                        float* coef0, int C0, int raw_moment0, int eval0,
+                                        const float* partials1, int T1, double count1, const float* gamma1,
+                                        const float* mean1, const float* rstd1, float* dgamma1, float* dbeta1,
+                                        float* coef1, int C1, int raw_moment1, int eval1, hipStream_t stream) {
+  KOD_CHECK_ARG(partials0 && gamma0 && mean0 && rstd0 && dgamma0 && dbeta0 && coef0 && C0 > 0 && T0 > 0 &&
+                (eval0 || count0 > 0) &&
+                partials1 && gamma1 && mean1 && rstd1 && dgamma1 && dbeta1 && coef1 && C1 > 0 && T1 > 0 &&
+                (eval1 || count1 > 0), "bn_bwd_coeffs_eval_partials2: bad args");
+  CoefJob j0 = {partials0, T0, count0, gamma0, mean0, rstd0, dgamma0, dbeta0, coef0, C0, raw_moment0};
+  CoefJob j1 = {partials1, T1, count1, gamma1, mean1, rstd1, dgamma1, dbeta1, coef1, C1, raw_moment1};
+  hipLaunchKernelGGL(bn_bwd_coeffs_mode2_kernel, dim3(cdiv(C0 > C1 ? C0 : C1, 4), 2), dim3(256), 0, stream, j0, j1,
+                     eval0 ? 1 : 0, eval1 ? 1 : 0);
+  KOD_LAUNCH_CHECK("bn_bwd_coeffs_eval_partials2");
+  return KOD_OK;
+}
+
+int kodhip_bn_eval_constants(const void* desc, int n_units, float eps, hipStream_t stream) {
+  KOD_CHECK_ARG(desc && n_units > 0 && eps >= 0.f, "bn_eval_constants: bad args");
+  hipLaunchKernelGGL(bn_eval_constants_kernel, dim3(n_units), dim3(256), 0, stream, (const BnEvalDesc*)desc, eps);
+  KOD_LAUNCH_CHECK("bn_eval_constants");
+  return KOD_OK;
+}
+
+int kodhip_bn_eval_desc_bytes(void) { return (int)sizeof(BnEvalDesc); }
 
 int kodhip_bn_silu_apply(const void* y, int ldy, const float* scale, const float* shift,
                          const void* residual, int ldr, int rcoff,

@@ -270,6 +270,64 @@ class ArenaMixin:
             self._keep_masks[plan.key] = keep
         self.keep_mask = keep
 
+    # ------------------------------------------------------------------ BatchNorm modes (engine/bn_mode.py)
+    def bn_mode_flags(self):
+        """`training` of every conv unit's BatchNorm module, in program order (None: no modules registered)"""
+        mods = self.bn_modules
+        return None if mods is None else tuple(m.training for m in mods)
+
+    def sync_bn_mode(self):
+        """Read the BatchNorm modules' modes and rebuild the mode plan when they moved.  Called at every training forward;
+        the common case is one tuple of flags compared with the last one."""
+        flags = self.bn_mode_flags()
+        if self.bn_mode is not None and flags == self._bn_mode_flags:
+            return self.bn_mode
+        from .bn_mode import build_bn_mode_plan
+        names = [u.name for u in self.exec_units]
+        plan = build_bn_mode_plan(self.g, dict(zip(names, flags)) if flags is not None else {})
+        if self.bn_mode is None or self.bn_mode.key != plan.key:
+            self._on_bn_mode_change(plan)          # (raises on a rank mismatch before the plan is adopted)
+        self._bn_mode_flags, self.bn_mode = flags, plan
+        return plan
+
+    def bn_mode_active(self):
+        """The mode plan when some unit is in eval mode, else None: the default runs the program without eval units."""
+        mp = self.bn_mode
+        return None if (mp is None or mp.is_default) else mp
+
+    def _on_bn_mode_change(self, plan):
+        if self.collectives and self.world_size > 1:
+            # every rank must run the same collectives (eval units leave the SyncBN exchanges): compared across the group
+            # whenever the eval set changes, so a mismatch raises on every rank before any exchange
+            import torch.distributed as dist
+            keys = [None] * self.world_size
+            dist.all_gather_object(keys, plan.key, group=self.process_group)
+            if any(k != plan.key for k in keys):
+                raise RuntimeError("the ranks disagree on which BatchNorm modules are in eval mode: every rank must put "
+                                   "the same modules in eval mode")
+        if not plan.is_default and plan.key not in self._nbt_inc:
+            self._nbt_inc[plan.key] = torch.tensor(plan.train_mask(), dtype=torch.int64, device=self.device)
+
+    def _bn_eval_table(self, mp):
+        """(device descriptor table, unit count) of the forward's kodhip_bn_eval_constants launch for the current buffer
+        set.  One table per eval set and buffer set, kept for the engine's lifetime: a captured step bakes its address in."""
+        from .bn_mode import eval_constant_units
+        units = eval_constant_units(mp, self.freeze_active())
+        ptrs = tuple((self.ustate[n].aff.data_ptr(), self.ustate[n].coef.data_ptr() if c else 0) for n, c in units)
+        key = (mp.key, ptrs)
+        t = self._bn_eval_tables.get(key)
+        if t is None:
+            assert self.lib.kodhip_bn_eval_desc_bytes() == 8 * 8
+            pa, rm, rv = self.p_arena.data_ptr(), self.rm_arena.data_ptr(), self.rv_arena.data_ptr()
+            rows = []
+            for (n, _), (aff, coef) in zip(units, ptrs):
+                st = self.ustate[n]
+                rows.append([pa + 4 * st.g_off, pa + 4 * st.b_off, rm + 4 * st.rs_off, rv + 4 * st.rs_off, aff, coef,
+                             st.u.cout, 0])
+            t = torch.tensor(rows, dtype=torch.int64).to(self.device)
+            self._bn_eval_tables[key] = t
+        return t, len(units)
+
     def _frozen_f32plan(self, fz):
         """EngineOptions.dx_accum_fp32 under a freeze plan: the fp32-accumulation modes planned over the gradient writes
         that backward still issues (engine/plan.py; skipped writers change who is first / last of a buffer)."""

@@ -43,6 +43,8 @@ class BackwardMixin:
         fz = self.freeze_active()
         if fz is not None:
             fz.require_trainable()
+        # BatchNorm mode plan of the forward (engine/bn_mode.py), None when every unit was in train mode
+        mp = self.bn_mode_active()
         # Weight gradients run on a side stream: dW of a layer is off the critical path (bn-bwd -> dgrad -> next
         # layer), so it fills the tails of the small kernels on the main stream and, under SyncBN, the latency of
         # the per-layer statistic all-reduce.  All wgrads share one stream (and the split-K scratch) => ordered.
@@ -209,6 +211,12 @@ class BackwardMixin:
             units (a CSP layer's short + main convs) are exchanged as ONE grouped collective."""
             for u in group:
                 sync_grad(u.dst.buf.name)          # (a head's data gradient on the side stream may be its last writer)
+            if mp is not None:
+                self._bn_bwd_stats_modes(mp, fz, group, bn_bwd_stats_train, sync, gp, pa, s)
+                return
+            bn_bwd_stats_train(group)
+
+        def bn_bwd_stats_train(group):
             for u in group:
                 st, C_ = self.ustate[u.name], u.cout
                 if not st.fused_red:
@@ -379,6 +387,43 @@ class BackwardMixin:
         if self.g.inputs:
             return [self.gact[v.buf.name][..., v.coff:v.coff + v.C].permute(0, 3, 1, 2).float() if v.buf.name in touched
                     else torch.zeros((B, v.C, H // v.stride, W // v.stride), device=self.device) for v in self.g.inputs]
+
+    def _bn_bwd_stats_modes(self, mp, fz, group, bn_bwd_stats_train, sync, gp, pa, s):
+        """bn_bwd_stats under a BatchNorm mode plan (engine/bn_mode.py): eval units take the eval-mode coefficient kernel
+        and no exchange; an eval unit whose gamma and beta are both frozen launches nothing (its coefficients came with the
+        forward's eval constants); the train units of the group run the batch-statistics program."""
+        from .bn_mode import coef_launches
+        lib, chk = self.lib, _lib.check
+        launches = coef_launches(mp, fz, [u.name for u in group], sync)
+        by_name = {u.name: u for u in group}
+        for kind, names, flags in launches:
+            units = [by_name[n] for n in names]
+            if kind == "train":
+                bn_bwd_stats_train(units)
+                continue
+            for u in units:
+                st, C_ = self.ustate[u.name], u.cout
+                if not st.fused_red:
+                    aff, dA = st.aff.data_ptr(), u.dst
+                    e0 = self._t0()
+                    chk(lib.kodhip_bn_act_bwd_reduce(self._ptr(dA, True), dA.buf.C, dA.coff, st.raw.data_ptr(), st.raw_ld,
+                                                     aff, aff + 4 * C_, aff + 8 * C_, aff + 12 * C_,
+                                                     st.bpart.data_ptr(), st.M, C_, self.act_kind, self.act_slope, s), u.name)
+                    self._t1(e0, "bn_bwd_reduce", 4.0 * st.M * C_, name=u.name)
+            e0 = self._t0()
+            args = []
+            for u, ev in zip(units, flags):
+                st, C_ = self.ustate[u.name], u.cout
+                aff = st.aff.data_ptr()
+                args.append((st.bpart.data_ptr(), st.T2, float(st.M) * (self.world_size if sync else 1), pa + 4 * st.g_off,
+                             aff + 8 * C_, aff + 12 * C_, gp + 4 * st.g_off, gp + 4 * st.b_off, st.coef.data_ptr(), C_,
+                             1 if st.fused_red else 0, ev))
+            if kind == "mode2":
+                chk(lib.kodhip_bn_bwd_coeffs_eval_partials2(*args[0], *args[1], s), "+".join(names))
+            else:
+                a = args[0]
+                chk(lib.kodhip_bn_bwd_coeffs_eval_partials(a[0], a[1], *a[3:11], s), names[0])
+            self._t1(e0, "bn_bwd_coeffs", sum(8.0 * u.cout * self.ustate[u.name].T2 for u in units), name="+".join(names))
 
     def _bwd_group_frozen(self, fz, group, bn_bwd_stats, bucket_tick, B, H, W, s, gp, pa, dp, wgp, acc_flag, timed_wgrad):
         """_bwd_unit over a unit group ([unit] or [short_conv, main_conv]) under a freeze plan (engine/freeze.py): units

@@ -68,6 +68,13 @@ class Engine(ArenaMixin, BufferMixin, ForwardMixin, BackwardMixin):
         self.param_version = 0
         self.stats_version = 0         # bumped by every eager training forward (BatchNorm running statistics moved)
         self._eval_aff = None          # eval-mode BN constants of all units (flat), see _eval_affine_ptrs
+        # BatchNorm modules of the conv units in program order (set by the owning nn.Module): their `training` flags make
+        # the BatchNorm mode plan of a training forward (engine/bn_mode.py); None = every unit in train mode
+        self.bn_modules = None
+        self.bn_mode = None            # BnModePlan of the last training forward (None: never read)
+        self._bn_mode_flags = None
+        self._bn_eval_tables = {}      # (eval set, buffer addresses) -> device descriptor table of kodhip_bn_eval_constants
+        self._nbt_inc = {}             # eval set -> per-unit num_batches_tracked increment (1 = train mode)
         self._fork_ev = None
         self.br_stream = None         # side stream of the CSP short_conv branch in forward()
         self.head_stream = None       # side stream of the P3 / P4 head convolutions in forward()

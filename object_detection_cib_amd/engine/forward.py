@@ -132,6 +132,11 @@ class ForwardMixin:
         if sync:
             self._check_equal_local_batch((B, H, W))
         rm, rv = self.rm_arena.data_ptr(), self.rv_arena.data_ptr()
+        # BatchNorm mode plan (engine/bn_mode.py), None when every unit is in train mode: then this is the program
+        # without eval units.  With one: the eval units' constants come from one launch before the first conv, and they
+        # have no statistics stage (no running-statistic update, no SyncBN exchange)
+        mp = self.sync_bn_mode() if training else None
+        mp = None if (mp is None or mp.is_default) else mp
 
         def conv_stage(u: ConvUnit, s=s):
             st, C_ = self.ustate[u.name], u.cout
@@ -149,6 +154,10 @@ class ForwardMixin:
         def stats_stage(group, s=s):
             """Batch statistics -> BatchNorm constants.  Under SyncBN the [sum, sum of squares] vectors of the group's
             units (a CSP layer's main + short convs) are exchanged as ONE grouped collective."""
+            if mp is not None:
+                group = mp.stat_group(group)
+                if not group:
+                    return
             e0 = self._t0()
             if not sync:
                 for u in group:
@@ -209,6 +218,12 @@ class ForwardMixin:
         heads_on_aux = False
         joined_buf = None                # concat buffer whose short_conv half is being written on the side stream
         ops = self.g.ops
+        if mp is not None:
+            table, n_ev = self._bn_eval_table(mp)
+            e0 = self._t0()
+            chk(lib.kodhip_bn_eval_constants(table.data_ptr(), n_ev, self.bn_eps, s), "bn_eval_constants")
+            self._t1(e0, "bn_eval_constants", 8.0 * sum(u.cout for u in self.exec_units if mp.is_eval(u.name)),
+                     name="eval_units")
         i = 0
         while i < len(ops):
             op = ops[i]
@@ -291,9 +306,13 @@ class ForwardMixin:
         if heads_on_aux:
             main_stream.wait_stream(self.head_stream)
         self._stamp("fwd_end")
-        if training:
+        if training and mp is None:
             self.nbt_arena += 1
             self.stats_version += 1              # running statistics moved
+        elif training:
+            self.nbt_arena += self._nbt_inc[mp.key]         # train-mode units only
+            if mp.any_train:
+                self.stats_version += 1
         self.training_ready = training          # an eval forward overwrites the saved pre-BN tensors
         for v in self.g.outputs:                # sub-network graphs: their output views, NCHW fp32
             outs.append(self.act[v.buf.name][..., v.coff:v.coff + v.C].permute(0, 3, 1, 2).float())

@@ -13,7 +13,8 @@ static op list of engine/graph.py:
 
 The engine reads the flags from the parameters at every training forward and rebuilds the plan only when the key moves;
 with ``is_default`` (everything trainable) it runs the unfrozen program launch for launch.  BatchNorm modules in eval mode
-inside a training network are not part of the plan: the training step normalises every unit with batch statistics.
+inside a training network are not part of this plan: engine/bn_mode.py plans them, and the backward combines the two
+only where an eval unit's gamma and beta are both frozen (no coefficient kernel then).
 """
 from __future__ import annotations
 

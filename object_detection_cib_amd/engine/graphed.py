@@ -48,6 +48,7 @@ class GraphedTrainStep:
         self.params = list(net.parameters())
         self.graph = None
         self._freeze_flags, self._keep_mask = None, None
+        self._bn_flags = None
         self.total = None
         self.parts = None
         self._host = []
@@ -146,6 +147,8 @@ class GraphedTrainStep:
         torch.cuda.synchronize()
         # the freeze set the graph's backward program and masked SGD were captured for (the mask stays alive with it)
         self._freeze_flags, self._keep_mask = eng.freeze_flags(), eng.keep_mask
+        # and the BatchNorm modes it was captured with (eval units: constants from running statistics, no statistics stage)
+        self._bn_flags = eng.bn_mode_flags()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.total, self.parts = self._step()
@@ -166,6 +169,10 @@ class GraphedTrainStep:
             # the graph replays the backward program of the freeze set it was captured with
             raise RuntimeError("requires_grad changed after capture(): the captured step would train the old freeze set; "
                                "build a new GraphedTrainStep and capture() again")
+        if self.eng.bn_mode_flags() != self._bn_flags:
+            # the graph replays the forward / backward program of the BatchNorm modes it was captured with
+            raise RuntimeError("a BatchNorm module changed mode (train / eval) after capture(): the captured step would "
+                               "normalise with the old modes; build a new GraphedTrainStep and capture() again")
         if lr is not None:
             self.eng.set_hyper(lr, momentum, weight_decay, grad_scale)
         if self.eng.peer is not None:

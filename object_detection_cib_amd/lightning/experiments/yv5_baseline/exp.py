@@ -114,12 +114,15 @@ class DefaultYolov5Experiment:
                 self._geval[key] = GraphedEvalForward(self.net, self.anchor_info, key[0], key[2], key[3])
             det = self._geval[key](images if images.dtype == torch.float32 else images.float())
             return targets, non_max_suppression(det, self.val_nms_conf_threshold, self.val_nms_iou_threshold)
-        was = self.net.training
+        # every submodule's own mode is restored afterwards (as Lightning's validation loop does): net.train(was) would
+        # put a backbone the user keeps in eval mode (frozen BatchNorm) back into train mode
+        modes = [(m, m.training) for m in self.net.modules()]
         self.net.eval()
         res = self.net(images)
         det = get_detections(FeatureShape(width=images.shape[3], height=images.shape[2]), res, self.anchor_info)
         out = non_max_suppression(det, self.val_nms_conf_threshold, self.val_nms_iou_threshold)
-        self.net.train(was)
+        for m, was in modes:
+            m.training = was
         return targets, out
 
     # exp.py:164-185 + Lightning automatic optimisation

@@ -153,6 +153,9 @@ class GraphModule(nn.Module):
             eng.bn_eps, eng.bn_momentum = getattr(self, "_bn_eps", BN_EPS), getattr(self, "_bn_momentum", BN_MOMENTUM)
             eng.set_activation(*getattr(self, "_act", (ACT_SILU, 0.0)))
             eng._build_arenas(dev)
+            # the units' BatchNorm modules: their `training` flags decide, at every training forward, which units
+            # normalise with running statistics (engine/bn_mode.py)
+            eng.bn_modules = [self.get_submodule(u.name + ".1") for u in eng.exec_units]
             self._engine, self._engine_device = eng, dev
         return self._engine
 

@@ -109,6 +109,9 @@ class Yolov5Network(nn.Module):
             eng.bn_eps, eng.bn_momentum = self._bn_eps, self._bn_momentum
             eng.set_activation(*self._act)
             eng._build_arenas(dev)
+            # the units' BatchNorm modules: their `training` flags decide, at every training forward, which units
+            # normalise with running statistics (engine/bn_mode.py)
+            eng.bn_modules = [self.get_submodule(u.name + ".1") for u in eng.exec_units]
             self._engine, self._engine_device = eng, dev
         return self._engine
 
