@@ -66,7 +66,9 @@ def conv_fwd_raw(xb, ldx_view, pk, stride, padding, out=None, ycoff=0):
     if out is None:
         out = torch.zeros((B, Ho, Wo, N), dtype=torch.bfloat16, device="cuda")
     T = lib.kodhip_conv_stats_slots(B * Ho * Wo, N)
-    stats = torch.zeros(2 * N * T, dtype=torch.float32, device="cuda")
+    # NaN, not zeros: the kernel must write every slot (the ones its launch uses and zeros in the rest), as the engine
+    # reuses its slabs from step to step without clearing them
+    stats = torch.full((2 * N * T,), float("nan"), dtype=torch.float32, device="cuda")
     _lib.check(lib.kodhip_conv_fwd_raw(xb.data_ptr(), pk["f"].data_ptr(), out.data_ptr(), stats.data_ptr(),
                                        B, H, W, ld, coff, Cin, N, KH, KW, stride, stride, padding, padding,
                                        pk["Kp"], out.shape[-1], ycoff, stream()), "conv_fwd_raw")
