@@ -254,6 +254,32 @@ int kodhip_sgd_nesterov(float* params, const float* grads, float* momentum_buf, 
    engine/freeze.py) are not touched: no weight decay, no momentum, no update */
 int kodhip_sgd_nesterov_masked(float* params, const float* grads, float* momentum_buf, const void* group_ids,
                                const void* keep_mask, long n, const float* hyper, kodStream_t stream);
+/* ---- gradient norm and clipping over the gradient arena (torch.nn.utils.clip_grad_norm_ / clip_grad_value_, Lightning's
+ * Trainer(gradient_clip_val, gradient_clip_algorithm)) ----
+ * clip block: device memory, kodhip_clip_block_bytes() = 16 fp32:
+ *   [0] total 2-norm of grad_scale * g over the counted elements   [1] bias group  [2] decay group  [3] norm group
+ *   [4] clip coefficient min(1, max_norm / (total + 1e-6)), formed in fp32 as torch forms it
+ *   [5] 1.0 when the total norm is NaN or Inf, else 0.0            [6] steps skipped so far (skip_nonfinite)   [7] spare
+ *   [8] INPUT: max_norm (mode 0, norm) or the clamp value (mode 1, value); written by the caller, may change between
+ *       replays of a captured step like `hyper`                    [9..15] spare
+ * [0..6] are written by kodhip_grad_norm only.  Sums of squares are formed in fp64 and reduced in a fixed order (one partial
+ * per block and group, no atomics): the same bits on every run and replay, whatever the device. */
+int kodhip_clip_block_bytes(void);
+int kodhip_grad_norm_workspace_bytes(void);
+/* count_mask (device, n bytes, may be NULL = every element of groups 0..2 counts): 0 leaves the element out (arena
+   padding, frozen tensors).  workspace: kodhip_grad_norm_workspace_bytes(), 8-byte aligned.  skip_nonfinite: a NaN / Inf
+   total bumps clip[6].  nontemporal: gradient loads that do not allocate in the caches.  Two launches. */
+int kodhip_grad_norm(const float* grads, const void* group_ids, const void* count_mask, long n, const float* hyper,
+                     float* clip, void* workspace, int skip_nonfinite, int nontemporal, kodStream_t stream);
+/* kodhip_sgd_nesterov (keep_mask NULL) / kodhip_sgd_nesterov_masked with the gradient clipped after the scale:
+   mode 0: (g * grad_scale) * clip[4]; mode 1: clamp(g * grad_scale, -clip[8], +clip[8]) (a NaN stays a NaN).  clip[4] == 1
+   gives the bits of the unclipped entries.  skip_nonfinite and clip[5] != 0: nothing is written. */
+int kodhip_sgd_nesterov_clipped(float* params, const float* grads, float* momentum_buf, const void* group_ids,
+                                const void* keep_mask, long n, const float* hyper, const float* clip, int mode,
+                                int skip_nonfinite, kodStream_t stream);
+/* the gradients themselves, in place, over the counted elements: mode 0 g *= clip[4], mode 1 g = clamp(g, -clip[8], +clip[8]) */
+int kodhip_grad_clip_inplace(float* grads, const void* group_ids, const void* count_mask, long n, const float* clip,
+                             int mode, kodStream_t stream);
 int kodhip_fill_u32(void* p, uint32_t value, long n, kodStream_t stream);
 /* dst (device) <- src (PINNED host memory), bytes % 16 == 0, both 16-byte aligned: a kernel pulling the bytes through the
  * host memory's device mapping - the small per-step tables of the data path (kod/data/detection.py's per-sample results)

@@ -655,6 +655,148 @@ __global__ void sgd_nesterov_masked_kernel(float* p, const float* g, float* buf,
   *reinterpret_cast<f32x4*>(buf + i) = bv;
 }
 
+// ------------------------------------------------------------------ gradient norm / clipping (include/kodhip.h: clip block)
+// Clip block (device, KOD_CLIP_FLOATS fp32): outputs [0] total norm | [1..3] norms of the groups bias, decay, norm | [4] clip
+// coefficient | [5] 1 when the total norm is NaN / Inf | [6] steps skipped so far | [7] spare; input [8] max_norm (norm
+// mode) or the clamp value (value mode), [9..15] spare.  The outputs are written by grad_norm_finalize_kernel only, the
+// input by the host between steps (like `hyper`), so neither tramples the other.
+#define KOD_CLIP_FLOATS 16
+#define KOD_NORM_BLOCKS 1024          // partial slots: 4 blocks of 256 lanes per CU on 256 CUs; fixed, so the bits do not
+                                      // depend on the device the step runs on
+enum { KOD_CLIP_NORM = 0, KOD_CLIP_VALUE = 1 };
+
+// Sum of squares of the fp32 product gscale * g (what the SGD kernels form first) per optimizer group: squares and sums
+// in fp64 per lane, fp64 wave / block reduction, ONE partial per block and group in a fixed slot - no atomics, the same
+// bits on every run.  count[i] == 0 (may be NULL: everything counts) leaves element i out: arena padding, frozen tensors.
+// NT: non-temporal loads of the gradients (the SGD kernel re-reads them right after; which form is faster is a
+// measurement, LOG.md).
+template <bool NT>
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const float* __restrict__ g, const unsigned char* __restrict__ gid,
+                                                                const unsigned char* __restrict__ count, long n,
+                                                                const float* __restrict__ hyper, double* __restrict__ part) {
+  const float gscale = hyper[9];
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  const long stride = (long)gridDim.x * 256 * 4;
+  // four independent 16-byte loads in flight per lane: unconditional, from a clamped address (a lane past the end re-reads
+  // element 0 and counts nothing), so that no branch sits between them
+  for (long i0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i0 < n; i0 += 4 * stride) {
+    f32x4 gv[4];
+    unsigned int kv[4];
+    unsigned char grp[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long i = i0 + u * stride;
+      const bool in = i < n;
+      const long ic = in ? i : 0;
+      grp[u] = gid[ic >> 6];
+      kv[u] = count ? *reinterpret_cast<const unsigned int*>(count + ic) : 0x01010101u;
+      gv[u] = NT ? kod_load_once<f32x4>(g + ic) : *reinterpret_cast<const f32x4*>(g + ic);
+      if (!in || grp[u] > 2) kv[u] = 0;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      double t = 0.0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const double d = (double)(gv[u][e] * gscale);
+        t += ((kv[u] >> (8 * e)) & 0xffu) ? d * d : 0.0;      // (a select, not a product: a masked NaN / 1e30 must not count)
+      }
+      s0 += grp[u] == 0 ? t : 0.0;
+      s1 += grp[u] == 1 ? t : 0.0;
+      s2 += grp[u] == 2 ? t : 0.0;
+    }
+  }
+  __shared__ double sm[3][4];
+  s0 = wave_sum_d(s0); s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { sm[0][wave] = s0; sm[1][wave] = s1; sm[2][wave] = s2; }
+  __syncthreads();
+  if (threadIdx.x < 3)
+    part[(size_t)blockIdx.x * 3 + threadIdx.x] = (sm[threadIdx.x][0] + sm[threadIdx.x][1]) + (sm[threadIdx.x][2] + sm[threadIdx.x][3]);
+}
+
+// One wave: lane l adds slots l, l + 64, ... in that order, then the fixed butterfly of wave_sum_d.  Coefficient as
+// torch.nn.utils.clip_grad_norm_ forms it in fp32: max_norm / (total + 1e-6) is Tensor.__rtruediv__, i.e.
+// reciprocal(total + 1e-6) * max_norm, then clamp(max = 1) (a NaN stays a NaN).
+__global__ __launch_bounds__(64) void grad_norm_finalize_kernel(const double* __restrict__ part, int nblk, float* clip, int skip_nonfinite) {
+  const int lane = threadIdx.x;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  for (int b = lane; b < nblk; b += 64) { s0 += part[b * 3]; s1 += part[b * 3 + 1]; s2 += part[b * 3 + 2]; }
+  s0 = wave_sum_d(s0); s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
+  if (lane != 0) return;
+  const float total = (float)sqrt((s0 + s1) + s2);
+  clip[0] = total;
+  clip[1] = (float)sqrt(s0); clip[2] = (float)sqrt(s1); clip[3] = (float)sqrt(s2);
+  const float c = (1.0f / (total + 1e-6f)) * clip[8];
+  clip[4] = c > 1.0f ? 1.0f : c;
+  const bool bad = !(fabsf(total) <= 3.402823466e38f);        // NaN or Inf
+  clip[5] = bad ? 1.0f : 0.0f;
+  if (bad && skip_nonfinite) clip[6] = clip[6] + 1.0f;
+}
+
+// The SGD kernels above with the gradient clipped between the scale and the update (torch's order: DDP's average, then
+// clip_grad_*_): MODE norm: gg = (g * gscale) * coef; MODE value: gg = clamp(g * gscale, -v, +v) with clamp_'s NaN (it stays).
+// With coef == 1 the bits are those of sgd_nesterov(_masked)_kernel.  skip_nonfinite and a NaN / Inf norm: nothing is
+// touched (every lane reads the same flag: a uniform branch).
+template <bool MASKED, int MODE>
+__global__ void sgd_nesterov_clipped_kernel(float* p, const float* g, float* buf, const unsigned char* gid,
+                                            const unsigned char* keep, long n, const float* hyper, const float* clip,
+                                            int skip_nonfinite) {
+  long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i >= n) return;
+  if (skip_nonfinite && clip[5] != 0.f) return;
+  unsigned char grp = gid[i >> 6];
+  if (grp > 2) return;
+  unsigned char kk[4] = {1, 1, 1, 1};
+  if (MASKED) {
+    const uchar4 kv = *reinterpret_cast<const uchar4*>(keep + i);
+    kk[0] = kv.x; kk[1] = kv.y; kk[2] = kv.z; kk[3] = kv.w;
+    if ((kk[0] | kk[1] | kk[2] | kk[3]) == 0) return;
+  }
+  const float lr = hyper[grp], mu = hyper[3 + grp], wd = hyper[6 + grp], gscale = hyper[9];
+  const int flags = (int)hyper[10];
+  const bool nesterov = (flags & 1) != 0, maximize = (flags & 2) != 0, first = (flags & 4) != 0;
+  const float undamped = 1.0f - hyper[11];
+  const float coef = clip[4], cv = clip[8];
+  f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);
+  f32x4 gv = kod_load_once<f32x4>(g + i);
+  f32x4 bv = *reinterpret_cast<const f32x4*>(buf + i);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (MASKED && !kk[e]) continue;
+    float gg = gv[e] * gscale;
+    if (MODE == KOD_CLIP_NORM) gg = gg * coef;
+    else gg = gg < -cv ? -cv : (gg > cv ? cv : gg);
+    if (maximize) gg = -gg;
+    if (wd != 0.f) gg = gg + wd * pv[e];
+    float b = (first || mu == 0.f) ? gg : mu * bv[e] + undamped * gg;
+    bv[e] = b;
+    pv[e] = pv[e] - lr * (nesterov ? gg + mu * b : b);
+  }
+  *reinterpret_cast<f32x4*>(p + i) = pv;
+  *reinterpret_cast<f32x4*>(buf + i) = bv;
+}
+
+// eager clip_grad_norm_ / clip_grad_value_: the gradients themselves, in place (p.grad shows clipped values, as with torch):
+// MODE norm g *= coef, MODE value g = clamp(g, -v, +v), over the counted elements
+template <int MODE>
+__global__ void grad_clip_inplace_kernel(float* g, const unsigned char* gid, const unsigned char* count, long n, const float* clip) {
+  long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i >= n) return;
+  if (gid[i >> 6] > 2) return;
+  const unsigned int kv = count ? *reinterpret_cast<const unsigned int*>(count + i) : 0x01010101u;
+  if (kv == 0) return;
+  const float coef = clip[4], cv = clip[8];
+  f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (!((kv >> (8 * e)) & 0xffu)) continue;
+    const float x = gv[e];
+    gv[e] = MODE == KOD_CLIP_NORM ? x * coef : (x < -cv ? -cv : (x > cv ? cv : x));
+  }
+  *reinterpret_cast<f32x4*>(g + i) = gv;
+}
+
 __global__ void fill_u32_kernel(uint32_t* p, uint32_t v, long n) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
@@ -804,6 +946,62 @@ int kodhip_sgd_nesterov_masked(float* params, const float* grads, float* momentu
   hipLaunchKernelGGL(sgd_nesterov_masked_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, stream, params, grads, momentum_buf,
                      (const unsigned char*)group_ids, (const unsigned char*)keep_mask, n, hyper);
   KOD_LAUNCH_CHECK("sgd_nesterov_masked");
+  return KOD_OK;
+}
+
+int kodhip_clip_block_bytes(void) { return KOD_CLIP_FLOATS * (int)sizeof(float); }
+int kodhip_grad_norm_workspace_bytes(void) { return KOD_NORM_BLOCKS * 3 * (int)sizeof(double); }
+
+// clip: the clip block (layout above / kodhip.h); workspace: kodhip_grad_norm_workspace_bytes(), 8-byte aligned;
+// count_mask (may be NULL): u8 per element, 0 = not counted.  Two launches: partials, finalize.
+int kodhip_grad_norm(const float* grads, const void* group_ids, const void* count_mask, long n, const float* hyper,
+                     float* clip, void* workspace, int skip_nonfinite, int nontemporal, hipStream_t stream) {
+  KOD_CHECK_ARG(grads && group_ids && hyper && clip && workspace && n > 0 && n % 64 == 0 && ((uintptr_t)workspace % 8) == 0,
+                "grad_norm: bad args");
+  int grid = cdiv(n / 4, 256);
+  if (grid > KOD_NORM_BLOCKS) grid = KOD_NORM_BLOCKS;
+  if (nontemporal)
+    hipLaunchKernelGGL(grad_norm_partial_kernel<true>, dim3(grid), dim3(256), 0, stream, grads, (const unsigned char*)group_ids,
+                       (const unsigned char*)count_mask, n, hyper, (double*)workspace);
+  else
+    hipLaunchKernelGGL(grad_norm_partial_kernel<false>, dim3(grid), dim3(256), 0, stream, grads, (const unsigned char*)group_ids,
+                       (const unsigned char*)count_mask, n, hyper, (double*)workspace);
+  KOD_LAUNCH_CHECK("grad_norm");
+  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(64), 0, stream, (const double*)workspace, grid, clip, skip_nonfinite);
+  KOD_LAUNCH_CHECK("grad_norm_finalize");
+  return KOD_OK;
+}
+
+// keep_mask may be NULL (everything trainable); mode: 0 norm (reads clip[4]), 1 value (reads clip[8])
+int kodhip_sgd_nesterov_clipped(float* params, const float* grads, float* momentum_buf, const void* group_ids,
+                                const void* keep_mask, long n, const float* hyper, const float* clip, int mode,
+                                int skip_nonfinite, hipStream_t stream) {
+  KOD_CHECK_ARG(params && grads && momentum_buf && group_ids && hyper && clip && n > 0 && n % 64 == 0,
+                "sgd_nesterov_clipped: bad args");
+  KOD_CHECK_ARG(mode == KOD_CLIP_NORM || mode == KOD_CLIP_VALUE, "sgd_nesterov_clipped: unknown mode %d", mode);
+  const dim3 grid(cdiv(n / 4, 256)), blk(256);
+  const unsigned char* gid = (const unsigned char*)group_ids;
+  const unsigned char* keep = (const unsigned char*)keep_mask;
+#define KOD_SGD_CLIPPED(M, MODE) \
+  hipLaunchKernelGGL((sgd_nesterov_clipped_kernel<M, MODE>), grid, blk, 0, stream, params, grads, momentum_buf, gid, keep, n, hyper, clip, skip_nonfinite)
+  if (keep) { if (mode == KOD_CLIP_NORM) KOD_SGD_CLIPPED(true, KOD_CLIP_NORM); else KOD_SGD_CLIPPED(true, KOD_CLIP_VALUE); }
+  else { if (mode == KOD_CLIP_NORM) KOD_SGD_CLIPPED(false, KOD_CLIP_NORM); else KOD_SGD_CLIPPED(false, KOD_CLIP_VALUE); }
+#undef KOD_SGD_CLIPPED
+  KOD_LAUNCH_CHECK("sgd_nesterov_clipped");
+  return KOD_OK;
+}
+
+int kodhip_grad_clip_inplace(float* grads, const void* group_ids, const void* count_mask, long n, const float* clip,
+                             int mode, hipStream_t stream) {
+  KOD_CHECK_ARG(grads && group_ids && clip && n > 0 && n % 64 == 0, "grad_clip_inplace: bad args");
+  KOD_CHECK_ARG(mode == KOD_CLIP_NORM || mode == KOD_CLIP_VALUE, "grad_clip_inplace: unknown mode %d", mode);
+  if (mode == KOD_CLIP_NORM)
+    hipLaunchKernelGGL(grad_clip_inplace_kernel<KOD_CLIP_NORM>, dim3(cdiv(n / 4, 256)), dim3(256), 0, stream, grads,
+                       (const unsigned char*)group_ids, (const unsigned char*)count_mask, n, clip);
+  else
+    hipLaunchKernelGGL(grad_clip_inplace_kernel<KOD_CLIP_VALUE>, dim3(cdiv(n / 4, 256)), dim3(256), 0, stream, grads,
+                       (const unsigned char*)group_ids, (const unsigned char*)count_mask, n, clip);
+  KOD_LAUNCH_CHECK("grad_clip_inplace");
   return KOD_OK;
 }
 

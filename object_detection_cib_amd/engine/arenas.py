@@ -180,6 +180,22 @@ class ArenaMixin:
         self._hyper_events = [None] * len(self._hyper_host)
         self._hyper_slot = 0
         self._hyper_vals = None
+        # gradient norm / clipping (csrc/misc_ops.hip, clip block layout in include/kodhip.h): off by default - the step then
+        # issues exactly the launches it always did
+        self.clip = torch.zeros(self.lib.kodhip_clip_block_bytes() // 4, dtype=torch.float32, device=device)
+        self.norm_ws = torch.zeros(self.lib.kodhip_grad_norm_workspace_bytes() // 8, dtype=torch.float64, device=device)
+        self.clip_algorithm: Optional[str] = None      # None | "norm" | "value"
+        self.clip_skip_nonfinite = False
+        self.track_grad_norm = False
+        self.norm_nontemporal = False                  # plain loads: the SGD kernel re-reads the arena right after (LOG.md)
+        self._count_masks = {}                         # freeze key (None: default plan) -> u8 per element: counts in the norm
+        self._unit_hyper = torch.zeros(12, dtype=torch.float32, device=device)
+        self._unit_hyper[9] = 1.0                      # grad_scale 1: the norm of .grad as published (clip_grad_norm_)
+        self._clip_host = [torch.zeros(4, dtype=torch.float32).pin_memory() for _ in range(16)]
+        self._clip_events = [None] * len(self._clip_host)
+        self._clip_slot = 0
+        self.clip[8] = float("inf")                    # input slot: max_norm / clamp value (set_clip); inf clips nothing
+        self._clip_val = float("inf")
 
     def _grad_view(self, name, arena=None):
         o, k = self.layout[name]
@@ -386,8 +402,91 @@ class ArenaMixin:
         self.set_hyper(lr, momentum, weight_decay, grad_scale)
         self.sgd_step_device()
 
+    # ------------------------------------------------------------------ gradient norm / clipping
+    CLIP_MODES = {"norm": 0, "value": 1}
+
+    def configure_clip(self, algorithm: Optional[str] = None, skip_nonfinite: bool = False, track_grad_norm: bool = False):
+        """Which launches sgd_step_device() issues: algorithm None = no clipping.  The clip VALUE lives in device memory
+        (set_clip); this choice is baked into a captured step."""
+        if algorithm is not None and algorithm not in self.CLIP_MODES:
+            raise ValueError(f"gradient_clip_algorithm {algorithm!r}: expected 'norm' or 'value'")
+        self.clip_algorithm, self.clip_skip_nonfinite = algorithm, bool(skip_nonfinite)
+        self.track_grad_norm = bool(track_grad_norm)
+
+    def set_clip(self, value: Optional[float]):
+        """Upload max_norm (algorithm "norm") or the clamp value ("value") into the clip block's input slot - outside any
+        captured graph, like set_hyper.  None = +inf: nothing is clipped (skip_nonfinite without a clip value)."""
+        v = float("inf") if value is None else float(value)
+        if v != self._clip_val:
+            k = self._clip_slot
+            self._clip_slot = (k + 1) % len(self._clip_host)
+            if self._clip_events[k] is not None:
+                self._clip_events[k].synchronize()
+            host = self._clip_host[k]
+            host[0] = v
+            self.clip[8:12].copy_(host, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._clip_events[k] = ev
+            self._clip_val = v
+
+    def _count_mask(self):
+        """u8 per arena element: 1 where the element belongs to a trainable tensor.  The 64-element padding behind a
+        parameter set carries the set's group id and the head tensors share granules, so the norm masks per element
+        instead of trusting every writer of both gradient arenas to leave the padding zero.  One mask per freeze set, kept
+        for the engine's lifetime (a captured step bakes its address in)."""
+        fz = self.freeze_active()
+        key = None if fz is None else fz.key
+        m = self._count_masks.get(key)
+        if m is None:
+            host = np.zeros(self.n_arena, dtype=np.uint8)
+            for n in (self.layout if fz is None else fz.trainable):
+                o, k = self.layout[n]
+                host[o:o + k] = 1
+            m = torch.from_numpy(host).to(self.device)
+            self._count_masks[key] = m
+        return m
+
+    def grad_norm_device(self, hyper=None):
+        """Launch the norm reduction over the current gradient arena (two launches); the results land in self.clip."""
+        h = self.hyper if hyper is None else hyper
+        _lib.check(self.lib.kodhip_grad_norm(self.current_grad_arena().data_ptr(), self.gid.data_ptr(),
+                                             self._count_mask().data_ptr(), self.n_arena, h.data_ptr(), self.clip.data_ptr(),
+                                             self.norm_ws.data_ptr(), int(self.clip_skip_nonfinite and hyper is None),
+                                             int(self.norm_nontemporal), self._stream()), "grad_norm")
+
+    def clip_grads_inplace(self, algorithm: str, value: float):
+        """torch.nn.utils.clip_grad_norm_ / clip_grad_value_ over the published .grad views (eager path): the norm of the
+        gradients as they stand (no grad_scale), then g *= coef (or the clamp) in place.  Returns the total norm as a device
+        scalar for "norm", None for "value"."""
+        mode = self.CLIP_MODES[algorithm]
+        self.wait_grads()
+        self.set_clip(value)
+        if mode == 0:
+            self.grad_norm_device(self._unit_hyper)
+        _lib.check(self.lib.kodhip_grad_clip_inplace(self.current_grad_arena().data_ptr(), self.gid.data_ptr(),
+                                                     self._count_mask().data_ptr(), self.n_arena, self.clip.data_ptr(),
+                                                     mode, self._stream()), "grad_clip_inplace")
+        return self.clip[0].clone() if mode == 0 else None
+
     def sgd_step_device(self):
-        """SGD with whatever is in self.hyper (device, 12 floats) - the graph-capturable form."""
+        """SGD with whatever is in self.hyper (device, 12 floats) - the graph-capturable form.  With clipping configured
+        (configure_clip): norm reduction (after wait_grads(), so every rank reduces the same all-reduced gradients and forms
+        the same coefficient without a collective of its own), then the SGD form that consumes it."""
+        algo, skip = self.clip_algorithm, self.clip_skip_nonfinite
+        if algo is not None or skip or self.track_grad_norm:
+            if algo != "value" or skip or self.track_grad_norm:
+                self.grad_norm_device()
+            if algo is not None or skip:
+                fz = self.freeze_active()
+                _lib.check(self.lib.kodhip_sgd_nesterov_clipped(
+                    self.p_arena.data_ptr(), self.current_grad_arena().data_ptr(), self.m_arena.data_ptr(),
+                    self.gid.data_ptr(), None if fz is None else self.keep_mask.data_ptr(), self.n_arena,
+                    self.hyper.data_ptr(), self.clip.data_ptr(), self.CLIP_MODES[algo or "norm"], int(skip),
+                    self._stream()), "sgd_clipped")
+                self.param_version += 1
+                self.note_sgd_step()
+                return
         if self.freeze_active() is None:
             _lib.check(self.lib.kodhip_sgd_nesterov(self.p_arena.data_ptr(), self.current_grad_arena().data_ptr(),
                                                     self.m_arena.data_ptr(), self.gid.data_ptr(), self.n_arena,

@@ -9,6 +9,7 @@ run at device speed (bench.py measures exactly this replay).  What makes the ste
   image indices of all targets padded to a fixed capacity with zero-size boxes, which the assigner never matches
   (kod/core/label_assignment/yv5.py:262-296: the anchor-ratio test rejects w = h = 0);
 * optimizer hyper-parameters are read from device memory (Engine.set_hyper), so warm-up / LR schedules keep working;
+  so is the gradient-clipping value (Engine.set_clip): the norm reduction and the clipped SGD run inside the graph;
 * no host synchronisation anywhere in the step (assigner counts stay on the device).
 """
 from __future__ import annotations
@@ -22,11 +23,28 @@ from ..core.label_assignment.yv5 import BatchedTargets
 from ..core.types import FeatureShape
 
 
+_KEEP = object()          # __call__(gradient_clip_val=...) left out: keep the current value
+
+
 class GraphedTrainStep:
     def __init__(self, net, loss, batch_size: int, height: int, width: int, max_targets: int = 4096,
-                 loss_scale: Optional[float] = None, input_pairs: bool = False):
+                 loss_scale: Optional[float] = None, input_pairs: bool = False,
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
+                 skip_nonfinite: bool = False, track_grad_norm: bool = False):
         """input_pairs: batches arrive as bf16 pixel pairs [B, H, W/2, 8] (DeviceTrainPipeline.make_batch(out_pairs=True)) and
-        are copied straight into the network's input buffer - no fp32 NCHW batch, no layout-change pass in the step."""
+        are copied straight into the network's input buffer - no fp32 NCHW batch, no layout-change pass in the step.
+        gradient_clip_val / gradient_clip_algorithm ("norm" | "value"): Lightning's Trainer arguments; the clipping runs
+        between the gradient all-reduce and the update inside the captured step (the value may change per call, the
+        algorithm and on / off may not).  skip_nonfinite: a step whose gradient norm is NaN / Inf leaves parameters and
+        momentum untouched and is counted in `skipped_steps`.  track_grad_norm: run the norm reduction without clipping.
+        `grad_norm` (total, bias, decay, norm-group norms before clipping) and `skipped_steps` are static device tensors:
+        reading them is the caller's synchronisation, the step has none."""
+        if gradient_clip_algorithm not in ("norm", "value"):
+            raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected 'norm' or 'value'")
+        self.gradient_clip_val = None if gradient_clip_val is None else float(gradient_clip_val)
+        self.gradient_clip_algorithm = gradient_clip_algorithm
+        self.skip_nonfinite, self.track_grad_norm = bool(skip_nonfinite), bool(track_grad_norm)
+        self._clip_cfg = None             # what capture() baked in
         self.net, self.loss = net, loss
         self.input_pairs = bool(input_pairs)
         self.eng = net.engine()
@@ -65,12 +83,27 @@ class GraphedTrainStep:
         assert self.input_pairs
         return self.eng.image_buffer(self.B, self.H, self.W)
 
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """[total, bias, decay, norm] gradient norms of the last step, before clipping (device, static)"""
+        return self.eng.clip[0:4]
+
+    @property
+    def skipped_steps(self) -> torch.Tensor:
+        """steps skipped for a NaN / Inf gradient norm so far (device scalar, static)"""
+        return self.eng.clip[6]
+
+    def _clip_config(self):
+        return (self.gradient_clip_algorithm if self.gradient_clip_val is not None else None, self.skip_nonfinite,
+                self.track_grad_norm)
+
     # -- the step itself (what gets captured)
     def _step(self):
         for p in self.params:
             p.grad = None
         total, lr = self.net.train_step(self.x, self.loss, self.shape, self.targets, self.scale, image_ready=self.input_pairs)
         self.eng.wait_grads()
+        self.eng.configure_clip(*self._clip_config())
         self.eng.sgd_step_device()
         return total, (lr.localization.detach(), lr.objectness.detach(), lr.classification.detach())
 
@@ -137,7 +170,10 @@ class GraphedTrainStep:
         eng = self.eng
         eng.pin_shape(self.B, self.H, self.W)      # the graph bakes this shape's buffer addresses in (Engine.allocate)
         self._load(images, targets)
-        keep = [t.clone() for t in (eng.p_arena, eng.m_arena, eng.rm_arena, eng.rv_arena, eng.nbt_arena)] if preserve_state else None
+        self._clip_cfg = self._clip_config()
+        eng.set_clip(self.gradient_clip_val)
+        state = (eng.p_arena, eng.m_arena, eng.rm_arena, eng.rv_arena, eng.nbt_arena, eng.clip)     # (clip: the skipped-steps count)
+        keep = [t.clone() for t in state] if preserve_state else None
         side = torch.cuda.Stream(device=eng.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -153,16 +189,16 @@ class GraphedTrainStep:
         with torch.cuda.graph(self.graph):
             self.total, self.parts = self._step()
         if keep is not None:
-            for t, k in zip((eng.p_arena, eng.m_arena, eng.rm_arena, eng.rv_arena, eng.nbt_arena), keep):
+            for t, k in zip(state, keep):
                 t.copy_(k)
             eng.mark_params_changed()
         return self
 
     def __call__(self, images: torch.Tensor, targets, lr: Optional[Sequence[float]] = None,
                  momentum: Optional[Sequence[float]] = None, weight_decay: Optional[Sequence[float]] = None,
-                 grad_scale: float = 1.0):
+                 grad_scale: float = 1.0, gradient_clip_val=_KEEP, gradient_clip_algorithm: Optional[str] = None):
         """One replayed step on a new batch.  Returns (total, (box, obj, cls)) - static tensors that the next call
-        overwrites (clone to keep)."""
+        overwrites (clone to keep).  gradient_clip_val: a new max_norm / clamp value from this step on."""
         if self.graph is None:
             raise RuntimeError("call capture() first")
         if self.eng.freeze_flags() != self._freeze_flags:
@@ -173,6 +209,16 @@ class GraphedTrainStep:
             # the graph replays the forward / backward program of the BatchNorm modes it was captured with
             raise RuntimeError("a BatchNorm module changed mode (train / eval) after capture(): the captured step would "
                                "normalise with the old modes; build a new GraphedTrainStep and capture() again")
+        if gradient_clip_val is not _KEEP:
+            self.gradient_clip_val = None if gradient_clip_val is None else float(gradient_clip_val)
+        if gradient_clip_algorithm is not None:
+            self.gradient_clip_algorithm = gradient_clip_algorithm
+        if self._clip_config() != self._clip_cfg:
+            # the graph replays the launches of the clipping mode it was captured with; only the value is device data
+            raise RuntimeError("the gradient clipping algorithm (or clipping on / off, skip_nonfinite, track_grad_norm) changed "
+                               "after capture(): the captured step holds the old launches; build a new GraphedTrainStep and "
+                               "capture() again (gradient_clip_val itself may change per step)")
+        self.eng.set_clip(self.gradient_clip_val)
         if lr is not None:
             self.eng.set_hyper(lr, momentum, weight_decay, grad_scale)
         if self.eng.peer is not None:

@@ -16,7 +16,7 @@ import torch
 from .... import _lib
 from ....core.types import FeatureShape
 from ....core.nms import non_max_suppression
-from ....nn.optim.smart import SmartOptimizer, FusedSGD
+from ....nn.optim.smart import SmartOptimizer, FusedSGD, CLIP_ALGORITHMS
 from ....nn.optim.schedulers import LinearScheduler
 from ...callbacks.map_eval import DeviceMAPEvaluator
 from .layers import get_detections
@@ -50,7 +50,12 @@ class DefaultYolov5Experiment:
                  lr_scheduler: Optional[Callable] = None,
                  optimizer_warmup_updater: Optional[OptimizerWarmupUpdater] = None,
                  val_nms_conf_threshold: float = 0.001, val_nms_iou_threshold: float = 0.6, *, max_epochs: int = 300,
-                 graphed: bool = False, max_targets: int = 4096, world_size: int = 1):
+                 graphed: bool = False, max_targets: int = 4096, world_size: int = 1,
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm"):
+        if gradient_clip_algorithm not in CLIP_ALGORITHMS:
+            raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected one of {CLIP_ALGORITHMS}")
+        # Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm): handed to the FusedSGD / the captured step
+        self.gradient_clip_val, self.gradient_clip_algorithm = gradient_clip_val, gradient_clip_algorithm
         self.net, self.loss, self.anchor_info = net, loss, anchor_info
         self.smart_optimizer = smart_optimizer or SmartOptimizer(
             partial(torch.optim.SGD, lr=0.01, momentum=0.937, nesterov=True), weight_decay=0.0005)
@@ -81,6 +86,14 @@ class DefaultYolov5Experiment:
             self.optimizer = self.smart_optimizer(self.net)
             if isinstance(self.optimizer, FusedSGD):
                 self.optimizer.world_size = self.world_size
+                if self.gradient_clip_val is not None:
+                    # (the reference's partial(torch.optim.SGD, ...) knows no such keywords; a partial(FusedSGD, ...) that
+                    # carries its own keeps them when the experiment has none)
+                    self.optimizer.gradient_clip_val = self.gradient_clip_val
+                    self.optimizer.gradient_clip_algorithm = self.gradient_clip_algorithm
+                    self.optimizer.track_grad_norm = True          # the grad_norm metric, also under "value"
+            elif self.gradient_clip_val is not None and self.graphed:
+                raise RuntimeError("gradient_clip_val with graphed=True needs the HIP network's FusedSGD")
             self.scheduler = self.lr_scheduler(optimizer=self.optimizer, max_epochs=self.max_epochs)
         return [self.optimizer], [self.scheduler]
 
@@ -89,8 +102,13 @@ class DefaultYolov5Experiment:
         self.configure_optimizers()
         return self.scheduler.sch_fn
 
+    def _clipping(self) -> bool:
+        opt = self.optimizer
+        return (self.gradient_clip_val is not None
+                or (isinstance(opt, FusedSGD) and (opt.gradient_clip_val is not None or opt.track_grad_norm)))
+
     def get_metrics_to_display(self):
-        return ["box", "cls", "obj"]
+        return ["box", "cls", "obj"] + (["grad_norm"] if self._clipping() else [])
 
     # exp.py:104-138
     def training_step(self, batch, batch_idx: int = 0):
@@ -134,7 +152,22 @@ class DefaultYolov5Experiment:
         total = self.training_step(batch)
         total.backward()
         self._warmup(num_training_batches)
-        self.optimizer.step()
+        if self._clipping():
+            if isinstance(self.optimizer, FusedSGD):
+                # clipping is inside FusedSGD.step(); the norm stays a device scalar until the metrics are fetched
+                self.optimizer.step()
+                self.logged["grad_norm"] = self.net.engine().clip[0].clone()
+            else:          # a torch network / optimizer: what Lightning's own hook does between backward and step
+                params = [p for g in self.optimizer.param_groups for p in g["params"]]
+                if self.gradient_clip_algorithm == "norm":
+                    self.logged["grad_norm"] = torch.nn.utils.clip_grad_norm_(params, self.gradient_clip_val).detach()
+                else:
+                    self.logged["grad_norm"] = torch.linalg.vector_norm(
+                        torch.stack([torch.linalg.vector_norm(p.grad) for p in params if p.grad is not None])).detach()
+                    torch.nn.utils.clip_grad_value_(params, self.gradient_clip_val)
+                self.optimizer.step()
+        else:
+            self.optimizer.step()
         self.global_step += 1
         return total
 
@@ -150,15 +183,23 @@ class DefaultYolov5Experiment:
         images, targets, _ = batch
         if self._gstep is None:
             B, _, H, W = images.shape
-            self._gstep = GraphedTrainStep(self.net, self.loss, B, H, W, self.max_targets).capture(images, targets)
+            opt = self.optimizer
+            self._gstep = GraphedTrainStep(self.net, self.loss, B, H, W, self.max_targets,
+                                           gradient_clip_val=opt.gradient_clip_val,
+                                           gradient_clip_algorithm=opt.gradient_clip_algorithm,
+                                           skip_nonfinite=opt.skip_nonfinite,
+                                           track_grad_norm=opt.track_grad_norm).capture(images, targets)
         self._warmup(num_training_batches)
         lr, mom, wd = self.optimizer.hyper()
-        total, (box, obj, cls) = self._gstep(images, targets, lr, mom, wd, 1.0 / self.optimizer.world_size)
+        total, (box, obj, cls) = self._gstep(images, targets, lr, mom, wd, 1.0 / self.optimizer.world_size,
+                                             gradient_clip_val=self.optimizer.gradient_clip_val)
         self.optimizer.steps_taken += 1
         # the replayed graph contains the SGD update: tell torch's bookkeeping that a step happened (LambdaLR.step() checks
         # optimizer._step_count to warn about a scheduler stepped before the optimizer)
         self.optimizer._step_count = getattr(self.optimizer, "_step_count", 0) + 1
         self.logged = {"obj": obj, "cls": cls, "box": box}
+        if self._clipping():
+            self.logged["grad_norm"] = self._gstep.grad_norm[0]          # (static, like the loss parts)
         self.global_step += 1
         return total.clone()
 

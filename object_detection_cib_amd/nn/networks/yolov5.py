@@ -267,6 +267,19 @@ class Yolov5Network(nn.Module):
                 total = scale * (lr.localization + lr.classification + lr.objectness)
         return total, lr
 
+    # ------------------------------------------------------------------ gradient clipping (eager)
+    def clip_grad_norm_(self, max_norm: float) -> torch.Tensor:
+        """torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm) over the gradient arena: one deterministic fp64
+        reduction and one in-place scale instead of torch's foreach over every tensor.  Returns the total norm before
+        clipping as a device scalar (no host synchronisation); parameters whose .grad is None (frozen) do not count.
+        Like torch's it sees .grad as published: under data parallelism that is the sum over the ranks (FusedSGD applies
+        1 / world_size in its update) - FusedSGD(gradient_clip_val=...) is the form that clips the average."""
+        return self.engine().clip_grads_inplace("norm", max_norm)
+
+    def clip_grad_value_(self, clip_value: float) -> None:
+        """torch.nn.utils.clip_grad_value_(net.parameters(), clip_value): .grad clamped to [-clip_value, clip_value] in place."""
+        self.engine().clip_grads_inplace("value", clip_value)
+
     def forward(self, x: torch.Tensor) -> Yolov5NetworkResult:
         raws = self.forward_raw(x)
         return Yolov5NetworkResult(*[DetectionHeadResult(t[..., 0:4], t[..., 4:5], t[..., 5:]) for t in raws])

@@ -11,10 +11,13 @@ parameter / gradient / momentum arenas instead of torch's foreach update over 18
 from __future__ import annotations
 
 from functools import partial
-from typing import Callable
+from typing import Callable, Optional
 
 import torch
 import torch.nn as nn
+
+
+CLIP_ALGORITHMS = ("norm", "value")
 
 
 def split_param_groups(net: nn.Module):
@@ -36,11 +39,16 @@ class FusedSGD(torch.optim.Optimizer):
     """torch.optim.SGD (momentum with or without Nesterov, dampening, maximize) over a HIP Yolov5Network: same
     param_groups / state_dict layout, the update itself is the engine's fused multi-tensor kernel.  lr / momentum /
     weight_decay are read from ``param_groups`` at every ``step()`` (so warm-up and LR schedulers work unchanged);
-    dampening, nesterov and maximize are the constructor's (one value for all groups, as SmartOptimizer builds them)."""
+    dampening, nesterov and maximize are the constructor's (one value for all groups, as SmartOptimizer builds them).
+    gradient_clip_val / gradient_clip_algorithm / skip_nonfinite: gradient clipping fused into ``step()`` (see __init__)."""
 
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0,
                  weight_decay: float = 0.0, nesterov: bool = False, *, net: nn.Module, world_size: int = 1,
-                 maximize: bool = False, foreach=None, differentiable: bool = False):
+                 maximize: bool = False, foreach=None, differentiable: bool = False,
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
+                 skip_nonfinite: bool = False, track_grad_norm: bool = False):
+        if gradient_clip_algorithm not in CLIP_ALGORITHMS:            # (Lightning: MisconfigurationException at Trainer())
+            raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected one of {CLIP_ALGORITHMS}")
         if nesterov and (momentum <= 0 or dampening != 0):            # torch.optim.SGD.__init__
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         if foreach is False or differentiable:
@@ -53,6 +61,11 @@ class FusedSGD(torch.optim.Optimizer):
         self._nesterov = bool(nesterov)
         self._dampening, self._maximize = float(dampening), bool(maximize)
         self.steps_taken = 0          # torch keeps no momentum_buffer before the first step (checkpoint layout)
+        # Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm): applied inside step() - the norm reduction
+        # and the SGD form that consumes its coefficient, after the 1 / world_size scale (torch's order).  Plain attributes:
+        # an experiment sets them on the optimizer it gets back from a partial(torch.optim.SGD, ...), as it sets world_size
+        self.gradient_clip_val, self.gradient_clip_algorithm = gradient_clip_val, gradient_clip_algorithm
+        self.skip_nonfinite, self.track_grad_norm = bool(skip_nonfinite), bool(track_grad_norm)
 
     def _by_name(self):
         g = {pg.get("name"): pg for pg in self.param_groups}
@@ -68,6 +81,13 @@ class FusedSGD(torch.optim.Optimizer):
         g = self._by_name()
         return ([float(x["lr"]) for x in g], [float(x["momentum"]) for x in g], [float(x["weight_decay"]) for x in g])
 
+    def clip_config(self):
+        """(algorithm or None, skip_nonfinite, track_grad_norm): Engine.configure_clip's arguments"""
+        if self.gradient_clip_algorithm not in CLIP_ALGORITHMS:
+            raise ValueError(f"gradient_clip_algorithm {self.gradient_clip_algorithm!r}: expected one of {CLIP_ALGORITHMS}")
+        return (self.gradient_clip_algorithm if self.gradient_clip_val is not None else None, self.skip_nonfinite,
+                self.track_grad_norm)
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -75,7 +95,10 @@ class FusedSGD(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         lr, mom, wd = self.hyper()
-        self.net.engine().sgd_step(lr, mom, wd, 1.0 / self.world_size)
+        eng = self.net.engine()
+        eng.configure_clip(*self.clip_config())
+        eng.set_clip(self.gradient_clip_val)
+        eng.sgd_step(lr, mom, wd, 1.0 / self.world_size)
         self.steps_taken += 1
         return loss
 
