@@ -8,15 +8,14 @@ the optimizer is one launch.  Mixed into engine.executor.Engine.
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, List, Optional
+from typing import Dict, Optional
 
 import numpy as np
 
 import torch
 
 from .. import _lib
-from .graph import Graph, ConvUnit, HeadUnit, View, Buf, head_param
+from .graph import Graph, head_param
 
 
 def _pad(n: int, a: int = 64) -> int:
@@ -59,6 +58,29 @@ class _UnitState:
     __slots__ = ("u", "w_off", "g_off", "b_off", "f_off", "d_off", "Kp", "Kdp", "rs_off", "stats", "T",
                  "sums", "aff", "bsums", "bsums_g", "bpart", "T2", "coef", "raw", "M", "H", "W", "Ho", "Wo",
                  "fused_red", "segs", "seg_slots", "Kp_f", "raw_ld", "s2_fold", "stem_fused", "wg_dual")
+
+
+class _StagingRing:
+    """Pinned staging ring of small host -> device uploads issued outside any captured graph (optimizer hyper-parameters,
+    the clip value): the H2D copy is asynchronous, so a slot is not rewritten for the next 15 uploads."""
+
+    def __init__(self, numel: int, slots: int = 16):
+        self.host = [torch.zeros(numel, dtype=torch.float32).pin_memory() for _ in range(slots)]
+        self.events = [None] * slots
+        self.slot = 0
+
+    def upload(self, dst: torch.Tensor, values):
+        """dst <- a slot whose first len(values) elements are `values`, on the current stream"""
+        k = self.slot
+        self.slot = (k + 1) % len(self.host)
+        if self.events[k] is not None:          # the DMA that last read this pinned slot must have run
+            self.events[k].synchronize()
+        host = self.host[k]
+        host[:len(values)].copy_(torch.tensor(values, dtype=torch.float32))
+        dst.copy_(host, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.events[k] = ev
 
 
 class ArenaMixin:
@@ -175,10 +197,7 @@ class ArenaMixin:
         self._f32_frozen = {}             # freeze key -> F32Plan over the writes backward still issues
         self._stepped_key = None
         self._hyper_args = None
-        # pinned staging ring: the H2D copy is asynchronous, so a slot is not rewritten for the next 15 uploads
-        self._hyper_host = [torch.zeros(12, dtype=torch.float32).pin_memory() for _ in range(16)]
-        self._hyper_events = [None] * len(self._hyper_host)
-        self._hyper_slot = 0
+        self._hyper_ring = _StagingRing(12)
         self._hyper_vals = None
         # gradient norm / clipping (csrc/misc_ops.hip, clip block layout in include/kodhip.h): off by default - the step then
         # issues exactly the launches it always did
@@ -191,9 +210,7 @@ class ArenaMixin:
         self._count_masks = {}                         # freeze key (None: default plan) -> u8 per element: counts in the norm
         self._unit_hyper = torch.zeros(12, dtype=torch.float32, device=device)
         self._unit_hyper[9] = 1.0                      # grad_scale 1: the norm of .grad as published (clip_grad_norm_)
-        self._clip_host = [torch.zeros(4, dtype=torch.float32).pin_memory() for _ in range(16)]
-        self._clip_events = [None] * len(self._clip_host)
-        self._clip_slot = 0
+        self._clip_ring = _StagingRing(4)
         self.clip[8] = float("inf")                    # input slot: max_norm / clamp value (set_clip); inf clips nothing
         self._clip_val = float("inf")
 
@@ -263,16 +280,23 @@ class ArenaMixin:
         fz = self.freeze
         return None if (fz is None or fz.is_default) else fz
 
+    def _require_same_on_all_ranks(self, key, what):
+        """Every rank must run the same program (the same collectives): `key` is compared across the group and a
+        mismatch raises on every rank before any collective of the step.  `what`: the error text ("{keys}": what the
+        ranks hold)."""
+        if not (self.collectives and self.world_size > 1):
+            return
+        import torch.distributed as dist
+        keys = [None] * self.world_size
+        dist.all_gather_object(keys, key, group=self.process_group)
+        if any(k != key for k in keys):
+            raise RuntimeError(what.format(keys=keys))
+
     def _on_freeze_change(self, plan):
-        if self.collectives and self.world_size > 1:
-            # every rank must run the same backward program (the same collectives): the freeze set is compared across
-            # the group whenever it changes - so every rank changes it at the same step, as a training script does
-            import torch.distributed as dist
-            keys = [None] * self.world_size
-            dist.all_gather_object(keys, plan.key, group=self.process_group)
-            if any(k != plan.key for k in keys):
-                raise RuntimeError("the ranks disagree on which parameters are frozen (requires_grad): every rank must "
-                                   "freeze the same set")
+        # the freeze set is compared across the group whenever it changes - so every rank changes it at the same step, as
+        # a training script does
+        self._require_same_on_all_ranks(plan.key, "the ranks disagree on which parameters are frozen (requires_grad): "
+                                        "every rank must freeze the same set")
         if plan.is_default:
             self.keep_mask = None
             return
@@ -312,64 +336,12 @@ class ArenaMixin:
         return None if (mp is None or mp.is_default) else mp
 
     def _on_bn_mode_change(self, plan):
-        if self.collectives and self.world_size > 1:
-            # every rank must run the same collectives (eval units leave the SyncBN exchanges): compared across the group
-            # whenever the eval set changes, so a mismatch raises on every rank before any exchange
-            import torch.distributed as dist
-            keys = [None] * self.world_size
-            dist.all_gather_object(keys, plan.key, group=self.process_group)
-            if any(k != plan.key for k in keys):
-                raise RuntimeError("the ranks disagree on which BatchNorm modules are in eval mode: every rank must put "
-                                   "the same modules in eval mode")
+        # (eval units leave the SyncBN exchanges): compared across the group whenever the eval set changes, so a mismatch
+        # raises on every rank before any exchange
+        self._require_same_on_all_ranks(plan.key, "the ranks disagree on which BatchNorm modules are in eval mode: every "
+                                        "rank must put the same modules in eval mode")
         if not plan.is_default and plan.key not in self._nbt_inc:
             self._nbt_inc[plan.key] = torch.tensor(plan.train_mask(), dtype=torch.int64, device=self.device)
-
-    def _bn_eval_table(self, mp):
-        """(device descriptor table, unit count) of the forward's kodhip_bn_eval_constants launch for the current buffer
-        set.  One table per eval set and buffer set, kept for the engine's lifetime: a captured step bakes its address in."""
-        from .bn_mode import eval_constant_units
-        units = eval_constant_units(mp, self.freeze_active())
-        ptrs = tuple((self.ustate[n].aff.data_ptr(), self.ustate[n].coef.data_ptr() if c else 0) for n, c in units)
-        key = (mp.key, ptrs)
-        t = self._bn_eval_tables.get(key)
-        if t is None:
-            assert self.lib.kodhip_bn_eval_desc_bytes() == 8 * 8
-            pa, rm, rv = self.p_arena.data_ptr(), self.rm_arena.data_ptr(), self.rv_arena.data_ptr()
-            rows = []
-            for (n, _), (aff, coef) in zip(units, ptrs):
-                st = self.ustate[n]
-                rows.append([pa + 4 * st.g_off, pa + 4 * st.b_off, rm + 4 * st.rs_off, rv + 4 * st.rs_off, aff, coef,
-                             st.u.cout, 0])
-            t = torch.tensor(rows, dtype=torch.int64).to(self.device)
-            self._bn_eval_tables[key] = t
-        return t, len(units)
-
-    def _frozen_f32plan(self, fz):
-        """EngineOptions.dx_accum_fp32 under a freeze plan: the fp32-accumulation modes planned over the gradient writes
-        that backward still issues (engine/plan.py; skipped writers change who is first / last of a buffer)."""
-        from .plan import backward_writes, plan_f32_accumulation
-        cached = self._f32_frozen.get(fz.key)
-        if cached is None:
-            ws, _ = backward_writes(self.g, {v.name for v in self._dual.values()})
-            kept = []
-            for w in ws:
-                kind, ident = w.key
-                if kind == "dgrad":
-                    ok = fz.units[ident].needs_in_grad
-                elif kind == "res":
-                    ok = fz.units[ident].res_grad
-                elif kind == "head":
-                    ok = fz.heads[ident].needs_in_grad
-                else:
-                    ok = fz.op_in_grad[ident]
-                if ok:
-                    kept.append(w)
-            cached = plan_f32_accumulation(kept, {b.name: b.C for b in self.g.bufs})
-            self._f32_frozen[fz.key] = cached
-        for name in cached.shadow_bufs:           # (a buffer that needs a shadow only with fewer writers)
-            if name not in self.gact32:
-                self.gact32[name] = torch.empty(self.gact[name].shape, dtype=torch.float32, device=self.device)
-        return cached
 
     def current_grad_arena(self):
         """Arena holding the gradients published by the last backward()."""
@@ -384,16 +356,7 @@ class ArenaMixin:
         flags = (1.0 if self.sgd_nesterov else 0.0) + (2.0 if self.sgd_maximize else 0.0) + (4.0 if first else 0.0)
         vals = (*lr, *momentum, *weight_decay, grad_scale, flags, float(self.sgd_dampening))
         if vals != self._hyper_vals:                       # only touch the device copy when the schedule moved
-            k = self._hyper_slot
-            self._hyper_slot = (k + 1) % len(self._hyper_host)
-            if self._hyper_events[k] is not None:          # the DMA that last read this pinned slot must have run
-                self._hyper_events[k].synchronize()
-            host = self._hyper_host[k]
-            host.copy_(torch.tensor(vals, dtype=torch.float32))
-            self.hyper.copy_(host, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._hyper_events[k] = ev
+            self._hyper_ring.upload(self.hyper, vals)
             self._hyper_vals = vals
 
     def sgd_step(self, lr, momentum, weight_decay, grad_scale: float = 1.0):
@@ -418,16 +381,7 @@ class ArenaMixin:
         captured graph, like set_hyper.  None = +inf: nothing is clipped (skip_nonfinite without a clip value)."""
         v = float("inf") if value is None else float(value)
         if v != self._clip_val:
-            k = self._clip_slot
-            self._clip_slot = (k + 1) % len(self._clip_host)
-            if self._clip_events[k] is not None:
-                self._clip_events[k].synchronize()
-            host = self._clip_host[k]
-            host[0] = v
-            self.clip[8:12].copy_(host, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._clip_events[k] = ev
+            self._clip_ring.upload(self.clip[8:12], (v,))
             self._clip_val = v
 
     def _count_mask(self):

@@ -8,13 +8,11 @@ module asks libkodhip for the slot / split counts of each launch and allocates a
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, List, Optional
+from typing import Dict
 
 import torch
 
 from .. import _lib
-from .graph import Graph, ConvUnit, HeadUnit, View, Buf
 from .arenas import _pad
 from .plan import backward_writes, plan_f32_accumulation, plan_dual_dgrads, plan_bn_reduce_fusion
 
@@ -152,12 +150,8 @@ class BufferMixin:
         if not (self.collectives and self.sync_bn and self.world_size > 1) or key in self._checked_shapes:
             return
         self._checked_shapes.add(key)
-        import torch.distributed as dist
-        shapes = [None] * self.world_size
-        dist.all_gather_object(shapes, tuple(key), group=self.process_group)
-        if any(tuple(s) != tuple(key) for s in shapes):
-            raise RuntimeError(f"SyncBN needs the same local batch shape on every rank, got {shapes}: pad or drop the "
-                               "last uneven batch (DistributedSampler drop_last / padding)")
+        self._require_same_on_all_ranks(tuple(key), "SyncBN needs the same local batch shape on every rank, got {keys}: pad "
+                                        "or drop the last uneven batch (DistributedSampler drop_last / padding)")
 
     def _plan_bn_fusion(self, B: int):
         """Turns the static plans of engine/plan.py into launch state for this shape: which CSP entry convs share a dual

@@ -28,9 +28,11 @@ from .backward import BackwardMixin
 
 class Engine(ArenaMixin, BufferMixin, ForwardMixin, BackwardMixin):
     """Owns arenas + buffers for one network instance (one process, one GPU).  The work is split by concern:
-    engine/options.py (every switch), engine/plan.py + engine/ddp.py (pure planning, CPU-testable), engine/arenas.py
-    (parameters, packs, optimizer), engine/buffers.py (per-shape buffer sets), engine/forward.py / engine/backward.py
-    (the launch programs), engine/comm.py (RCCL communicator, SyncBN peer exchange)."""
+    engine/options.py (every switch), engine/plan.py + engine/ddp.py + engine/freeze.py + engine/bn_mode.py (pure
+    planning, CPU-testable), engine/arenas.py (parameters, packs, optimizer), engine/buffers.py (per-shape buffer sets),
+    engine/forward.py / engine/backward.py (the launch programs; the state of one backward pass lives in
+    backward._BackwardPass, the engine keeps none between calls), engine/comm.py (RCCL communicator, SyncBN peer
+    exchange)."""
 
     def __init__(self, graph: Graph, params: Dict[str, torch.nn.Parameter], buffers: Dict[str, torch.Tensor],
                  options: Optional[EngineOptions] = None):
@@ -75,7 +77,6 @@ class Engine(ArenaMixin, BufferMixin, ForwardMixin, BackwardMixin):
         self._bn_mode_flags = None
         self._bn_eval_tables = {}      # (eval set, buffer addresses) -> device descriptor table of kodhip_bn_eval_constants
         self._nbt_inc = {}             # eval set -> per-unit num_batches_tracked increment (1 = train mode)
-        self._fork_ev = None
         self.br_stream = None         # side stream of the CSP short_conv branch in forward()
         self.head_stream = None       # side stream of the P3 / P4 head convolutions in forward()
         self.aux_stream = None        # side stream of work that only depends on the step's inputs (label assignment)

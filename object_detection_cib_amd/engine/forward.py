@@ -6,15 +6,10 @@ BatchNorm -> SiLU units, torch.cat / nn.Upsample as channel-slice writes, the th
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import Dict, List, Optional
-
-import numpy as np
-
 import torch
 
 from .. import _lib
-from .graph import Graph, ConvUnit, HeadUnit, View, Buf
+from .graph import ConvUnit, HeadUnit, View
 
 BN_EPS, BN_MOMENTUM = 1e-3, 0.03        # kod/nn/networks/yolov5.py:24
 
@@ -151,6 +146,14 @@ class ForwardMixin:
             in_px = B * H * W if u.stem else B * st.H * st.W
             self._t1(e0, "conv_fwd", 2 * (in_px * cin_true + st.M * C_), name=u.name)
 
+        def finalize_args(u: ConvUnit, ranks: int):
+            """the finalize kernels' common arguments: (element count over `ranks`, gamma, beta, running mean / variance,
+            momentum, eps, scale | shift | mean | rstd of st.aff, channels, update the running statistics)"""
+            st, C_ = self.ustate[u.name], u.cout
+            aff = st.aff.data_ptr()
+            return (float(st.M) * ranks, pa + 4 * st.g_off, pa + 4 * st.b_off, rm + 4 * st.rs_off, rv + 4 * st.rs_off,
+                    self.bn_momentum, self.bn_eps, aff, aff + 4 * C_, aff + 8 * C_, aff + 12 * C_, C_, 1)
+
         def stats_stage(group, s=s):
             """Batch statistics -> BatchNorm constants.  Under SyncBN the [sum, sum of squares] vectors of the group's
             units (a CSP layer's main + short convs) are exchanged as ONE grouped collective."""
@@ -161,33 +164,21 @@ class ForwardMixin:
             e0 = self._t0()
             if not sync:
                 for u in group:
-                    st, C_ = self.ustate[u.name], u.cout
-                    aff = st.aff.data_ptr()
-                    chk(lib.kodhip_bn_finalize_partials(st.stats.data_ptr(), st.T, float(st.M), pa + 4 * st.g_off,
-                                                        pa + 4 * st.b_off, rm + 4 * st.rs_off, rv + 4 * st.rs_off,
-                                                        self.bn_momentum, self.bn_eps, aff, aff + 4 * C_, aff + 8 * C_,
-                                                        aff + 12 * C_, C_, 1, s), u.name)
+                    st = self.ustate[u.name]
+                    chk(lib.kodhip_bn_finalize_partials(st.stats.data_ptr(), st.T, *finalize_args(u, 1), s), u.name)
             elif self.peer is not None:
                 # SyncBN over peer buffers: the same single launch per unit, the ranks' sums meet inside the kernel
                 for u in group:
-                    st, C_ = self.ustate[u.name], u.cout
-                    aff = st.aff.data_ptr()
-                    chk(lib.kodhip_bn_finalize_partials_peer(st.stats.data_ptr(), st.T, float(st.M) * self.world_size,
-                                                             pa + 4 * st.g_off, pa + 4 * st.b_off, rm + 4 * st.rs_off,
-                                                             rv + 4 * st.rs_off, self.bn_momentum, self.bn_eps, aff, aff + 4 * C_,
-                                                             aff + 8 * C_, aff + 12 * C_, C_, 1, self.peer.view_ptr(),
-                                                             self.peer_slots[(u.name, "f")], s), u.name)
+                    st = self.ustate[u.name]
+                    chk(lib.kodhip_bn_finalize_partials_peer(st.stats.data_ptr(), st.T, *finalize_args(u, self.world_size),
+                                                             self.peer.view_ptr(), self.peer_slots[(u.name, "f")], s), u.name)
             else:
                 for u in group:
                     st = self.ustate[u.name]
                     chk(lib.kodhip_bn_reduce_partials(st.stats.data_ptr(), st.sums.data_ptr(), u.cout, st.T, s), u.name)
                 self._allreduce_group([self.ustate[u.name].sums for u in group])
                 for u in group:
-                    st, C_ = self.ustate[u.name], u.cout
-                    aff = st.aff.data_ptr()
-                    chk(lib.kodhip_bn_finalize(st.sums.data_ptr(), float(st.M) * self.world_size, pa + 4 * st.g_off,
-                                               pa + 4 * st.b_off, rm + 4 * st.rs_off, rv + 4 * st.rs_off, self.bn_momentum,
-                                               self.bn_eps, aff, aff + 4 * C_, aff + 8 * C_, aff + 12 * C_, C_, 1, s), u.name)
+                    chk(lib.kodhip_bn_finalize(self.ustate[u.name].sums.data_ptr(), *finalize_args(u, self.world_size), s), u.name)
             self._t1(e0, "bn_finalize", sum(8.0 * u.cout * self.ustate[u.name].T for u in group), name="+".join(u.name for u in group))
 
         def apply_stage(u: ConvUnit, s=s):
@@ -201,6 +192,11 @@ class ForwardMixin:
                                         res.coff if res else 0,
                                         self._ptr(u.dst), u.dst.buf.C, u.dst.coff, st.M, C_, self.act_kind, self.act_slope, s), u.name)
             self._t1(e0, "bn_silu_apply", (6.0 if res else 4.0) * st.M * C_, name=u.name)
+
+        def run_unit(u: ConvUnit, s=s):
+            conv_stage(u, s)
+            stats_stage([u], s)
+            apply_stage(u, s)
 
         # A CSP layer's short_conv (conv -> statistics -> apply) depends only on the layer input and is needed only by
         # last_conv: it runs on a side stream next to main_conv and the blocks, where it fills the chip while the main
@@ -241,20 +237,13 @@ class ForwardMixin:
                 # graph executor keeps a node's first captured successor on its queue (see backward())
                 fork = torch.cuda.Event()
                 fork.record(main_stream)
-                conv_stage(op.unit)
-                stats_stage([op.unit])
-                apply_stage(op.unit)
+                run_unit(op.unit)
                 self.br_stream.wait_event(fork)
-                bs = self.br_stream.cuda_stream
-                conv_stage(short, bs)
-                stats_stage([short], bs)
-                apply_stage(short, bs)
+                run_unit(short, self.br_stream.cuda_stream)
                 joined_buf = short.dst.buf.name
                 continue
             if op.kind == "conv" and op.unit.dst.buf.name in head_src and not (branch and op.unit.sibling is not None):
-                conv_stage(op.unit)
-                stats_stage([op.unit])
-                apply_stage(op.unit)
+                run_unit(op.unit)
                 ev = torch.cuda.Event()
                 ev.record(main_stream)
                 head_src[op.unit.dst.buf.name] = ev
@@ -317,6 +306,26 @@ class ForwardMixin:
         for v in self.g.outputs:                # sub-network graphs: their output views, NCHW fp32
             outs.append(self.act[v.buf.name][..., v.coff:v.coff + v.C].permute(0, 3, 1, 2).float())
         return outs
+
+    def _bn_eval_table(self, mp):
+        """(device descriptor table, unit count) of the forward's kodhip_bn_eval_constants launch for the current buffer
+        set.  One table per eval set and buffer set, kept for the engine's lifetime: a captured step bakes its address in."""
+        from .bn_mode import eval_constant_units
+        units = eval_constant_units(mp, self.freeze_active())
+        ptrs = tuple((self.ustate[n].aff.data_ptr(), self.ustate[n].coef.data_ptr() if c else 0) for n, c in units)
+        key = (mp.key, ptrs)
+        t = self._bn_eval_tables.get(key)
+        if t is None:
+            assert self.lib.kodhip_bn_eval_desc_bytes() == 8 * 8
+            pa, rm, rv = self.p_arena.data_ptr(), self.rm_arena.data_ptr(), self.rv_arena.data_ptr()
+            rows = []
+            for (n, _), (aff, coef) in zip(units, ptrs):
+                st = self.ustate[n]
+                rows.append([pa + 4 * st.g_off, pa + 4 * st.b_off, rm + 4 * st.rs_off, rv + 4 * st.rs_off, aff, coef,
+                             st.u.cout, 0])
+            t = torch.tensor(rows, dtype=torch.int64).to(self.device)
+            self._bn_eval_tables[key] = t
+        return t, len(units)
 
     def _eval_affine_ptrs(self):
         """Eval-mode BatchNorm constants of every unit (scale = gamma * rsqrt(running_var + eps), shift = beta -

@@ -19,7 +19,7 @@ only where an eval unit's gamma and beta are both frozen (no coefficient kernel 
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, List, Mapping, Optional, Tuple
+from typing import Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple
 
 from .graph import Graph, View, head_param
 
@@ -149,3 +149,42 @@ def trainable_span(unit_starts, plan: FreezePlan, layout: Mapping[str, Tuple[int
     while i + 1 < len(unit_starts) and unit_starts[i + 1] <= first:
         i += 1
     return i
+
+
+class UnitLaunch(NamedTuple):
+    """What backward launches for one conv unit of a group (BackwardPass.unit)"""
+    dgrad: str                   # "own" | "skip" (its main_conv's dual launch covers it) | "dual" | "none" (nobody needs it)
+    partner: object              # the short_conv a "dual" data gradient also serves, else None
+    dual_w: bool                 # the pair's weight gradients are one launch
+    w_grad: bool                 # the weight gradient is needed
+    res_grad: bool               # the residual pass-through is needed
+
+
+def group_launches(group: Sequence, plan: Optional[FreezePlan], dual, wg_dual: bool) -> List[Optional[UnitLaunch]]:
+    """The backward launches of one unit group ([unit] or [short_conv, main_conv]), one entry per unit in group order;
+    None = the unit lies outside the plan's grad region and launches nothing (its gradient-bucket tick stays, in order).
+    plan None = the default plan (everything trainable): the same answer without a plan object.  dual: the main_convs
+    that have a dual data gradient (engine/plan.py plan_dual_dgrads); wg_dual: the pair has a dual weight gradient.  The
+    pair's dual forms are used only when both partners run them - one data gradient when the shared input needs a
+    gradient, one weight gradient when both weights are trainable - and fall back to the single forms otherwise."""
+    if plan is None:
+        flags = [UnitFreeze(True, (True, True), True, not u.stem, u.residual is not None) for u in group]
+    else:
+        flags = [plan.units[u.name] for u in group]
+    runs = [i for i, f in enumerate(flags) if f.needs_out_grad or f.res_grad]
+    is_dual = dual_w = False
+    if len(runs) == 2:
+        is_dual = flags[0].needs_in_grad and group[1].name in dual
+        dual_w = is_dual and wg_dual and flags[0].w_trainable and flags[1].w_trainable
+    elif len(group) == 2 and len(runs) == 1:
+        # a CSP entry pair reads one full buffer: the partner outside the grad region means it needs no data gradient
+        assert not flags[runs[0]].needs_in_grad, (group[0].name, group[1].name)
+    out: List[Optional[UnitLaunch]] = []
+    for i, f in enumerate(flags):
+        if i not in runs:
+            out.append(None)
+        elif is_dual:
+            out.append(UnitLaunch("skip" if i == 0 else "dual", group[0] if i == 1 else None, dual_w, f.w_trainable, f.res_grad))
+        else:
+            out.append(UnitLaunch("own" if f.needs_in_grad else "none", None, dual_w, f.w_trainable, f.res_grad))
+    return out

@@ -1,6 +1,6 @@
 """Static analysis of the backward program (pure host logic, no GPU: tests/test_host_logic.py).
 
-The engine's backward pass (engine/executor.py) walks the forward op list in reverse.  Several decisions depend only on
+The engine's backward pass (engine/backward.py) walks the forward op list in reverse.  Several decisions depend only on
 WHO WRITES WHICH GRADIENT BUFFER IN WHAT ORDER, which is a property of the graph (engine/graph.py), not of the data:
 
 * which data-gradient launch is the last writer of a conv unit's output gradient (it then also carries that unit's

@@ -137,3 +137,94 @@ def test_buckets_tile_the_trainable_span():
     assert plan_buckets(starts, n, 4096) == plan_buckets(starts, n, 4096, trainable_span(starts, _plan(g), layout))
     assert plan_buckets(starts, n, 4096)[-1][1] == 0
     assert trainable_span(starts, _plan(g, lambda n_: True), layout) == -1
+
+
+# ---------------------------------------------------------------------------------------------- group_launches
+def _groups(g, dual, pair_all=False):
+    """backward's unit groups: reversed op list, [short_conv, main_conv] where the pair shares a launch (a dual data
+    gradient; pair_all: every sibling pair, as under RCCL SyncBN)"""
+    rops, ri, out = list(reversed(g.ops)), 0, []
+    while ri < len(rops):
+        op = rops[ri]
+        ri += 1
+        if op.kind != "conv":
+            continue
+        grp = [op.unit]
+        if ri < len(rops) and rops[ri].kind == "conv" and rops[ri].unit.sibling is op.unit and \
+                (pair_all or rops[ri].unit.name in dual):
+            grp.append(rops[ri].unit)
+            ri += 1
+        out.append(grp)
+    return out
+
+
+def _launches(g, plan, dual, grp, wg_dual=True):
+    """group_launches with the partner written as its name"""
+    from object_detection_cib_amd.engine.freeze import group_launches
+    out = group_launches(grp, plan, dual, wg_dual and len(grp) == 2)
+    return [None if ln is None else (ln.dgrad, ln.partner.name if ln.partner is not None else None, ln.dual_w, ln.w_grad,
+                                     ln.res_grad) for ln in out]
+
+
+@pytest.mark.parametrize("dual_on", [True, False])
+@pytest.mark.parametrize("pair_all", [False, True])
+@pytest.mark.parametrize("wg_dual", [True, False])
+def test_group_launches_without_a_plan_equal_the_default_plan(dual_on, pair_all, wg_dual):
+    from object_detection_cib_amd.engine.plan import plan_dual_dgrads
+    g = _g()
+    dual = set(plan_dual_dgrads(g)) if dual_on else set()
+    default = _plan(g)
+    assert default.is_default
+    groups = _groups(g, dual, pair_all)
+    assert sum(len(grp) for grp in groups) == len([op for op in g.ops if op.kind == "conv"])
+    for grp in groups:
+        got = _launches(g, None, dual, grp, wg_dual)
+        assert got == _launches(g, default, dual, grp, wg_dual), [u.name for u in grp]
+        assert all(ln is not None and ln[3] for ln in got)                    # every unit runs, every weight gradient
+        if len(grp) == 2 and grp[1].name in dual:
+            assert [ln[0] for ln in got] == ["skip", "dual"] and got[1][1] == grp[0].name
+            assert got[0][2] == got[1][2] == wg_dual
+        else:
+            assert [ln[0] for ln in got] == ["none" if u.stem else "own" for u in grp]
+            assert not any(ln[2] for ln in got)
+
+
+def test_group_launches_under_freeze_plans():
+    """Where a plan's answer differs from the default's, written out; the values are what the engine's separate
+    freeze-plan path handed to the unit launches for the same plans before the default and the freeze path became one."""
+    from object_detection_cib_amd.engine.plan import plan_dual_dgrads
+    g = _g()
+    dual = set(plan_dual_dgrads(g))
+    default = _plan(g)
+    groups = _groups(g, dual)
+    bb = [tuple(u.name for u in grp) for grp in groups if grp[0].name.startswith("backbone.")]
+    S1 = "backbone.stages.stage1.blocks.1."
+    TD = "neck.top_down_layers.1."
+    cases = {
+        # no data gradient where needs_in_grad is false, nothing at all in the no-grad region (the tick stays: None)
+        "backbone": (lambda n: n.startswith("backbone."),
+                     {("neck.reduce_layers.2",): [("none", None, False, True, False)],
+                      **{names: [None] * len(names) for names in bb}}),
+        "stem": (lambda n: n.startswith("backbone.stem."),
+                 {("backbone.stages.stage1.blocks.0",): [("none", None, False, True, False)],
+                  ("backbone.stem",): [None]}),
+        "mid_conv_weight": (lambda n: n == "backbone.stages.stage2.blocks.1.blocks.0.conv1.0.weight",
+                            {("backbone.stages.stage2.blocks.1.blocks.0.conv1",): [("own", None, False, False, False)]}),
+        # one weight of a pair frozen: the dual data gradient stays, the dual weight gradient does not
+        "short_weight": (lambda n: n == TD + "short_conv.0.weight",
+                         {(TD + "short_conv", TD + "main_conv"): [("skip", None, False, False, False),
+                                                                  ("dual", TD + "short_conv", False, True, False)]}),
+        # one partner of a pair outside the grad region: the other takes the single forms
+        "entry_and_short": (lambda n: n.startswith(("backbone.stem.", "backbone.stages.stage1.blocks.0.", S1 + "short_conv.")),
+                            {(S1 + "short_conv", S1 + "main_conv"): [None, ("none", None, False, True, False)],
+                             ("backbone.stages.stage1.blocks.0",): [None], ("backbone.stem",): [None]}),
+    }
+    assert len(bb) == 29
+    for key, (frozen, want) in cases.items():
+        plan = _plan(g, frozen)
+        differs = {}
+        for grp in groups:
+            got = _launches(g, plan, dual, grp)
+            if got != _launches(g, default, dual, grp):
+                differs[tuple(u.name for u in grp)] = got
+        assert differs == want, key

@@ -1,0 +1,50 @@
+"""The launch program of the training step, pinned: one eager step's libkodhip calls, stream / event operations and aten
+operations (tools/launch_trace.py) for every engine switch, freeze set, BatchNorm mode, collective mode and clipping mode,
+against tests/golden/launch_trace.json (per configuration: number of lines, launches per entry point, SHA-256 of the text).
+
+The eager sequence of stream operations is what a capture turns into graph nodes and edges: equal traces mean an equal
+captured graph.  A refactor of engine/forward.py / engine/backward.py / the optimizer step must leave every hash where it
+is.  A pull request that changes the program on purpose re-records the file on its own tree and shows the diff of the
+traces (`--keep` writes them next to the JSON):
+
+    python tools/launch_trace.py --record tests/golden/launch_trace.json [--keep DIR]
+"""
+import importlib.util
+import json
+import os
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_spec = importlib.util.spec_from_file_location("launch_trace", os.path.join(ROOT, "tools", "launch_trace.py"))
+launch_trace = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(launch_trace)
+
+GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "launch_trace.json")))
+# a child that ended by a signal, an abort or its time limit: no further GPU child is started in this run
+_stopped = []
+
+
+def test_golden_covers_the_table():
+    assert sorted(GOLDEN) == sorted(launch_trace.CONFIGS)
+
+
+@pytest.mark.parametrize("config", list(launch_trace.CONFIGS))
+def test_launch_trace_equals_golden(config, tmp_path):
+    if _stopped:
+        pytest.fail(f"not started: the trace child of {_stopped[0]} ended by a signal or its time limit")
+    out = str(tmp_path / (config + ".trace"))
+    rc, err = launch_trace.run_child(config, out)
+    if rc is None or rc < 0 or rc in (124, 134, 137, 139):
+        _stopped.append(config)
+        pytest.fail(f"trace child of {config} ended by a signal or its time limit (rc {rc}):\n{err}")
+    assert rc == 0, err
+    got = launch_trace.summary(open(out).read())
+    want = GOLDEN[config]
+    hint = (f"full trace: {out}; the recorded tree's, for a diff: python tools/launch_trace.py {config} "
+            "(on a checkout of the commit that recorded tests/golden/launch_trace.json)")
+    assert got["lines"] == want["lines"], hint
+    assert got["launches"] == want["launches"], hint
+    assert got["sha256"] == want["sha256"], hint
