@@ -50,7 +50,14 @@ int kodhip_conv_fwd_raw(const void* x, const void* w_packed, void* y, float* sta
                         int B, int H, int W, int ldx, int xcoff, int Cin,
                         int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
                         int ldy, int ycoff, kodStream_t stream);
-/* three biased 1x1 head convs of one level fused (kod/nn/heads/yolov5.py:12-136), out [B][A][H*W][5+nc] fp32 */
+/* three biased 1x1 head convs of one level fused (kod/nn/heads/yolov5.py:12-136), out [B][A][H*W][5+nc] fp32.
+ * Class-count limit.  This entry point, kodhip_yolo_loss and kodhip_yolo_loss_iou take 5 + nc <= 128 (nc <= 123, the
+ * range of their element -> (cell, slot) division) and refuse more with an error status ("at most 123 classes").  The
+ * backward pass of the heads, kodhip_head_bwd_prep, additionally needs A * (5 + nc) padded to 8 to be <= 256 (one row
+ * of its LDS tile).  The limit of a network that is to be TRAINED is therefore the smaller one:
+ *     nc <= min(256 / A, 128) - 5, i.e. 80 classes with the 3 anchors per cell of every shipped configuration
+ * (3 * 85 = 255 -> 256 sits exactly on it).  The Python engine refuses a larger class count when it is built
+ * (engine/graph.py check_head_limits), before any launch. */
 int kodhip_conv_fwd_head(const void* x, const void* w_packed, const float* bias, float* out,
                          int B, int H, int W, int ldx, int xcoff, int Cin, int A, int nc, int Kp,
                          kodStream_t stream);
@@ -240,7 +247,8 @@ int kodhip_upsample2x_fwd(const void* x, int ldx, int xcoff, void* y, int ldy, i
                           int B, int H, int W, int C, kodStream_t stream);
 int kodhip_upsample2x_bwd(const void* dy, int ldy, int ycoff, void* dx, int ldx, int xcoff, int accumulate,
                           int B, int H, int W, int C, const float* dx_f32, kodStream_t stream);
-/* workspace: 2048 * Npad floats (per-block bias partials) */
+/* workspace: 2048 * Npad floats (per-block bias partials).  Npad = A * (5 + nc) padded to 8, at most 256 (see the
+ * class-count limit at kodhip_conv_fwd_head); anything else is refused with "head_bwd_prep: bad Npad" */
 int kodhip_head_bwd_prep(const float* g, void* dy, float* workspace, float* db_box, float* db_obj, float* db_cls,
                          int B, int HW, int A, int nc, int Npad, kodStream_t stream);
 

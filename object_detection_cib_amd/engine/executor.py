@@ -18,7 +18,7 @@ from typing import Dict, Optional
 import torch
 
 from .. import _lib
-from .graph import Graph
+from .graph import Graph, check_head_limits
 from .options import EngineOptions
 from .arenas import ArenaMixin, _UnitState, _pad          # noqa: F401
 from .buffers import BufferMixin
@@ -36,6 +36,8 @@ class Engine(ArenaMixin, BufferMixin, ForwardMixin, BackwardMixin):
 
     def __init__(self, graph: Graph, params: Dict[str, torch.nn.Parameter], buffers: Dict[str, torch.Tensor],
                  options: Optional[EngineOptions] = None):
+        if graph.heads:               # the class-count limit of the head / loss kernels: before anything is allocated or launched
+            check_head_limits(graph.num_anchors, graph.num_classes)
         _lib.require_gpu()
         self.lib = _lib.lib()
         self.opt = options or EngineOptions.from_env()      # every switch, read once (engine/options.py)

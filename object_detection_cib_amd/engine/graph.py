@@ -226,6 +226,28 @@ def _neck(b: _Builder, g: Graph, pre: str, cs, P5: View, td0cat: Buf, td1cat: Bu
     return T3, O4, O5
 
 
+MAX_HEAD_CHANNELS = 256       # the head gradient re-layout's LDS tile (csrc/misc_ops.hip head_bwd_prep), see include/kodhip.h
+MAX_SLOTS_PER_ANCHOR = 128    # 5 + nc: the element -> (cell, slot) division of the loss / head kernels
+
+
+def max_trainable_classes(num_anchors_per_cell: int) -> int:
+    """Largest class count the head and loss kernels take in all of forward, loss and backward (80 with 3 anchors)."""
+    return min(MAX_HEAD_CHANNELS // num_anchors_per_cell, MAX_SLOTS_PER_ANCHOR) - 5
+
+
+def check_head_limits(num_anchors_per_cell: int, num_classes: int) -> None:
+    """The one class-count limit of a network with detection heads, checked where an engine is built - before any launch,
+    not in the middle of the first backward pass."""
+    A, nc = int(num_anchors_per_cell), int(num_classes)
+    if A < 1 or nc < 1:
+        raise ValueError(f"detection heads need at least one anchor per cell and one class (got {A} anchors, {nc} classes)")
+    if nc > max_trainable_classes(A):
+        raise ValueError(
+            f"num_classes = {nc} with {A} anchors per cell makes {A * (5 + nc)} head channels: the head kernels take at most "
+            f"{MAX_HEAD_CHANNELS} channels (padded to 8) and {MAX_SLOTS_PER_ANCHOR} per anchor, i.e. at most "
+            f"{max(max_trainable_classes(A), 0)} classes with {A} anchors (include/kodhip.h, 'class-count limit')")
+
+
 def build_graph(num_anchors_per_cell: int, num_classes: int, widen_factor: float = 1.0,
                 deepen_factor: float = 1.0) -> Graph:
     g = Graph(num_anchors_per_cell, num_classes)

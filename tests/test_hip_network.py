@@ -103,6 +103,33 @@ def test_train_step_vs_oracle(case):
     assert all(int(sd_h[k]) == int(sd_r[k]) == 1 for k in sd_r if k.endswith("num_batches_tracked"))
 
 
+def test_class_count_limit_80_trains_81_is_refused_at_construction():
+    """The shipped 80-class head (3 * 85 = 255 -> 256 channels) sits exactly on the limit of the head kernels: a whole
+    train step runs and agrees with the fp32 oracle.  81 classes would pass the forward pass and the loss and fail in
+    the backward pass (kodhip_head_bwd_prep: "bad Npad"); the engine refuses them when it is built instead."""
+    widen, deepen, nc, B, size, seed = 0.25, 0.33, 80, 2, 160, 2023
+    torch.manual_seed(seed)
+    ref = OracleYolov5(3, nc, widen, deepen).train()
+    torch.manual_seed(seed)
+    net = Yolov5Network(3, nc, widen_factor=widen, deepen_factor=deepen).cuda().train()
+    x, tg = synth.batch(B, size, nc, seed)
+    lr_r = D.yolo_loss(size, size, ref(x), [D.Target(b, l) for b, l in tg])
+    tot_r = D.train_step_total(lr_r, B)
+    tot_r.backward()
+    _, lr_h, tot_h = _step(net, x.cuda(), tg, size, B)
+    assert np.isfinite(tot_r.item())
+    np.testing.assert_allclose(tot_h.item(), tot_r.item(), rtol=2e-2)
+    gn_r = torch.sqrt(sum((p.grad.double() ** 2).sum() for p in ref.parameters())).item()
+    gn_h = torch.sqrt(sum((p.grad.double() ** 2).sum() for p in net.parameters())).item()
+    assert abs(gn_h - gn_r) <= 0.15 * gn_r, (gn_h, gn_r)
+    # the class heads' bias gradients come out of head_bwd_prep's column sums at Npad = 256
+    for k, p in net.named_parameters():
+        assert p.grad is not None and bool(torch.isfinite(p.grad).all()), k
+    bad = Yolov5Network(3, 81, widen_factor=widen, deepen_factor=deepen)
+    with pytest.raises(ValueError, match="at most 80 classes with 3 anchors"):
+        bad.cuda().train()(x.cuda())
+
+
 @pytest.mark.parametrize("act", ["leaky", "hardswish"])
 def test_train_step_with_another_activation(act):
     """Yolov5Network(activation_layer=...) other than the reference's SiLUInplace (kod/nn/networks/yolov5.py:40-50 takes any

@@ -284,51 +284,134 @@ def test_conv_wgrad_dual(case):
         _close(gw[i].cpu(), g1.cpu(), 1e-4, 2e-5 * want.abs().max().item(), f"dual wgrad layer {i} vs single launch")
 
 
-def test_head_conv_fwd_bwd():
-    g = torch.Generator().manual_seed(3)
-    B, C, H, W, A, nc = 2, 128, 8, 8, 3, 10
+# B, H, W, C, nc, backward too?  A = 3 throughout.  Class counts 25 / 26 straddle Npad = 128, where head_bwd_prep switches from
+# 64-row to 32-row tiles; 80 is the limit of a trainable network (Npad = 256); 91 / 123 run the forward pass only (the
+# loss kernels' limit).  (3, 5, 7): M = 105, one 64-row tile spans three images; (16, 80, 80): more than 2048 * 32 rows, so
+# that head_bwd_prep's grid cap (2048 persistent blocks) is reached.
+HEAD_CASES = [
+    (2, 8, 8, 128, 10, True),                 # M = 128: two full half tiles, one column tile
+    (3, 5, 7, 64, 1, True), (3, 5, 7, 128, 25, True), (3, 5, 7, 256, 26, True), (3, 5, 7, 64, 80, True),
+    (1, 20, 20, 128, 3, True), (1, 20, 20, 256, 20, True), (1, 20, 20, 64, 26, True), (1, 20, 20, 128, 80, True),
+    (2, 9, 11, 256, 1, True), (2, 9, 11, 64, 20, True), (2, 9, 11, 128, 25, True), (2, 9, 11, 256, 80, True),
+    (16, 80, 80, 64, 80, True),
+    (3, 5, 7, 128, 91, False), (1, 20, 20, 64, 123, False), (2, 9, 11, 256, 123, False), (1, 20, 20, 256, 91, False),
+]
+
+
+def _head_columns(A, nc):
+    """GEMM column n of (anchor, slot): box (4 A) | obj (A) | cls (nc A), as the three head convs are stacked."""
+    P = 5 + nc
+    n = torch.empty(A, P, dtype=torch.long)
+    for a in range(A):
+        n[a, :4] = 4 * a + torch.arange(4)
+        n[a, 4] = 4 * A + a
+        n[a, 5:] = 5 * A + a * nc + torch.arange(nc)
+    return n
+
+
+@pytest.mark.parametrize("case", HEAD_CASES, ids=lambda c: "B%d_%dx%d_C%d_nc%d%s" % (*c[:5], "" if c[5] else "_fwd"))
+def test_head_conv_fwd_bwd(case):
+    """The fused head convolution and the head gradient re-layout against fp64 on the same bf16 values.
+
+    Forward: fp32 output of bf16 inputs with fp32 accumulation; every product of two bf16 numbers is exact in fp32, so
+    what rounds is the accumulation: C - 1 additions, the bias, the final store -> |err| <= gamma(C + 2) * (sum_c |x_c w_c|
+    + |bias|) (gamma as in tests/bn_reference.py), a bound tensor, not a flat number.
+    head_bwd_prep is a transpose through LDS plus one conversion: dy is EXACTLY the round-to-nearest-even bf16 of the
+    permuted gradient, its padding columns exactly 0, nothing written past the last row; the bias gradients are fp32
+    column sums (<= M terms each) -> gamma(M) * sum |g|."""
+    from bn_reference import gamma_n, ulp32
+    B, H, W, C, nc, bwd = case
+    A, P = 3, 5 + nc
+    g = torch.Generator().manual_seed(3 + nc + C + H)
+    M, N = B * H * W, A * P
     x = bf(torch.randn(B, C, H, W, generator=g))
     ws = [bf(torch.randn(n, C, 1, 1, generator=g) / C ** 0.5) for n in (4 * A, A, nc * A)]
     bs = [torch.randn(n, generator=g) for n in (4 * A, A, nc * A)]
-    xr = x.clone().requires_grad_(True)
-    wr = [w.clone().requires_grad_(True) for w in ws]
-    br = [b.clone().requires_grad_(True) for b in bs]
-    outs = []
-    for w, b, p in zip(wr, br, (4, 1, nc)):
-        y = F.conv2d(xr, w, b)
-        outs.append(y.view(B, A, p, H, W).permute(0, 1, 3, 4, 2))
-    ref = torch.cat(outs, -1)                                   # [B,A,H,W,15]
-    gout = torch.randn(ref.shape, generator=g)
-    ref.backward(gout)
+    X = x.permute(0, 2, 3, 1).reshape(M, C).double()
+    Wm = torch.cat([w.reshape(w.shape[0], C) for w in ws]).double()          # [N, C]
+    bias64 = torch.cat(bs).double()
+    col = _head_columns(A, nc)                                                # [A, P]
+    Y = X @ Wm.t() + bias64
+    Yabs = X.abs() @ Wm.abs().t() + bias64.abs()
+    to_out = lambda t: t.view(B, H * W, N)[:, :, col].permute(0, 2, 1, 3).reshape(B, A, H, W, P)
     lib = _lib.lib()
-    npad = pad(A * (5 + nc), 8)
+    npad = pad(N, 8)
     pk = pack(ws, ntot=npad)
     xb = nhwc(x)
     bias = torch.cat(bs).cuda()
-    out = torch.zeros((B, A, H, W, 5 + nc), dtype=torch.float32, device="cuda")
+    guard = 1024
+    obuf = torch.full((B * A * H * W * P + 2 * guard,), -7.0, dtype=torch.float32, device="cuda")
+    out = obuf[guard:guard + B * A * H * W * P].view(B, A, H, W, P)
     _lib.check(lib.kodhip_conv_fwd_head(xb.data_ptr(), pk["f"].data_ptr(), bias.data_ptr(), out.data_ptr(),
                                         B, H, W, C, 0, C, A, nc, pk["Kp"], stream()), "head")
-    _close(out.cpu(), ref.detach(), 2e-3, 2e-3, "head fwd")
+    torch.cuda.synchronize()
+    assert bool((obuf[:guard] == -7.0).all()) and bool((obuf[-guard:] == -7.0).all()), "head fwd wrote outside its output"
+    err = (out.cpu().double() - to_out(Y)).abs()
+    bound = gamma_n(C + 2) * to_out(Yabs)
+    ratio = (err / bound).max().item()
+    print(f"HEADFWD {case} max err/bound {ratio:.3f} median {(err / bound).median().item():.3f}")
+    assert ratio <= 1.0, f"head fwd: {(err > bound).sum().item()}/{err.numel()} above gamma(C + 2) * sum|xw|, worst ratio {ratio:.3f}"
+    if not bwd:
+        # beyond the limit of a trainable network the gradient re-layout refuses, with a message and without a launch
+        dy = torch.full((8, npad), 3.0, dtype=torch.bfloat16, device="cuda")
+        rc = lib.kodhip_head_bwd_prep(out.data_ptr(), dy.data_ptr(), obuf.data_ptr(), bias.data_ptr(), bias.data_ptr(),
+                                      bias.data_ptr(), B, H * W, A, nc, npad, stream())
+        assert rc != 0 and b"head_bwd_prep: bad Npad" in lib.kodhip_last_error()
+        torch.cuda.synchronize()
+        assert bool((dy == 3.0).all())
+        return
     # backward
-    dy = torch.zeros((B * H * W, npad), dtype=torch.bfloat16, device="cuda")
+    gout = torch.randn(B, A, H, W, P, generator=g)
+    G = torch.zeros(M, N, dtype=torch.float32)
+    G.view(B, H * W, N)[:, :, col] = gout.view(B, A, H * W, P).permute(0, 2, 1, 3)      # dY of the stacked GEMM
+    dybuf = torch.full(((M + 64) * npad,), 3.0, dtype=torch.bfloat16, device="cuda")     # 64 poisoned rows past the end
+    dy = dybuf[:M * npad].view(M, npad)
     ws_ = torch.zeros(2048 * npad, dtype=torch.float32, device="cuda")
     db = [torch.zeros(n, device="cuda") for n in (4 * A, A, nc * A)]
     _lib.check(lib.kodhip_head_bwd_prep(gout.cuda().contiguous().data_ptr(), dy.data_ptr(), ws_.data_ptr(),
                                         db[0].data_ptr(), db[1].data_ptr(), db[2].data_ptr(), B, H * W, A, nc, npad,
                                         stream()), "head prep")
-    for d, r in zip(db, br):
-        _close(d.cpu(), r.grad, 1e-4, 1e-4, "head bias grad")
+    torch.cuda.synchronize()
+    assert bool((dybuf[M * npad:] == 3.0).all()), "head_bwd_prep wrote past the last row"
+    dyc = dy.cpu()
+    assert torch.equal(dyc[:, :N].view(torch.int16), G.to(torch.bfloat16).view(torch.int16)), "dy is not the RNE bf16 of the permuted gradient"
+    assert bool((dyc[:, N:].view(torch.int16) == 0).all()), "padding columns of dy are not zero"
+    dbias = torch.cat([d.cpu() for d in db]).double()
+    want_b, abs_b = G.double().sum(0), G.double().abs().sum(0)
+    berr = (dbias - want_b).abs()
+    bbound = gamma_n(M) * abs_b + ulp32(want_b) / 2
+    print(f"HEADBIAS {case} max err/bound {(berr / bbound).max().item():.4f}")
+    assert bool((berr <= bbound).all()), f"head bias grad: worst err/bound {(berr / bbound).max().item():.3f}"
+    # data and weight gradient of the stacked GEMM from that dy (fp64 of the unrounded gradient; bf16 dy / dX: 2^-9)
     dx = torch.zeros((B, H, W, C), dtype=torch.bfloat16, device="cuda")
     _lib.check(lib.kodhip_conv_dgrad(dy.data_ptr(), pk["d"].data_ptr(), dx.data_ptr(), B, H, W, C, 0, C, npad, 1, 1, 1, 1,
                                      0, 0, pk["Kdp"], npad, 0, 0, None, stream()), "head dgrad")
-    _close(nchw(dx), xr.grad, 2e-2, 3e-2, "head dgrad")
+    _close(dx.float().cpu().reshape(M, C), (G.double() @ Wm).float(), 2e-2, 3e-2, "head dgrad")
     splits = lib.kodhip_conv_wgrad_splits_geo(B, H, W, C, C, npad, 1, 1, 1, 1, 0, 0, pk["Kp"], npad)
     part = torch.zeros(splits * npad * pk["Kp"], dtype=torch.float32, device="cuda")
-    gw = torch.zeros(A * (5 + nc), C, device="cuda")
+    gw = torch.zeros(N, C, device="cuda")
     _lib.check(lib.kodhip_conv_wgrad(xb.data_ptr(), dy.data_ptr(), part.data_ptr(), gw.data_ptr(), B, H, W, C, 0, C, npad,
-                                     1, 1, 1, 1, 0, 0, pk["Kp"], npad, 0, A * (5 + nc), 0, 1.0, stream()), "head wgrad")
-    refw = torch.cat([w.grad.reshape(w.shape[0], C) for w in wr], 0)
+                                     1, 1, 1, 1, 0, 0, pk["Kp"], npad, 0, N, 0, 1.0, stream()), "head wgrad")
+    refw = (G.double().t() @ X).float()
     _close(gw.cpu(), refw, 1e-2, 1e-2 * refw.abs().max().item(), "head wgrad")
+
+
+def test_head_entry_points_refuse_out_of_range_class_counts():
+    """nc / Npad out of range: an error status and a message on every entry point, nothing launched."""
+    lib = _lib.lib()
+    buf = torch.full((4096,), 5.0, device="cuda")
+    p = buf.data_ptr()
+    pk = pack([bf(torch.randn(n, 32, 1, 1)) for n in (12, 3, 30)], ntot=48)
+    xb = torch.zeros((1, 2, 2, 32), dtype=torch.bfloat16, device="cuda")
+    for nc, msg in ((124, b"at most 123 classes"),):
+        rc = lib.kodhip_conv_fwd_head(xb.data_ptr(), pk["f"].data_ptr(), p, p, 1, 2, 2, 32, 0, 32, 3, nc, pk["Kp"], stream())
+        assert rc != 0 and msg in lib.kodhip_last_error(), (nc, lib.kodhip_last_error())
+    for A, nc, npad, msg in ((3, 81, 264, b"bad Npad"), (3, 10, 40, b"bad Npad"), (3, 10, 44, b"bad Npad"), (1, 124, 136, b"bad class count"),
+                             (1, 0, 8, b"bad class count")):
+        rc = lib.kodhip_head_bwd_prep(p, p, p, p, p, p, 1, 4, A, nc, npad, stream())
+        assert rc != 0 and msg in lib.kodhip_last_error(), (A, nc, npad, lib.kodhip_last_error())
+    torch.cuda.synchronize()
+    assert bool((buf == 5.0).all())
 
 
 @pytest.mark.parametrize("C,res,hw", [(32, False, (10, 6)), (64, True, (10, 6)), (48, True, (10, 6)), (256, False, (10, 6)),

@@ -524,3 +524,20 @@ def test_host_protocol_vs_reference_recording(case):
         assert np.array_equal(bb, g["boxes"][ob:ob + cnt]) and np.array_equal(lb, g["labels"][ob:ob + cnt]), (case, k)
         ob += cnt
     assert ob == len(g["boxes"])
+
+
+def test_class_count_limit_is_checked_where_the_engine_is_built():
+    """One limit for a trainable network, min(256 / A, 128) - 5 classes (80 with 3 anchors: 3 * 85 = 255 -> 256 head
+    channels): the engine refuses more by name of the limit before it touches the GPU (this runs without one)."""
+    from object_detection_cib_amd.engine.graph import build_graph, check_head_limits, max_trainable_classes
+    from object_detection_cib_amd.engine.executor import Engine
+    assert max_trainable_classes(3) == 80 and max_trainable_classes(1) == 123 and max_trainable_classes(2) == 123
+    assert max_trainable_classes(4) == 59
+    check_head_limits(3, 80)
+    check_head_limits(3, 1)
+    check_head_limits(1, 123)
+    for A, nc in ((3, 81), (3, 123), (1, 124), (4, 60), (3, 0)):
+        with pytest.raises(ValueError, match="class"):
+            check_head_limits(A, nc)
+    with pytest.raises(ValueError, match="at most 80 classes with 3 anchors"):
+        Engine(build_graph(3, 81, 0.25, 0.33), {}, {})
