@@ -121,16 +121,33 @@ int kodhip_conv_dgrad_dual_bnred_slots(int B, int H, int W, int Cin, int N, int 
 int kodhip_conv_dgrad_dual_bnred(const void* dy1, const void* w1, const void* dy2, const void* w2, void* dx,
                                  int B, int H, int W, int ldx, int xcoff, int Cin, int N, int Kp, int ldy, int ycoff,
                                  int accumulate, void* dx_f32, const void* segments, int nseg, int slots, kodStream_t stream);
+/* Read-only launch plan of a convolution (nothing is launched, no pointer is read): which tile shape and kernel form a
+ * geometry reaches.  The geometry is given as the entry point named by `op` takes it: 0 kodhip_conv_fwd_raw, 1 kodhip_conv_dgrad,
+ * 2 kodhip_conv_dgrad_s2, 3 kodhip_conv_dgrad_s2f, 4 kodhip_conv_dgrad_dual (ops 2..4 ignore KH .. PW; ops 2, 3 ignore Kp).
+ * out (host, 8 ints) = {bm, bn (pixels x channels of a block's tile), row3 (1: the 3x3 / stride-1 row form), fast (1: LDS-DMA
+ * path), tiles_m, tiles_n, groups_m (persistent blocks per channel tile: a block loops over tiles_m / groups_m pixel tiles),
+ * bm of the merged four-class launch of op 2, 0 when the launch is not merged}. */
+int kodhip_conv_plan_query(int op, int B, int H, int W, int ldx, int xcoff, int Cin,
+                           int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
+                           int ldy, int ycoff, int* out);
 int kodhip_conv_wgrad_splits(long M, int N, int Kp);     /* generic split-K kernel */
 /* split count of the kernel kodhip_conv_wgrad picks for this geometry (3x3 / stride 1 / pad 1 layers with whole
  * 32-channel chunks take a form that stages dY once per block and every input row once per kernel row): size the slab
  * region with this one.  H, W: input dims; ldx / ldy: row strides of x / dy in elements. */
 int kodhip_conv_wgrad_splits_geo(int B, int H, int W, int ldx, int Cin, int N, int KH, int KW, int SH, int SW, int PH, int PW,
                                  int Kp, int ldy);
+/* grad: fp32 [n_valid][Cin][KH][KW] = scale * dW of the first n_valid output channels (the state_dict layout; stem = 1:
+ * [n_valid][3][6][6] from the pixel-pair K axis).  n_valid < N (dy padded with columns that are no weights, e.g. the heads'
+ * Npad): exactly n_valid * Cin * KH * KW floats are written, nothing behind them; the partial slabs always hold all N rows. */
 int kodhip_conv_wgrad(const void* x, const void* dy, float* partials, float* grad,
                       int B, int H, int W, int ldx, int xcoff, int Cin,
                       int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
                       int ldy, int ycoff, int n_valid, int stem, float scale, kodStream_t stream);
+/* Read-only launch plan of kodhip_conv_wgrad (dual = 0) / kodhip_conv_wgrad_dual (dual = 1; KH .. PW ignored).
+ * out (host, 8 ints) = {tn, tk (output rows x K columns of a block's tile; ROW3 form: 32 wn rn rows x 32 wc channels of all nine
+ * taps), row3, wn, rn, wc (the ROW3 form's wave layout, 0 otherwise), splits, dma (1: LDS-DMA kernel, 0: register-staged)}. */
+int kodhip_conv_wgrad_plan_query(int B, int H, int W, int ldx, int Cin, int N, int KH, int KW, int SH, int SW, int PH, int PW,
+                                 int Kp, int ldy, int dual, int* out);
 /* Weight gradients of TWO pointwise layers with the same input (a CSP layer's main_conv and short_conv,
  * kod/nn/layers/csp.py:85-99) in one launch + one reduction: the shared input is streamed from HBM once.  dy1 / dy2:
  * [B*H*W][ldy] (+ycoff, N channels each); partials: kodhip_conv_wgrad_dual_splits(...) * 2N * Kp floats; grad1 / grad2: fp32

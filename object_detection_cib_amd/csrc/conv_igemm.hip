@@ -1329,16 +1329,21 @@ int launch(const ConvArgs& a, hipStream_t stream) {
   return KOD_OK;
 }
 
-// one launch for four FAST problems that share M, N and the tile plan (chosen for the longest reduction)
+// the tile plan four FAST problems of one merged launch share: chosen for the longest reduction
+Plan plan_x4(const ConvArgs c[4]) {
+  int kmax = 0;
+  for (int i = 0; i < 4; ++i) kmax = c[i].K > kmax ? c[i].K : kmax;
+  return make_plan(c[0].M, c[0].N, kmax, true);
+}
+
+// one launch for four FAST problems that share M, N and the tile plan
 template <int MODE, bool F32ACC = false>
 int launch_x4(ConvArgs c[4], hipStream_t stream) {
   if constexpr (!F32ACC) {
     if (c[0].f32_mode != 0) return launch_x4<MODE, true>(c, stream);
   }
   ConvArgs4 p;
-  int kmax = 0;
-  for (int i = 0; i < 4; ++i) kmax = c[i].K > kmax ? c[i].K : kmax;
-  const Plan pl = make_plan(c[0].M, c[0].N, kmax, true);
+  const Plan pl = plan_x4(c);
   for (int i = 0; i < 4; ++i) {
     p.c[i] = c[i];
     p.c[i].x_bytes = (uint32_t)((long)c[i].B * c[i].Hs * c[i].Ws * c[i].ldx * 2);
@@ -1403,11 +1408,11 @@ static int fill_common(ConvArgs& a, const void* x, const void* w, int B, int Hs,
 }
 
 // Forward conv of a conv+BN+SiLU unit: y_raw[M][ldy] (bf16) + BatchNorm partials stats[2][N][slots].
-int kodhip_conv_fwd_raw(const void* x, const void* w_packed, void* y, float* stats,
+static int prep_fwd_raw(ConvArgs& a, const void* x, const void* w_packed, void* y, float* stats,
                         int B, int H, int W, int ldx, int xcoff, int Cin,
                         int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
-                        int ldy, int ycoff, hipStream_t stream) {
-  ConvArgs a = {};
+                        int ldy, int ycoff) {
+  a = ConvArgs{};
   // wide-pixel form (the stem: Cin = 32 = four 8-channel pixel pairs per tap, KW = 1): the window's last pixel is
   // K-alignment padding with zero weights, so the true kernel width for the output size is Cin/ldx - 1
   const int kw_out = (Cin > ldx && KW == 1) ? Cin / ldx - 1 : KW;
@@ -1419,6 +1424,15 @@ int kodhip_conv_fwd_raw(const void* x, const void* w_packed, void* y, float* sta
   a.y = (bf16_t*)y; a.stats = stats; a.ldy = ldy; a.ycoff = ycoff;
   a.stats_slots = kodhip_conv_stats_slots(a.M, N);
   a.mul_h = SH; a.mul_w = SW; a.add_h = -PH; a.add_w = -PW; a.tap_sign = 1; a.sh_shift = 0; a.sw_shift = 0;
+  return KOD_OK;
+}
+
+int kodhip_conv_fwd_raw(const void* x, const void* w_packed, void* y, float* stats,
+                        int B, int H, int W, int ldx, int xcoff, int Cin,
+                        int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
+                        int ldy, int ycoff, hipStream_t stream) {
+  ConvArgs a;
+  if (int rc = prep_fwd_raw(a, x, w_packed, y, stats, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff)) return rc;
   return launch<MODE_RAW>(a, stream);
 }
 
@@ -1620,9 +1634,7 @@ int kodhip_conv_dgrad_bnred_slots(int B, int H, int W, int Cin, int N, int KH, i
     ConvArgs cls[4];
     bool all_fast;
     if (prep_dgrad_s2(cls, all_fast, fake, fake, (void*)fake, B, H, W, Cin, 0, Cin, N, ldy, 0, 0) || !all_fast) return 0;
-    int kmax = 0;
-    for (int i = 0; i < 4; ++i) kmax = cls[i].K > kmax ? cls[i].K : kmax;
-    return 4 * make_plan(cls[0].M, cls[0].N, kmax, true).groups_m;
+    return 4 * plan_x4(cls).groups_m;
   }
   ConvArgs a;
   const int Kp = KH * KW * ((N + 31) / 32 * 32);
@@ -1695,6 +1707,47 @@ int kodhip_conv_dgrad_s2_bnred(const void* dy, const void* w_dgrad_s2, void* dx,
   for (int c = 0; c < 4; ++c)
     if (int rc = set_segments(cls[c], (const BnRedSeg*)segments, nseg, slots, Cin)) return rc;
   return launch_x4<MODE_PLAIN_BN>(cls, stream);
+}
+
+// Read-only view of the launch plan (tests assert which kernel a case reaches; nothing is launched, no pointer is read).
+// The geometry is taken as the entry point named by `op` takes it: 0 kodhip_conv_fwd_raw, 1 kodhip_conv_dgrad,
+// 2 kodhip_conv_dgrad_s2, 3 kodhip_conv_dgrad_s2f, 4 kodhip_conv_dgrad_dual (ops 2..4 ignore KH .. PW; op 2 and 3 ignore Kp).
+// out = {bm, bn, row3, fast, tiles_m, tiles_n, groups_m, bm of the merged four-class launch or 0 when the launch is not
+// merged}; op 2 without the merged launch (KODHIP_S2_SEPARATE, a class off the FAST path) reports the four-tap class.
+int kodhip_conv_plan_query(int op, int B, int H, int W, int ldx, int xcoff, int Cin,
+                           int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
+                           int ldy, int ycoff, int* out) {
+  KOD_CHECK_ARG(out, "conv_plan_query: null output");
+  void* fake = (void*)64;                   // never dereferenced
+  ConvArgs a;
+  Plan p;
+  bool fast = true, row3 = false;
+  int merged = 0;
+  if (op == 2) {
+    ConvArgs cls[4];
+    bool all_fast;
+    if (int rc = prep_dgrad_s2(cls, all_fast, fake, fake, fake, B, H, W, ldx, xcoff, Cin, N, ldy, ycoff, 0)) return rc;
+    if (all_fast) {
+      p = plan_x4(cls);
+      merged = p.bm;
+    } else {
+      fast = fast_eligible(cls[3]);
+      p = plan_conv(cls[3], fast, row3);
+    }
+  } else {
+    int rc = KOD_OK;
+    KOD_CHECK_ARG(op >= 0 && op <= 4, "conv_plan_query: bad op %d", op);
+    if (op == 0) rc = prep_fwd_raw(a, fake, fake, fake, (float*)fake, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff);
+    else if (op == 1) rc = prep_dgrad(a, fake, fake, fake, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff, 0);
+    else if (op == 3) rc = prep_dgrad_s2f(a, fake, fake, fake, B, H, W, ldx, xcoff, Cin, N, ldy, ycoff, 0);
+    else rc = prep_dgrad_dual(a, fake, fake, fake, fake, fake, B, H, W, ldx, xcoff, Cin, N, Kp, ldy, ycoff, 0);
+    if (rc) return rc;
+    fast = fast_eligible(a);
+    p = plan_conv(a, fast, row3);
+  }
+  out[0] = p.bm; out[1] = p.bn; out[2] = row3 ? 1 : 0; out[3] = fast ? 1 : 0;
+  out[4] = p.tiles_m; out[5] = p.tiles_n; out[6] = p.groups_m; out[7] = merged;
+  return KOD_OK;
 }
 
 }  // extern "C"

@@ -869,6 +869,15 @@ static int launch_wgrad_reduce(const float* part, float* grad, int splits, int N
 constexpr int WGRAD_STAGES = WG_NST;     // LDS ring depth
 constexpr int WGRAD_ROWS = WG_RS;        // reduction rows per ring stage
 
+// operands within the 32-bit range of a raw buffer (the LDS-DMA kernels, ROW3 and dual forms need it)
+bool wgrad_in_range(long x_bytes, long dy_bytes) { return x_bytes < (1l << 32) - 64 && dy_bytes < (1l << 32) - 64; }
+
+// LDS-DMA ring (default) or the register-staged kernel (KODHIP_WGRAD_DMA=none, or an operand beyond the buffer range)
+bool wgrad_uses_dma(long x_bytes, long dy_bytes) {
+  static const char* mode = getenv("KODHIP_WGRAD_DMA");
+  return !(mode && mode[0] == 'n') && wgrad_in_range(x_bytes, dy_bytes);
+}
+
 template <int WN, int WK, int RN, int RK>
 int launch_cfg(WgradArgs a, hipStream_t stream) {
   constexpr int TNB = WN * RN * 32, TKB = WK * RK * 32;
@@ -881,8 +890,7 @@ int launch_cfg(WgradArgs a, hipStream_t stream) {
   // selects the register-staged kernel for A/B runs; an operand that does not fit a 32-bit buffer range always
   // takes it.
   const long xb = (long)a.B * a.Hs * a.Ws * a.ldx * 2, yb = (long)a.M * a.ldy * 2;
-  static const char* mode = getenv("KODHIP_WGRAD_DMA");
-  if (!(mode && mode[0] == 'n') && xb < (1l << 32) - 64 && yb < (1l << 32) - 64) {
+  if (wgrad_uses_dma(xb, yb)) {
     const bool pw = a.KH == 1 && a.KW == 1 && a.SH == 1 && a.SW == 1 && a.PH == 0 && a.PW == 0;
     const dim3 g(grid), b(64 * WN * WK);
     if (pw) hipLaunchKernelGGL((conv_wgrad_dma_kernel<WN, WK, RN, RK, WGRAD_STAGES, WGRAD_ROWS, 1>), g, b, 0, stream, a, (uint32_t)xb, (uint32_t)yb);
@@ -1133,6 +1141,13 @@ int launch_row3(WgradArgs a, hipStream_t stream) {
   return KOD_OK;
 }
 
+// the ROW3 form as launched: eligible by shape and knob, operands within the buffer range
+Row3Cfg row3_form(int N, int Cin, int KH, int KW, int SH, int SW, int PH, int PW, long x_bytes, long dy_bytes) {
+  Row3Cfg c = row3_cfg(N, Cin, KH, KW, SH, SW, PH, PW);
+  if (!wgrad_in_range(x_bytes, dy_bytes)) c.on = false;
+  return c;
+}
+
 void tile_shape(int N, int Kp, int* tn, int* tk) {
   *tn = N > 64 ? 128 : (N > 32 ? 64 : 32);
   // yv5m widths: N = 192 as three 64-row tiles (all used) instead of two 128-row tiles (a quarter idle)
@@ -1169,8 +1184,8 @@ static int wgrad_rows_per_split(long M, int N, int Kp) {
 // rows per split for a given geometry: the ROW3 form has its own block count (tiles = n tiles x channel chunks)
 static int wgrad_rows_per_split_geo(long M, int N, int Cin, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
                                     long x_bytes, long dy_bytes) {
-  const Row3Cfg c = row3_cfg(N, Cin, KH, KW, SH, SW, PH, PW);
-  if (!c.on || x_bytes >= (1l << 32) - 64 || dy_bytes >= (1l << 32) - 64) return wgrad_rows_per_split(M, N, Kp);
+  const Row3Cfg c = row3_form(N, Cin, KH, KW, SH, SW, PH, PW, x_bytes, dy_bytes);
+  if (!c.on) return wgrad_rows_per_split(M, N, Kp);
   const int tiles = cdiv(N, c.tnb) * cdiv(Cin, c.wc * 32);
   static int wave_slots = 0;                            // KODHIP_WGRAD_ROW3_SLOTS: resident-wave target (A/B knob; default 3072)
   if (!wave_slots) { const char* e = getenv("KODHIP_WGRAD_ROW3_SLOTS"); wave_slots = e ? atoi(e) : 3072; if (wave_slots < 96) wave_slots = 3072; }
@@ -1216,8 +1231,8 @@ static int wgrad_partial(WgradArgs& a, const void* x, const void* dy, float* par
   const long xb = (long)B * H * W * ldx * 2, yb = M * ldy * 2;
   a.m_per_split = wgrad_rows_per_split_geo(M, N, Cin, KH, KW, SH, SW, PH, PW, Kp, xb, yb);
   a.splits = cdiv(M, a.m_per_split);
-  const Row3Cfg r3 = row3_cfg(N, Cin, KH, KW, SH, SW, PH, PW);
-  if (r3.on && xb < (1l << 32) - 64 && yb < (1l << 32) - 64) {
+  const Row3Cfg r3 = row3_form(N, Cin, KH, KW, SH, SW, PH, PW, xb, yb);
+  if (r3.on) {
     a.tiles_n = cdiv(N, r3.tnb);
     a.tiles_k = cdiv(Cin, r3.wc * 32);
     if (r3.wn == 1 && r3.rn == 1 && r3.wc == 1) return launch_row3<1, 1, 1>(a, stream);
@@ -1262,9 +1277,8 @@ int kodhip_conv_wgrad(const void* x, const void* dy, float* partials, float* gra
 // kodhip_conv_wgrad_dual_splits: slab count (partials: splits * 2N * Kp floats), 0 when the form does not apply (operands
 // beyond the 32-bit buffer range, KODHIP_WGRAD_DMA=none) - the caller then launches kodhip_conv_wgrad twice.
 static bool wgrad_dual_ok(long M, int B, int H, int W, int ldx, int ldy) {
-  static const char* mode = getenv("KODHIP_WGRAD_DMA");
   const long xb = (long)B * H * W * ldx * 2, yb = M * ldy * 2;
-  return !(mode && mode[0] == 'n') && xb < (1l << 32) - 64 && yb < (1l << 32) - 64;
+  return wgrad_uses_dma(xb, yb);
 }
 
 static int wgrad_rows_per_split_dual(long M, int N, int Kp) {
@@ -1286,6 +1300,31 @@ int kodhip_conv_wgrad_dual_splits(int B, int H, int W, int ldx, int Cin, int N, 
   const long M = (long)B * H * W;
   if (!wgrad_dual_ok(M, B, H, W, ldx, ldy)) return 0;
   return (int)cdiv(M, (long)wgrad_rows_per_split_dual(M, N, Kp));
+}
+
+// Read-only view of the launch plan of kodhip_conv_wgrad (dual = 0) / kodhip_conv_wgrad_dual (dual = 1: KH .. PW ignored) for
+// a geometry, for tests that assert which kernel a case reaches; nothing is launched.
+// out = {tn, tk, row3, wn, rn, wc, splits, dma}: output rows x K columns of a block's tile (ROW3 form: tn = 32 wn rn rows, tk =
+// 32 wc channels of all nine taps), the ROW3 template parameters (0 otherwise), the slab count, 1 = LDS-DMA kernel /
+// 0 = register-staged kernel (generic form only; the ROW3 form always stages by DMA).
+int kodhip_conv_wgrad_plan_query(int B, int H, int W, int ldx, int Cin, int N, int KH, int KW, int SH, int SW, int PH, int PW,
+                                 int Kp, int ldy, int dual, int* out) {
+  KOD_CHECK_ARG(out, "conv_wgrad_plan_query: null output");
+  KOD_CHECK_ARG(B > 0 && H > 0 && W > 0 && N > 0 && Cin > 0 && Kp > 0, "conv_wgrad_plan_query: bad dims");
+  if (dual) { KH = KW = SH = SW = 1; PH = PW = 0; }
+  const int Ho = (H + 2 * PH - KH) / SH + 1, Wo = (W + 2 * PW - KW) / SW + 1;
+  const long M = (long)B * Ho * Wo;
+  const long xb = (long)B * H * W * ldx * 2, yb = M * ldy * 2;
+  const Row3Cfg r3 = dual ? Row3Cfg{false, 0, 0, 0, 0} : row3_form(N, Cin, KH, KW, SH, SW, PH, PW, xb, yb);
+  int tn, tk;
+  tile_shape(N, Kp, &tn, &tk);
+  const bool row3 = r3.on;
+  out[0] = row3 ? r3.tnb : tn; out[1] = row3 ? r3.wc * 32 : tk; out[2] = row3 ? 1 : 0;
+  out[3] = row3 ? r3.wn : 0; out[4] = row3 ? r3.rn : 0; out[5] = row3 ? r3.wc : 0;
+  out[6] = dual ? (wgrad_dual_ok(M, B, H, W, ldx, ldy) ? (int)cdiv(M, (long)wgrad_rows_per_split_dual(M, N, Kp)) : 0)
+                : (int)cdiv(M, (long)wgrad_rows_per_split_geo(M, N, Cin, KH, KW, SH, SW, PH, PW, Kp, xb, yb));
+  out[7] = (row3 || wgrad_uses_dma(xb, yb)) ? 1 : 0;
+  return KOD_OK;
 }
 
 int kodhip_conv_wgrad_dual(const void* x, const void* dy1, const void* dy2, float* partials, float* grad1, float* grad2,
