@@ -50,6 +50,20 @@ int kodhip_conv_fwd_raw(const void* x, const void* w_packed, void* y, float* sta
                         int B, int H, int W, int ldx, int xcoff, int Cin,
                         int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
                         int ldy, int ycoff, kodStream_t stream);
+/* Eval-mode conv+BN+act unit as ONE launch: out = act(conv(x, w) * scale + shift) (+ residual), scale = gamma *
+ * rsqrt(running_var + eps), shift = beta - running_mean * scale given by the caller ([N] floats each, 16-byte aligned).
+ * The constants meet the fp32 accumulator (z = fma(S, scale, shift)), act(z) is rounded to bf16 once; with a residual
+ * ([B*Ho*Wo][ldr] bf16, channels rcoff .. rcoff + N) the sum of that bf16 value and the residual is rounded again - the
+ * same two roundings as kodhip_bn_act_apply.  No pre-BN tensor is written and no statistics are summed.  Geometry, tiles
+ * and launch plan are those of kodhip_conv_fwd_raw (kodhip_conv_plan_query op 0).  act / slope as kodhip_bn_act_apply
+ * (0 SiLU, 1 ReLU, 2 LeakyReLU(slope), 3 Hardswish, 4 Identity).  `out` ([B*Ho*Wo][ldo], channels ocoff .. ocoff + N)
+ * must not overlap `x` or `residual`: a tile is stored while other tiles still read their inputs.  Errors name
+ * conv_fwd_fused. */
+int kodhip_conv_fwd_fused(const void* x, const void* w_packed, const float* scale, const float* shift,
+                          const void* residual /* or NULL */, int ldr, int rcoff, void* out,
+                          int B, int H, int W, int ldx, int xcoff, int Cin,
+                          int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
+                          int ldo, int ocoff, int act, float slope, kodStream_t stream);
 /* three biased 1x1 head convs of one level fused (kod/nn/heads/yolov5.py:12-136), out [B][A][H*W][5+nc] fp32.
  * Class-count limit.  This entry point, kodhip_yolo_loss and kodhip_yolo_loss_iou take 5 + nc <= 128 (nc <= 123, the
  * range of their element -> (cell, slot) division) and refuse more with an error status ("at most 123 classes").  The

@@ -428,13 +428,7 @@ __global__ __launch_bounds__(256) void bn_silu_bwd_reduce_kernel(const bf16_t* d
 // ReLU, LeakyReLU(slope), Hardswish, Identity (activation_layer=None) - with torch's conventions at the kinks
 // (aten/native/cpu/Activation.cpp: relu' (0) = 0, leaky_relu' uses x > 0, hardswish' = 0 up to -3, x / 3 + 0.5 inside (-3, 3), 1 from 3 on);
 // a network built with one of them runs its BatchNorm-backward reduction as its own pass (no fused epilogues).
-enum { ACT_SILU = 0, ACT_RELU = 1, ACT_LEAKY = 2, ACT_HARDSWISH = 3, ACT_IDENTITY = 4 };
-template <int ACT> __device__ __forceinline__ float kod_act(float z, float slope) {
-  if (ACT == ACT_RELU) return z > 0.f ? z : 0.f;
-  if (ACT == ACT_LEAKY) return z > 0.f ? z : z * slope;
-  if (ACT == ACT_HARDSWISH) return z * fminf(fmaxf(z + 3.f, 0.f), 6.f) / 6.f;
-  return z;
-}
+// (the ACT_* enum and kod_act<> live in kodhip_common.h: the forward convolution's fused epilogue uses them too)
 template <int ACT> __device__ __forceinline__ float kod_act_bwd(float g, float z, float slope) {
   if (ACT == ACT_RELU) return z > 0.f ? g : 0.f;
   if (ACT == ACT_LEAKY) return z > 0.f ? g : g * slope;

@@ -24,10 +24,20 @@
 // land on the same XCD (same L2).
 #include "kodhip_common.h"
 #include <stdlib.h>
+#include <type_traits>
+
+extern "C" const char* kodhip_last_error(void);
 
 namespace {
 
-enum { MODE_RAW = 0, MODE_PLAIN = 1, MODE_HEAD = 2, MODE_PLAIN_BN = 3 };
+enum { MODE_RAW = 0, MODE_PLAIN = 1, MODE_HEAD = 2, MODE_PLAIN_BN = 3, MODE_FUSED = 4, MODE_FUSED_ACT = 5 };
+
+// MODE_FUSED / MODE_FUSED_ACT: the forward conv of an EVAL-mode conv+BN+act unit.  scale / shift exist before the launch
+// (scale = gamma * rsqrt(running_var + eps), shift = beta - running_mean * scale), so the epilogue applies them and the
+// activation to the fp32 accumulators and the tile leaves as the unit's OUTPUT: no pre-BN tensor, no statistics, no apply
+// pass.  MODE_FUSED is SiLU (every shipped config); MODE_FUSED_ACT carries the other activations behind one block-uniform
+// switch on ConvArgs::act.  Same tiles and plans as MODE_RAW.
+constexpr bool mode_is_fused(int mode) { return mode == MODE_FUSED || mode == MODE_FUSED_ACT; }
 
 // MODE_PLAIN_BN: a data-gradient launch that is the LAST writer of some conv units' output gradients also produces
 // their BatchNorm-backward reduction (sum dz, sum dz*y per channel) in its epilogue - the tile it has just written
@@ -85,7 +95,30 @@ struct ConvArgs {
   const bf16_t* seg_raw[MAX_SEG];      // the unit's pre-BN output y [M_out][ldr]
   const float* seg_aff[MAX_SEG];       // scale[C] | shift[C]
   float* seg_part[MAX_SEG];            // [2][C][stats_slots]: sum dz | sum dz*y
+  // MODE_FUSED / MODE_FUSED_ACT (appended: the other modes' argument offsets stay where they were)
+  const float* scale;                  // [N], 16-byte aligned
+  const float* shift;                  // [N]
+  const bf16_t* residual;              // [M][ldr] (+ rcoff) or null
+  int ldr, rcoff;
+  int act;                             // ACT_* (kodhip_common.h); MODE_FUSED_ACT only
+  float slope;
 };
+
+// act(z) of the fused forward epilogue: SiLU as kodhip_bn_silu_apply forms it, the others as kod_act<> does
+template <int ACT> __device__ __forceinline__ float fused_act(float z, float slope) {
+  if constexpr (ACT == ACT_SILU) return z * kod_sigmoid_l2(KOD_NEG_LOG2E * z);
+  else return kod_act<ACT>(z, slope);
+}
+
+// One accumulator quad (4 consecutive channels of one pixel) through BatchNorm + activation: z = fma(S, scale, shift) on the
+// fp32 accumulator, ONE rounding to bf16
+template <int ACT>
+__device__ __forceinline__ bf16x4 fused_quad(const f32x16& acc, int g, const f32x4& sc, const f32x4& sh, float slope) {
+  bf16x4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = (bf16_t)fused_act<ACT>(__builtin_fmaf(acc[g * 4 + e], sc[e], sh[e]), slope);
+  return v;
+}
 
 // q = n / d, r = n % d via a float reciprocal + fix-up (exact: the loops absorb the fp32 rounding of large n)
 // instead of a 40-instruction integer divide
@@ -132,7 +165,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bid
   constexpr int B_PER_THREAD = (B_CHUNKS + NT - 1) / NT;
   static_assert(!ROW3 || (FAST && BM == 128), "ROW3 is a FAST-path form for 128-pixel tiles");
   constexpr int A3_ROWS = BM + 16;                   // ROW3: staged source rows (BM + 2 used)
-  static_assert(!STEM || (FAST && BM == 128 && !ROW3 && MODE == MODE_RAW), "STEM is a forward FAST-path form for 128-pixel tiles");
+  static_assert(!STEM || (FAST && BM == 128 && !ROW3 && (MODE == MODE_RAW || mode_is_fused(MODE))), "STEM is a forward FAST-path form for 128-pixel tiles");
   constexpr int AS_ROWS = BM + 64;                   // STEM: staged 16-byte pair rows (BM + 3 used): 3 DMA instructions
   constexpr int STAGE_ELEMS = STEM ? AS_ROWS * 8 + BN * LDS_ROW : (ROW3 ? (A3_ROWS + 3 * BN) * LDS_ROW : (BM + BN) * LDS_ROW);
   constexpr int CS_ROW = BN + 8;            // epilogue staging row (bf16)
@@ -780,6 +813,33 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bid
         }
       }
       bf16_t* Cs = lds;
+      if constexpr (mode_is_fused(MODE)) {
+        // scale / shift of this lane's quad change with (i, g): read at use as 16-byte loads (uniform over the 32 lanes of a
+        // half wave, L1 / L2 hits after the first tile) - TN * 32 constants held across the K loop would not fit the 128
+        // registers.  Quads past N (ragged channel tile) load nothing; their staged values are never stored.
+        auto stage = [&](auto actc) {
+          constexpr int ACT = decltype(actc)::value;
+#pragma unroll
+          for (int i = 0; i < TN; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+              const int col = wn * WN + i * 32 + 8 * g + 4 * fh;
+              f32x4 sc = {0.f, 0.f, 0.f, 0.f}, sh = {0.f, 0.f, 0.f, 0.f};
+              if (n0 + col < a.N) {
+                sc = *reinterpret_cast<const f32x4*>(a.scale + n0 + col);
+                sh = *reinterpret_cast<const f32x4*>(a.shift + n0 + col);
+              }
+#pragma unroll
+              for (int jj = 0; jj < TM; ++jj)
+                *reinterpret_cast<bf16x4*>(Cs + (wm * WM + jj * 32 + fr) * CS_ROW + col) = fused_quad<ACT>(acc[i][jj], g, sc, sh, a.slope);
+            }
+        };
+        if constexpr (MODE == MODE_FUSED) stage(std::integral_constant<int, ACT_SILU>{});
+        else if (a.act == ACT_RELU) stage(std::integral_constant<int, ACT_RELU>{});
+        else if (a.act == ACT_LEAKY) stage(std::integral_constant<int, ACT_LEAKY>{});
+        else if (a.act == ACT_HARDSWISH) stage(std::integral_constant<int, ACT_HARDSWISH>{});
+        else stage(std::integral_constant<int, ACT_IDENTITY>{});
+      } else {
 #pragma unroll
       for (int i = 0; i < TN; ++i)
 #pragma unroll
@@ -791,6 +851,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bid
             for (int e = 0; e < 4; ++e) v[e] = (bf16_t)acc[i][jj][g * 4 + e];
             *reinterpret_cast<bf16x4*>(Cs + (wm * WM + jj * 32 + fr) * CS_ROW + wn * WN + i * 32 + 8 * g + 4 * fh) = v;
           }
+      }
       __syncthreads();
       constexpr int CPR = BN / 8;            // 16-byte chunks per row
       constexpr int RPP = NT / CPR;          // rows per pass
@@ -878,6 +939,13 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bid
                   ssq[e] = __builtin_fmaf(dz, y, ssq[e]);
                 }
               }
+            }
+          } else if constexpr (mode_is_fused(MODE)) {
+            // the residual meets the activation as stored (bf16): second rounding, as in the two-pass form
+            if (a.residual) {
+              const bf16x8 r = *reinterpret_cast<const bf16x8*>(a.residual + (size_t)m * a.ldr + a.rcoff + n);
+#pragma unroll
+              for (int e = 0; e < 8; ++e) v[e] = (bf16_t)((float)v[e] + (float)r[e]);
             }
           } else {
 #pragma unroll
@@ -989,10 +1057,10 @@ void conv_igemm_row3_kernel(ConvArgs a) {
   conv_igemm_body<128, BN, WAVES_M, WAVES_N, MODE, true, true, F32ACC>(a, blockIdx.x);
 }
 
-template <int BN, int WAVES_M, int WAVES_N>
+template <int BN, int WAVES_M, int WAVES_N, int MODE = MODE_RAW>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 4)
 void conv_igemm_stem_kernel(ConvArgs a) {
-  conv_igemm_body<128, BN, WAVES_M, WAVES_N, MODE_RAW, true, false, false, true>(a, blockIdx.x);
+  conv_igemm_body<128, BN, WAVES_M, WAVES_N, MODE, true, false, false, true>(a, blockIdx.x);
 }
 
 // ---- the stem as its own kernel: weights resident, whole-tile double buffering -------------------------------------
@@ -1003,7 +1071,10 @@ void conv_igemm_stem_kernel(ConvArgs a) {
 // per tile, DMA latency behind a full tile of work.  Measured at B = 64 / 640 px: generic per-tap staging 355 us, row-shared
 // staging in the generic body 290 us, this kernel 240 us (0.52 GB of traffic: 2.2 TB/s; what is left is the prefetch depth
 // of one tile per block, three blocks per CU).  N <= 32.
-__global__ __launch_bounds__(256, 3) void conv_stem_fwd_kernel(ConvArgs a) {
+// MODE: MODE_RAW, or MODE_FUSED / MODE_FUSED_ACT (eval forward: BatchNorm + activation in the epilogue, no statistics).
+template <int MODE>
+__device__ __forceinline__ void conv_stem_fwd_body(const ConvArgs& a) {
+  constexpr bool FUSED = mode_is_fused(MODE);
   constexpr int BM = 128, BN = 32, NWV = 4;
   constexpr int PR = 192;                              // staged pair rows per kernel row (BM + 3 used)
   constexpr int KHM = 6;
@@ -1116,12 +1187,33 @@ __global__ __launch_bounds__(256, 3) void conv_stem_fwd_kernel(ConvArgs a) {
     //      as 16-byte channel-contiguous stores (measured: 240 us; 8-byte stores straight from the accumulators, one barrier
     //      per tile, statistics kept per lane: 257 us)
     bf16_t* Cs = reinterpret_cast<bf16_t*>(lds + W_BYTES + buf * P_BYTES);
+    if constexpr (FUSED) {
+      auto stage = [&](auto actc) {
+        constexpr int ACT = decltype(actc)::value;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int col = 8 * g + 4 * fh;
+          f32x4 sc = {0.f, 0.f, 0.f, 0.f}, sh = {0.f, 0.f, 0.f, 0.f};
+          if (col < a.N) {
+            sc = *reinterpret_cast<const f32x4*>(a.scale + col);
+            sh = *reinterpret_cast<const f32x4*>(a.shift + col);
+          }
+          *reinterpret_cast<bf16x4*>(Cs + (wave * 32 + fr) * CS_ROW + col) = fused_quad<ACT>(acc, g, sc, sh, a.slope);
+        }
+      };
+      if constexpr (MODE == MODE_FUSED) stage(std::integral_constant<int, ACT_SILU>{});
+      else if (a.act == ACT_RELU) stage(std::integral_constant<int, ACT_RELU>{});
+      else if (a.act == ACT_LEAKY) stage(std::integral_constant<int, ACT_LEAKY>{});
+      else if (a.act == ACT_HARDSWISH) stage(std::integral_constant<int, ACT_HARDSWISH>{});
+      else stage(std::integral_constant<int, ACT_IDENTITY>{});
+    } else {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       bf16x4 v;
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = (bf16_t)acc[g * 4 + e];
       *reinterpret_cast<bf16x4*>(Cs + (wave * 32 + fr) * CS_ROW + 8 * g + 4 * fh) = v;
+    }
     }
     __syncthreads();
     const int c = tid & 3, r0 = tid >> 2;
@@ -1131,12 +1223,20 @@ __global__ __launch_bounds__(256, 3) void conv_stem_fwd_kernel(ConvArgs a) {
       const int row = r0 + p * 64;
       const int m = m0 + row;
       if (m < a.M && col_ok) {
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(Cs + row * CS_ROW + c * 8);
+        bf16x8 v = *reinterpret_cast<const bf16x8*>(Cs + row * CS_ROW + c * 8);
+        if constexpr (FUSED) {
+          if (a.residual) {
+            const bf16x8 r = *reinterpret_cast<const bf16x8*>(a.residual + (size_t)m * a.ldr + a.rcoff + c * 8);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float f = (float)v[e];
-          ssum[e] += f;
-          ssq[e] += f * f;
+            for (int e = 0; e < 8; ++e) v[e] = (bf16_t)((float)v[e] + (float)r[e]);
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float f = (float)v[e];
+            ssum[e] += f;
+            ssq[e] += f * f;
+          }
         }
         *reinterpret_cast<bf16x8*>(a.y + (size_t)m * a.ldy + a.ycoff + c * 8) = v;
       }
@@ -1145,6 +1245,7 @@ __global__ __launch_bounds__(256, 3) void conv_stem_fwd_kernel(ConvArgs a) {
     buf ^= 1;
   }
 
+  if constexpr (FUSED) return;
   // ---- BatchNorm partial statistics of this block: rows by shuffle, waves by the owner thread (fixed order)
 #pragma unroll
   for (int o = 4; o < 64; o <<= 1)
@@ -1173,6 +1274,11 @@ __global__ __launch_bounds__(256, 3) void conv_stem_fwd_kernel(ConvArgs a) {
     }
   }
 }
+
+__global__ __launch_bounds__(256, 3) void conv_stem_fwd_kernel(ConvArgs a) { conv_stem_fwd_body<MODE_RAW>(a); }
+
+template <int MODE>
+__global__ __launch_bounds__(256, 3) void conv_stem_fwd_fused_kernel(ConvArgs a) { conv_stem_fwd_body<MODE>(a); }
 
 // Four problems of identical tiling in one launch (the parity classes of a stride-2 dgrad).  The classes have 4, 2, 2
 // and 1 taps - reductions of very different length - and the launch is a few rounds of resident blocks at most, so
@@ -1283,20 +1389,21 @@ int launch(const ConvArgs& a, hipStream_t stream) {
     args.slot_base = 0; args.slot_used = need;
   }
   dim3 g(p.grid);
-  if constexpr (MODE == MODE_RAW) {
+  if constexpr (MODE == MODE_RAW || mode_is_fused(MODE)) {
     // the stem's wide-pixel form
     if (fast && !row3 && a.wide_px == 4 && a.KW == 1 && a.mul_w == 1 && a.add_w == -1 && a.ldx == 8 && a.xcoff == 0 &&
         p.bm == 128 && (p.bn == 32 || p.bn == 64) && (long)a.M + 256 < (1l << 31)) {
       // the dedicated kernel for N <= 32, else row-shared staging inside the generic body
       if (p.bn == 32 && a.N <= 32 && a.KH == 6 && a.ycoff % 8 == 0) {
         int blocks = p.tiles_m < 768 ? p.tiles_m : 768;             // 3 resident blocks per CU (48 KB of LDS each)
-        if (blocks > a.stats_slots) blocks = a.stats_slots;
-        hipLaunchKernelGGL(conv_stem_fwd_kernel, dim3(blocks), dim3(256), 0, stream, args);
+        if (blocks > a.stats_slots) blocks = a.stats_slots;           // (the fused modes keep the raw mode's grid: same slot count)
+        if constexpr (MODE == MODE_RAW) hipLaunchKernelGGL(conv_stem_fwd_kernel, dim3(blocks), dim3(256), 0, stream, args);
+        else hipLaunchKernelGGL(conv_stem_fwd_fused_kernel<MODE>, dim3(blocks), dim3(256), 0, stream, args);
         KOD_LAUNCH_CHECK("conv_stem_fwd");
         return KOD_OK;
       }
-      if (p.bn == 32) hipLaunchKernelGGL((conv_igemm_stem_kernel<32, 4, 1>), g, dim3(256), 0, stream, args);
-      else hipLaunchKernelGGL((conv_igemm_stem_kernel<64, 2, 2>), g, dim3(256), 0, stream, args);
+      if (p.bn == 32) hipLaunchKernelGGL((conv_igemm_stem_kernel<32, 4, 1, MODE>), g, dim3(256), 0, stream, args);
+      else hipLaunchKernelGGL((conv_igemm_stem_kernel<64, 2, 2, MODE>), g, dim3(256), 0, stream, args);
       KOD_LAUNCH_CHECK("conv_igemm_stem");
       return KOD_OK;
     }
@@ -1434,6 +1541,36 @@ int kodhip_conv_fwd_raw(const void* x, const void* w_packed, void* y, float* sta
   ConvArgs a;
   if (int rc = prep_fwd_raw(a, x, w_packed, y, stats, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff)) return rc;
   return launch<MODE_RAW>(a, stream);
+}
+
+// Forward conv of an EVAL-mode conv+BN+act unit as one launch: out = act(conv(x, w) * scale + shift) (+ residual), the
+// BatchNorm constants applied to the fp32 accumulators (one bf16 rounding; with a residual a second one, of the sum of the
+// rounded activation and the residual - what the two-pass form rounds too).  No pre-BN tensor, no statistics.  Same
+// geometry, tiles and launch plan as kodhip_conv_fwd_raw (kodhip_conv_plan_query op 0 answers for both).  `out` must not
+// overlap `x` or `residual`: tiles are written while neighbouring tiles still read.
+int kodhip_conv_fwd_fused(const void* x, const void* w_packed, const float* scale, const float* shift,
+                          const void* residual, int ldr, int rcoff, void* out,
+                          int B, int H, int W, int ldx, int xcoff, int Cin,
+                          int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
+                          int ldo, int ocoff, int act, float slope, hipStream_t stream) {
+  ConvArgs a;
+  const void* fake = (const void*)64;        // prep_fwd_raw's output checks under its own name; replaced below
+  KOD_CHECK_ARG(scale && shift && out, "conv_fwd_fused: null scale / shift / output");
+  KOD_CHECK_ARG(act >= ACT_SILU && act <= ACT_IDENTITY, "conv_fwd_fused: bad activation %d", act);
+  KOD_CHECK_ARG(((uintptr_t)scale | (uintptr_t)shift) % 16 == 0, "conv_fwd_fused: scale / shift must be 16-byte aligned");
+  KOD_CHECK_ARG(N % 8 == 0 && ldo % 8 == 0 && ocoff % 8 == 0 && ocoff >= 0 && ocoff + N <= ldo, "conv_fwd_fused: bad output slice (N=%d ldo=%d off=%d)", N, ldo, ocoff);
+  KOD_CHECK_ARG(!residual || (ldr % 8 == 0 && rcoff % 8 == 0 && rcoff >= 0 && rcoff + N <= ldr),
+                "conv_fwd_fused: bad residual slice (N=%d ldr=%d off=%d)", N, ldr, rcoff);
+  if (int rc = prep_fwd_raw(a, x, w_packed, out, (float*)fake, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldo, ocoff)) {
+    char msg[448];                            // the shared geometry checks speak of "conv": name this entry point
+    snprintf(msg, sizeof(msg), "%s", kodhip_last_error());
+    kodhip_set_error("conv_fwd_fused: %s", msg);
+    return rc;
+  }
+  a.stats = nullptr;
+  a.scale = scale; a.shift = shift; a.residual = (const bf16_t*)residual; a.ldr = ldr; a.rcoff = rcoff;
+  a.act = act; a.slope = slope;
+  return act == ACT_SILU ? launch<MODE_FUSED>(a, stream) : launch<MODE_FUSED_ACT>(a, stream);
 }
 
 // Fused detection head of one level: out[B][A][Ho*Wo][P] fp32 = 1x1 conv (N = A*(5+nc) packed as

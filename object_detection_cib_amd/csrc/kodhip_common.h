@@ -68,6 +68,17 @@ __device__ __forceinline__ float kod_silu_bwd(float g, float z, float sg) {
   return g * __builtin_fmaf(sg, t, sg);
 }
 
+// The activation slot of a conv+BN+act unit (`act` of the C ABI), shared by the plain passes of bn_act.hip and the fused
+// forward epilogue of conv_igemm.hip.  SiLU is formed by its callers as z * kod_sigmoid_l2(KOD_NEG_LOG2E * z); the others
+// follow torch's conventions at the kinks (see bn_act.hip).
+enum { ACT_SILU = 0, ACT_RELU = 1, ACT_LEAKY = 2, ACT_HARDSWISH = 3, ACT_IDENTITY = 4 };
+template <int ACT> __device__ __forceinline__ float kod_act(float z, float slope) {
+  if (ACT == ACT_RELU) return z > 0.f ? z : 0.f;
+  if (ACT == ACT_LEAKY) return z > 0.f ? z : z * slope;
+  if (ACT == ACT_HARDSWISH) return z * fminf(fmaxf(z + 3.f, 0.f), 6.f) / 6.f;
+  return z;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

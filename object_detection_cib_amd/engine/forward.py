@@ -132,6 +132,9 @@ class ForwardMixin:
         # have no statistics stage (no running-statistic update, no SyncBN exchange)
         mp = self.sync_bn_mode() if training else None
         mp = None if (mp is None or mp.is_default) else mp
+        # eval forward only, read per call (the option may be toggled on a live engine).  A training forward never fuses,
+        # eval UNITS of a training network included: their backward needs the saved pre-BN tensor
+        fused = (not training) and self.opt.eval_fused
 
         def conv_stage(u: ConvUnit, s=s):
             st, C_ = self.ustate[u.name], u.cout
@@ -145,6 +148,24 @@ class ForwardMixin:
             cin_true = 3 if u.stem else u.cin
             in_px = B * H * W if u.stem else B * st.H * st.W
             self._t1(e0, "conv_fwd", 2 * (in_px * cin_true + st.M * C_), name=u.name)
+
+        def fused_stage(u: ConvUnit, s=s):
+            """eval forward with EngineOptions.eval_fused: conv + BatchNorm (running statistics) + activation (+ residual)
+            as ONE launch from u.src to u.dst - no pre-BN tensor (st.raw), no statistics, no apply pass"""
+            st, C_ = self.ustate[u.name], u.cout
+            if u.stem:
+                geo = (B, st.H, st.W, 8, 0, 32, C_, 6, 1, 2, 1, 2, 1, st.Kp_f)      # wide-pixel form, see Kp_f
+            else:
+                geo = (B, st.H, st.W, u.src.buf.C, u.src.coff, u.cin, C_, u.k, u.k, u.s, u.s, u.p, u.p, st.Kp_f)
+            sc_p, sh_p = eval_aff[u.name]
+            res = u.residual
+            e0 = self._t0()
+            chk(lib.kodhip_conv_fwd_fused(self._ptr(u.src), fp + 2 * st.f_off, sc_p, sh_p,
+                                          self._ptr(res) if res else None, res.buf.C if res else 0, res.coff if res else 0,
+                                          self._ptr(u.dst), *geo, u.dst.buf.C, u.dst.coff, self.act_kind, self.act_slope, s), u.name)
+            cin_true = 3 if u.stem else u.cin
+            in_px = B * H * W if u.stem else B * st.H * st.W
+            self._t1(e0, "conv_fwd_fused", 2 * (in_px * cin_true + st.M * C_) + (2 * st.M * C_ if res else 0), name=u.name)
 
         def finalize_args(u: ConvUnit, ranks: int):
             """the finalize kernels' common arguments: (element count over `ranks`, gamma, beta, running mean / variance,
@@ -251,7 +272,9 @@ class ForwardMixin:
             if op.kind == "conv" and after_first_layer is not None and i > 1:
                 after_first_layer()
                 after_first_layer = None
-            if op.kind == "conv":
+            if op.kind == "conv" and fused:
+                fused_stage(op.unit)
+            elif op.kind == "conv":
                 group = [op.unit]
                 # SyncBN over RCCL: a unit and its sibling (same input, next in the program) share one statistic exchange
                 if sync and self.peer is None and op.unit.sibling is not None and i < len(ops) and ops[i].unit is op.unit.sibling:

@@ -246,6 +246,7 @@ class GraphedEvalForward:
         self.x = torch.zeros((batch_size, 3, height, width), dtype=torch.float32, device=self.eng.device)
         self.shape = FeatureShape(width=width, height=height)
         self.graph, self.det = None, None
+        self._eval_fused = None           # EngineOptions.eval_fused the graph was captured with
 
     def _forward(self):
         from ..nn.networks.yolov5 import Yolov5NetworkResult
@@ -273,6 +274,7 @@ class GraphedEvalForward:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self._refresh()
+        self._eval_fused = bool(eng.opt.eval_fused)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.det = self._forward()
@@ -284,6 +286,10 @@ class GraphedEvalForward:
         if self.graph is None:
             self.capture(images)
         assert tuple(images.shape) == tuple(self.x.shape), (images.shape, self.x.shape)
+        if bool(self.eng.opt.eval_fused) != self._eval_fused:
+            # the graph replays the launches of the form it was captured with (one fused launch per unit, or conv + apply)
+            raise RuntimeError("EngineOptions.eval_fused changed after capture(): the captured forward holds the old launches; "
+                               "build a new GraphedEvalForward and capture() again")
         self._refresh()
         self.x.copy_(images, non_blocking=True)
         # a replay needs this shape's buffer set to be what the graph captured - it is pinned, nothing to swap

@@ -40,6 +40,7 @@ class EngineOptions:
     dx_accum_fp32: bool = False       # KODHIP_DX_FP32: multi-consumer activation gradients accumulated in fp32
     dual_wgrad: bool = True           # KODHIP_NO_DUAL_WGRAD=1 switches off: a CSP layer's main + short weight gradients in one launch
     stem_bwd_fused: bool = True       # KODHIP_STEM_BWD_FUSED: the stem's BN/SiLU backward inside its weight gradient (dY never written)
+    eval_fused: bool = False          # KODHIP_EVAL_FUSED: eval forward runs conv + BatchNorm + activation (+ residual) as one launch per unit
     debug_plan: bool = False          # KODHIP_DEBUG_PLAN
     max_shape_sets: int = 4           # KODHIP_MAX_SHAPE_SETS
     bucket_mb: float = 8.0
@@ -60,6 +61,7 @@ class EngineOptions:
             dx_accum_fp32=_flag("KODHIP_DX_FP32", False),
             dual_wgrad=not _flag("KODHIP_NO_DUAL_WGRAD", False),
             stem_bwd_fused=_flag("KODHIP_STEM_BWD_FUSED", True),
+            eval_fused=_flag("KODHIP_EVAL_FUSED", False),
             debug_plan=_flag("KODHIP_DEBUG_PLAN", False),
             max_shape_sets=int(e.get("KODHIP_MAX_SHAPE_SETS", "4")),
             native={k: e[k] for k in NATIVE_KNOBS if k in e},

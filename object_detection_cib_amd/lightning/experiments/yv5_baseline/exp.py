@@ -51,7 +51,8 @@ class DefaultYolov5Experiment:
                  optimizer_warmup_updater: Optional[OptimizerWarmupUpdater] = None,
                  val_nms_conf_threshold: float = 0.001, val_nms_iou_threshold: float = 0.6, *, max_epochs: int = 300,
                  graphed: bool = False, max_targets: int = 4096, world_size: int = 1,
-                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm"):
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
+                 eval_fused: Optional[bool] = None):
         if gradient_clip_algorithm not in CLIP_ALGORITHMS:
             raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected one of {CLIP_ALGORITHMS}")
         # Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm): handed to the FusedSGD / the captured step
@@ -73,6 +74,9 @@ class DefaultYolov5Experiment:
         # arithmetic, no per-launch Python; batches must keep one shape and at most max_targets boxes
         self.graphed, self.max_targets, self._gstep = graphed, max_targets, None
         self._geval = {}              # input shape -> GraphedEvalForward
+        # validation forwards with BatchNorm + activation in the conv epilogue (Yolov5Network.fuse_eval); None leaves the
+        # engine's option (EngineOptions.eval_fused / KODHIP_EVAL_FUSED) alone
+        self.eval_fused = eval_fused
         # cross-rank validation: "auto" (default) = the group the network was made data-parallel over
         # (Yolov5Network.configure_distributed) with sync "mean", i.e. what the reference logs under DDP
         # (`log_dict(results, sync_dist=True)`, pycoco_map_eval.py:139-142); without such a group every rank reports its
@@ -220,6 +224,8 @@ class DefaultYolov5Experiment:
     def validate(self, batches: Sequence, num_classes: int, class_names=None) -> dict:
         ev = DeviceMAPEvaluator(num_classes, class_names)
         _lib.limit_host_threads()
+        if self.eval_fused is not None:
+            self.net.fuse_eval(self.eval_fused)
         with _gc_paused():
             for b in batches:
                 targets, dets = self.validation_step(b)

@@ -9,6 +9,7 @@ kernel.  There is no CPU path.
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 from typing import Sequence
 
@@ -156,8 +157,20 @@ class GraphModule(nn.Module):
             # the units' BatchNorm modules: their `training` flags decide, at every training forward, which units
             # normalise with running statistics (engine/bn_mode.py)
             eng.bn_modules = [self.get_submodule(u.name + ".1") for u in eng.exec_units]
+            if getattr(self, "_eval_fused", None) is not None:          # fuse_eval() before the engine existed
+                eng.opt = dataclasses.replace(eng.opt, eval_fused=self._eval_fused)
             self._engine, self._engine_device = eng, dev
         return self._engine
+
+    def fuse_eval(self, enabled: bool = True):
+        """Eval-mode forwards run every conv + BatchNorm + activation (+ residual) unit as ONE kernel launch: the running-
+        statistic constants are applied in the convolution's epilogue (EngineOptions.eval_fused, kodhip_conv_fwd_fused).
+        Only the launch program changes: parameters, buffers and `state_dict()` are untouched, training forwards are
+        unaffected, and `fuse_eval(False)` returns to the two-pass form.  Returns self."""
+        self._eval_fused = bool(enabled)
+        if self._engine is not None:
+            self._engine.opt = dataclasses.replace(self._engine.opt, eval_fused=self._eval_fused)
+        return self
 
     def _freeze_anchor(self, eng):
         """Freeze plan from requires_grad (engine/freeze.py); a trainable tensor for the autograd node, None when every
