@@ -249,8 +249,9 @@ int kodhip_bn_silu_bwd_apply(const void* dA, int lda, int dacoff, void* y_inout,
 
 /* The same three elementwise passes for the other activations the reference's layer signatures admit
  * (kod/nn/layers/csp.py:16-46: `activation_layer: Callable[..., nn.Module]`; its configs use SiLUInplace only):
- * act = 0 SiLU (dispatches to the entries above), 1 ReLU, 2 LeakyReLU(slope), 3 Hardswish, 4 identity (activation_layer=None);
- * torch's conventions at the kinks.  A network built with one of them runs the BatchNorm-backward reduction as its own pass. */
+ * act = 0 SiLU (the entries above are this with act = 0), 1 ReLU, 2 LeakyReLU(slope), 3 Hardswish, 4 identity (activation_layer=None);
+ * torch's conventions at the kinks.  One set of kernels, the activation a template parameter; a network built with a
+ * non-SiLU one runs the BatchNorm-backward reduction as its own pass. */
 int kodhip_bn_act_apply(const void* y, int ldy, const float* scale, const float* shift, const void* residual, int ldr, int rcoff,
                         void* out, int ldo, int ocoff, long M, int C, int act, float slope, kodStream_t stream);
 int kodhip_bn_act_bwd_apply(const void* dA, int lda, int dacoff, void* y_inout, int ldy, const float* scale, const float* shift,

@@ -1,4 +1,4 @@
-// Train-mode BatchNorm2d(eps=1e-3, momentum=.03) + SiLU around the conv kernels
+// Train-mode BatchNorm2d(eps=1e-3, momentum=.03) + activation (SiLU, or another of kodhip_common.h's ACT_*) around the conv kernels
 // (kod/nn/networks/yolov5.py:24 Yolov5BatchNorm2d, kod/nn/layers/activations.py:7 SiLUInplace; the
 // aten ops native_batch_norm / silu / their backwards and the CSPBlock residual add, csp.py:55-56).
 //
@@ -287,20 +287,22 @@ __global__ __launch_bounds__(256) void bn_eval_constants_kernel(const BnEvalDesc
 // The elementwise passes are pure HBM streams: each thread keeps U rows (U x 16 B per operand) in flight before it
 // touches the first one - with a single load per iteration the chip holds too few bytes in flight to cover the
 // HBM latency (measured 3.5-4.5 TB/s; Little's law wants >= 12 MB outstanding for 8 TB/s).
-constexpr int U = 4;          // (the reduce kernels; the two apply passes take it as a template parameter)
+constexpr int U = 4;          // (the reduce kernel; the two apply passes take it as a template parameter)
 
 // ---------------------------------------------------------------- forward apply
-// out[m][ocoff + c] = silu(y[m][c]*scale[c] + shift[c]) (+ res[m][rcoff + c])
+// out[m][ocoff + c] = act(y[m][c]*scale[c] + shift[c]) (+ res[m][rcoff + c])
+// (the three passes keep the names they were tuned under - bn_silu_* - for every ACT: bench.py's family table,
+// tools/refresh_profiles.py and tools/pmc_s2_reduce.py find them by these names)
 // Launch shape (template + launch arguments, chosen per tensor by apply_shape() below): U rows of one block-contiguous chunk
 // in flight per thread (rows m0, m0 + rpb, ...: a block reads U * rpb * C * 2 contiguous bytes per operand), blocks of up to
 // MAXT threads, and - LDSK - the per-channel constants staged through LDS once per block instead of read from global memory
 // by every thread: with many short blocks the constant loads otherwise outnumber the payload's (4 + 2 vector memory
 // instructions per row here, 10 + 3 in the backward pass) and the pass becomes address-unit-bound
 // (tools/micro/stream_apply.hip, profiles/r06_stream_apply.txt).
-template <int U, bool LDSK, int MAXT>
+template <int ACT, int U, bool LDSK, int MAXT>
 __global__ __launch_bounds__(MAXT) void bn_silu_apply_kernel(const bf16_t* y, int ldy, const float* scale, const float* shift,
                                      const bf16_t* res, int ldr, int rcoff,
-                                     bf16_t* out, int ldo, int ocoff, long M, int C, int rows_per_block_iter) {
+                                     bf16_t* out, int ldo, int ocoff, long M, int C, int rows_per_block_iter, float slope) {
   extern __shared__ float kconst[];           // LDSK: [scale C | shift C]
   const int CC = C >> 3;
   const int cc = threadIdx.x % CC;
@@ -335,20 +337,20 @@ __global__ __launch_bounds__(MAXT) void bn_silu_apply_kernel(const bf16_t* y, in
       bf16x8 o;
       if (res) {
         // the reference adds in fp32 on the fp32 activation; here the activation is rounded to bf16 only when it
-        // is materialised, so add before the single rounding.
+        // is materialised, so add before the single rounding.  (SiLU: z * sg + r as one fma - the one place where its
+        // bits are not kod_act<>'s)
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float yv = (float)v[u][e];
           const float z = __builtin_fmaf(yv, sc[e], sh[e]);
-          const float sg = kod_sigmoid_l2(KOD_NEG_LOG2E * z);
-          o[e] = (bf16_t)__builtin_fmaf(z, sg, (float)r[u][e]);
+          if constexpr (ACT == ACT_SILU) o[e] = (bf16_t)__builtin_fmaf(z, kod_sigmoid_l2(KOD_NEG_LOG2E * z), (float)r[u][e]);
+          else o[e] = (bf16_t)(kod_act<ACT>(z, slope) + (float)r[u][e]);
         }
       } else {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float yv = (float)v[u][e];
-          const float z = __builtin_fmaf(yv, sc[e], sh[e]);
-          o[e] = (bf16_t)(z * kod_sigmoid_l2(KOD_NEG_LOG2E * z));
+          o[e] = (bf16_t)kod_act<ACT>(__builtin_fmaf(yv, sc[e], sh[e]), slope);
         }
       }
 #ifdef KOD_BN_NTST
@@ -361,11 +363,12 @@ __global__ __launch_bounds__(MAXT) void bn_silu_apply_kernel(const bf16_t* y, in
 }
 
 // ---------------------------------------------------------------- backward reduce
-// dz = dA * silu'(z), z = y*scale + shift ; xhat = (y - mean)*rstd
+// dz = dA * act'(z), z = y*scale + shift ; xhat = (y - mean)*rstd
 // part[0][c][blk] = sum dz ; part[1][c][blk] = sum dz*xhat
+template <int ACT>
 __global__ __launch_bounds__(256) void bn_silu_bwd_reduce_kernel(const bf16_t* dA, int lda, int dacoff, const bf16_t* y, int ldy,
                                           const float* scale, const float* shift, const float* mean,
-                                          const float* rstd, float* part, long M, int C, int rpb) {
+                                          const float* rstd, float* part, long M, int C, int rpb, float slope) {
   extern __shared__ float sm[];   // [rpb][CC][16]
   const int CC = C >> 3;
   const int cc = threadIdx.x % CC;
@@ -396,9 +399,7 @@ __global__ __launch_bounds__(256) void bn_silu_bwd_reduce_kernel(const bf16_t* d
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float yv = (float)v[u][e];
-          const float z = __builtin_fmaf(yv, sc[e], sh[e]);
-          const float sg = kod_sigmoid_l2(KOD_NEG_LOG2E * z);
-          const float dz = kod_silu_bwd((float)g[u][e], z, sg);
+          const float dz = kod_act_bwd<ACT>((float)g[u][e], __builtin_fmaf(yv, sc[e], sh[e]), slope);
           s0[e] += dz;
           s1[e] += dz * (yv - mu[e]) * rs[e];
         }
@@ -421,115 +422,6 @@ __global__ __launch_bounds__(256) void bn_silu_bwd_reduce_kernel(const bf16_t* d
   }
 }
 
-// ---------------------------------------------------------------- activations other than SiLU
-// The reference's layers take any activation callable (kod/nn/layers/csp.py:16-46, sppf.py:14-27, networks/yolov5.py:40-50);
-// its configs only ever use SiLUInplace, which the tuned kernels above (and the fused epilogues in conv_igemm.hip /
-// conv_wgrad.hip) implement.  These three plain passes carry the other elementwise activations torch offers for the slot -
-// ReLU, LeakyReLU(slope), Hardswish, Identity (activation_layer=None) - with torch's conventions at the kinks
-// (aten/native/cpu/Activation.cpp: relu' (0) = 0, leaky_relu' uses x > 0, hardswish' = 0 up to -3, x / 3 + 0.5 inside (-3, 3), 1 from 3 on);
-// a network built with one of them runs its BatchNorm-backward reduction as its own pass (no fused epilogues).
-// (the ACT_* enum and kod_act<> live in kodhip_common.h: the forward convolution's fused epilogue uses them too)
-template <int ACT> __device__ __forceinline__ float kod_act_bwd(float g, float z, float slope) {
-  if (ACT == ACT_RELU) return z > 0.f ? g : 0.f;
-  if (ACT == ACT_LEAKY) return z > 0.f ? g : g * slope;
-  if (ACT == ACT_HARDSWISH) return z <= -3.f ? 0.f : (z < 3.f ? g * ((z / 3.f) + 0.5f) : g);     // (torch 2.x: 0 at -3, g at 3)
-  return g;
-}
-
-template <int ACT>
-__global__ __launch_bounds__(256) void bn_act_apply_kernel(const bf16_t* y, int ldy, const float* scale, const float* shift,
-                                                           const bf16_t* res, int ldr, int rcoff, bf16_t* out, int ldo, int ocoff,
-                                                           long M, int C, int rpb, float slope) {
-  const int CC = C >> 3, cc = threadIdx.x % CC, rl = threadIdx.x / CC;
-  if (rl >= rpb) return;
-  float sc[8], sh[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { sc[e] = scale[cc * 8 + e]; sh[e] = shift[cc * 8 + e]; }
-  for (long m = (long)blockIdx.x * rpb + rl; m < M; m += (long)gridDim.x * rpb) {
-    const bf16x8 v = *reinterpret_cast<const bf16x8*>(y + m * ldy + cc * 8);
-    bf16x8 r = {}, o;
-    if (res) r = *reinterpret_cast<const bf16x8*>(res + m * ldr + rcoff + cc * 8);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float a = kod_act<ACT>(__builtin_fmaf((float)v[e], sc[e], sh[e]), slope);
-      o[e] = (bf16_t)(res ? a + (float)r[e] : a);
-    }
-    *reinterpret_cast<bf16x8*>(out + m * ldo + ocoff + cc * 8) = o;
-  }
-}
-
-template <int ACT>
-__global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const bf16_t* dA, int lda, int dacoff, bf16_t* y, int ldy,
-                                                               const float* scale, const float* shift, const float* coef,
-                                                               bf16_t* dI, int ldi, int dicoff, int di_accum, long M, int C, int rpb,
-                                                               float slope) {
-  const int CC = C >> 3, cc = threadIdx.x % CC, rl = threadIdx.x / CC;
-  if (rl >= rpb) return;
-  float sc[8], sh[8], k1[8], k2[8], k3[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int c = cc * 8 + e;
-    sc[e] = scale[c]; sh[e] = shift[c]; k1[e] = coef[c]; k2[e] = coef[C + c]; k3[e] = coef[2 * C + c];
-  }
-  for (long m = (long)blockIdx.x * rpb + rl; m < M; m += (long)gridDim.x * rpb) {
-    const bf16x8 g = *reinterpret_cast<const bf16x8*>(dA + m * lda + dacoff + cc * 8);
-    const bf16x8 v = *reinterpret_cast<const bf16x8*>(y + m * ldy + cc * 8);
-    bf16x8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float yv = (float)v[e];
-      const float dz = kod_act_bwd<ACT>((float)g[e], __builtin_fmaf(yv, sc[e], sh[e]), slope);
-      o[e] = (bf16_t)__builtin_fmaf(k1[e], dz, __builtin_fmaf(k2[e], yv, k3[e]));
-    }
-    *reinterpret_cast<bf16x8*>(y + m * ldy + cc * 8) = o;
-    if (dI) {
-      bf16x8 gi = g;
-      if (di_accum) {
-        const bf16x8 old = *reinterpret_cast<const bf16x8*>(dI + m * ldi + dicoff + cc * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) gi[e] = (bf16_t)((float)gi[e] + (float)old[e]);
-      }
-      *reinterpret_cast<bf16x8*>(dI + m * ldi + dicoff + cc * 8) = gi;
-    }
-  }
-}
-
-template <int ACT>
-__global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(const bf16_t* dA, int lda, int dacoff, const bf16_t* y, int ldy,
-                                                                const float* scale, const float* shift, const float* mean,
-                                                                const float* rstd, float* part, long M, int C, int rpb, float slope) {
-  extern __shared__ float sm[];   // [rpb][CC][16]
-  const int CC = C >> 3, cc = threadIdx.x % CC, rl = threadIdx.x / CC;
-  float s0[8], s1[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) s0[e] = s1[e] = 0.f;
-  if (rl < rpb) {
-    float sc[8], sh[8], mu[8], rs[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { sc[e] = scale[cc * 8 + e]; sh[e] = shift[cc * 8 + e]; mu[e] = mean[cc * 8 + e]; rs[e] = rstd[cc * 8 + e]; }
-    for (long m = (long)blockIdx.x * rpb + rl; m < M; m += (long)gridDim.x * rpb) {
-      const bf16x8 g = *reinterpret_cast<const bf16x8*>(dA + m * lda + dacoff + cc * 8);
-      const bf16x8 v = *reinterpret_cast<const bf16x8*>(y + m * ldy + cc * 8);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float yv = (float)v[e];
-        const float dz = kod_act_bwd<ACT>((float)g[e], __builtin_fmaf(yv, sc[e], sh[e]), slope);
-        s0[e] += dz;
-        s1[e] += dz * (yv - mu[e]) * rs[e];
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { sm[(rl * CC + cc) * 16 + e] = s0[e]; sm[(rl * CC + cc) * 16 + 8 + e] = s1[e]; }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < CC * 16; i += blockDim.x) {          // fixed-order reduction over the row lanes
-    const int c8 = i >> 4, e = i & 15;
-    float s = 0.f;
-    for (int r = 0; r < rpb; ++r) s += sm[(r * CC + c8) * 16 + e];
-    part[((size_t)(e >> 3) * C + c8 * 8 + (e & 7)) * gridDim.x + blockIdx.x] = s;
-  }
-}
-
 // grads from the LOCAL sums; coefficients from the (all-reduced) sums:
 //   dY = k1*dz + k2*y + k3,  k1 = g*rstd, k2 = -g*rstd^2*S1/n, k3 = -g*rstd*S0/n + g*rstd^2*mean*S1/n
 __global__ void bn_bwd_coeffs_kernel(const double* sums_local, const double* sums_global, double count,
@@ -549,11 +441,11 @@ __global__ void bn_bwd_coeffs_kernel(const double* sums_local, const double* sum
 }
 
 // dY (bf16, written in place over y) ; optional identity gradient: dI[m][c] (+)= dA[m][c]
-template <int U, bool LDSK, int MAXT>
+template <int ACT, int U, bool LDSK, int MAXT>
 __global__ __launch_bounds__(MAXT) void bn_silu_bwd_apply_kernel(const bf16_t* dA, int lda, int dacoff, bf16_t* y, int ldy,
                                          const float* scale, const float* shift, const float* coef,
                                          bf16_t* dI, int ldi, int dicoff, int di_accum,
-                                         long M, int C, int rpb) {
+                                         long M, int C, int rpb, float slope) {
   extern __shared__ float kconst[];           // LDSK: [scale C | shift C | k1 C | k2 C | k3 C]
   const int CC = C >> 3;
   const int cc = threadIdx.x % CC;
@@ -609,9 +501,7 @@ __global__ __launch_bounds__(MAXT) void bn_silu_bwd_apply_kernel(const bf16_t* d
 #pragma unroll
         for (int e = 4 * h; e < 4 * h + 4; ++e) {
           const float yv = (float)v[u][e];
-          const float z = __builtin_fmaf(yv, sc[e], sh[e]);
-          const float sg = kod_sigmoid_l2(KOD_NEG_LOG2E * z);
-          const float dz = kod_silu_bwd((float)g[u][e], z, sg);
+          const float dz = kod_act_bwd<ACT>((float)g[u][e], __builtin_fmaf(yv, sc[e], sh[e]), slope);
           o[e] = (bf16_t)__builtin_fmaf(k1[e], dz, __builtin_fmaf(k2[e], yv, k3[e]));
         }
       }
@@ -814,20 +704,25 @@ int kodhip_bn_eval_constants(const void* desc, int n_units, float eps, hipStream
 
 int kodhip_bn_eval_desc_bytes(void) { return (int)sizeof(BnEvalDesc); }
 
-int kodhip_bn_silu_apply(const void* y, int ldy, const float* scale, const float* shift,
-                         const void* residual, int ldr, int rcoff,
-                         void* out, int ldo, int ocoff, long M, int C, hipStream_t stream) {
-  KOD_CHECK_ARG(y && scale && shift && out && M > 0, "bn_silu_apply: bad args");
-  KOD_CHECK_ARG(C % 8 == 0 && C <= 2048 && ldo % 8 == 0 && ocoff % 8 == 0 && ocoff + C <= ldo, "bn_silu_apply: bad channel geometry");
-  KOD_CHECK_ARG(!residual || (ldr % 8 == 0 && rcoff % 8 == 0 && rcoff + C <= ldr), "bn_silu_apply: bad residual slice");
+// ---- the three elementwise passes: act = 0 SiLU, 1 ReLU, 2 LeakyReLU(slope), 3 Hardswish, 4 identity
+// (activation_layer=None).  One implementation per pass; `fn` names the entry point that was called in the messages.
+static int bn_apply(const char* fn, const void* y, int ldy, const float* scale, const float* shift, const void* residual, int ldr,
+                    int rcoff, void* out, int ldo, int ocoff, long M, int C, int act, float slope, hipStream_t stream) {
+  KOD_CHECK_ARG(act >= ACT_SILU && act <= ACT_IDENTITY, "%s: activation code %d", fn, act);
+  KOD_CHECK_ARG(y && scale && shift && out && M > 0, "%s: bad args", fn);
+  KOD_CHECK_ARG(C % 8 == 0 && C <= 2048 && ldo % 8 == 0 && ocoff % 8 == 0 && ocoff + C <= ldo, "%s: bad channel geometry", fn);
+  KOD_CHECK_ARG(!residual || (ldr % 8 == 0 && rcoff % 8 == 0 && rcoff + C <= ldr), "%s: bad residual slice", fn);
+  KOD_CHECK_ARG(ldy % 8 == 0 && ldy >= C, "%s: bad row stride of y", fn);
   const ApplyShape a = apply_shape(M, C, false);
-  Geo g = geo(M, C, a.cap, a.threads, a.u);
-  KOD_CHECK_ARG(ldy % 8 == 0 && ldy >= C, "bn_silu_apply: bad row stride of y");
-#define KOD_APPLY(UU, LL, TT) hipLaunchKernelGGL((bn_silu_apply_kernel<UU, LL, TT>), dim3(g.grid), dim3(g.threads), LL ? 2 * C * sizeof(float) : 0, stream, \
-                     (const bf16_t*)y, ldy, scale, shift, (const bf16_t*)residual, ldr, rcoff, (bf16_t*)out, ldo, ocoff, M, C, g.rpb)
-  KOD_APPLY_DISPATCH(KOD_APPLY);
+  const Geo g = geo(M, C, a.cap, a.threads, a.u);
+  kod_with_act(act, [&](auto actc) {
+    constexpr int ACT = decltype(actc)::value;
+#define KOD_APPLY(UU, LL, TT) hipLaunchKernelGGL((bn_silu_apply_kernel<ACT, UU, LL, TT>), dim3(g.grid), dim3(g.threads), LL ? 2 * C * sizeof(float) : 0, stream, \
+                     (const bf16_t*)y, ldy, scale, shift, (const bf16_t*)residual, ldr, rcoff, (bf16_t*)out, ldo, ocoff, M, C, g.rpb, slope)
+    KOD_APPLY_DISPATCH(KOD_APPLY);
 #undef KOD_APPLY
-  KOD_LAUNCH_CHECK("bn_silu_apply");
+  });
+  KOD_LAUNCH_CHECK(fn);
   return KOD_OK;
 }
 
@@ -841,17 +736,20 @@ static int bwd_reduce_blocks(long M, int C) {
 
 int kodhip_bn_bwd_slots(long M, int C) { return geo(M, C, bwd_reduce_blocks(M, C)).grid; }
 
-int kodhip_bn_silu_bwd_reduce(const void* dA, int lda, int dacoff, const void* y, int ldy, const float* scale,
-                              const float* shift, const float* mean, const float* rstd, float* partials,
-                              long M, int C, hipStream_t stream) {
-  KOD_CHECK_ARG(dA && y && scale && shift && mean && rstd && partials && M > 0, "bn_silu_bwd_reduce: bad args");
-  KOD_CHECK_ARG(C % 8 == 0 && C <= 2048 && lda % 8 == 0 && dacoff % 8 == 0 && dacoff + C <= lda, "bn_silu_bwd_reduce: bad geometry");
-  Geo g = geo(M, C, bwd_reduce_blocks(M, C));
-  size_t shm = (size_t)g.rpb * (C / 8) * 16 * sizeof(float);
-  KOD_CHECK_ARG(ldy % 8 == 0 && ldy >= C, "bn_silu_bwd_reduce: bad row stride of y");
-  hipLaunchKernelGGL(bn_silu_bwd_reduce_kernel, dim3(g.grid), dim3(g.threads), shm, stream, (const bf16_t*)dA, lda,
-                     dacoff, (const bf16_t*)y, ldy, scale, shift, mean, rstd, partials, M, C, g.rpb);
-  KOD_LAUNCH_CHECK("bn_silu_bwd_reduce");
+static int bn_bwd_reduce(const char* fn, const void* dA, int lda, int dacoff, const void* y, int ldy, const float* scale,
+                         const float* shift, const float* mean, const float* rstd, float* partials, long M, int C, int act,
+                         float slope, hipStream_t stream) {
+  KOD_CHECK_ARG(act >= ACT_SILU && act <= ACT_IDENTITY, "%s: activation code %d", fn, act);
+  KOD_CHECK_ARG(dA && y && scale && shift && mean && rstd && partials && M > 0, "%s: bad args", fn);
+  KOD_CHECK_ARG(C % 8 == 0 && C <= 2048 && lda % 8 == 0 && dacoff % 8 == 0 && dacoff + C <= lda, "%s: bad geometry", fn);
+  KOD_CHECK_ARG(ldy % 8 == 0 && ldy >= C, "%s: bad row stride of y", fn);
+  const Geo g = geo(M, C, bwd_reduce_blocks(M, C));
+  const size_t shm = (size_t)g.rpb * (C / 8) * 16 * sizeof(float);
+  kod_with_act(act, [&](auto actc) {
+    hipLaunchKernelGGL(bn_silu_bwd_reduce_kernel<decltype(actc)::value>, dim3(g.grid), dim3(g.threads), shm, stream, (const bf16_t*)dA,
+                       lda, dacoff, (const bf16_t*)y, ldy, scale, shift, mean, rstd, partials, M, C, g.rpb, slope);
+  });
+  KOD_LAUNCH_CHECK(fn);
   return KOD_OK;
 }
 
@@ -866,75 +764,62 @@ int kodhip_bn_bwd_coeffs(const double* sums_local, const double* sums_global, do
   return KOD_OK;
 }
 
+static int bn_bwd_apply(const char* fn, const void* dA, int lda, int dacoff, void* y_inout, int ldy, const float* scale,
+                        const float* shift, const float* coef, void* dI, int ldi, int dicoff, int di_accum, long M, int C,
+                        int act, float slope, hipStream_t stream) {
+  KOD_CHECK_ARG(act >= ACT_SILU && act <= ACT_IDENTITY, "%s: activation code %d", fn, act);
+  KOD_CHECK_ARG(dA && y_inout && scale && shift && coef && M > 0, "%s: bad args", fn);
+  KOD_CHECK_ARG(C % 8 == 0 && C <= 2048 && lda % 8 == 0 && dacoff % 8 == 0 && dacoff + C <= lda, "%s: bad geometry", fn);
+  KOD_CHECK_ARG(!dI || (ldi % 8 == 0 && dicoff % 8 == 0 && dicoff + C <= ldi), "%s: bad identity slice", fn);
+  KOD_CHECK_ARG(ldy % 8 == 0 && ldy >= C, "%s: bad row stride of y", fn);
+  const ApplyShape a = apply_shape(M, C, true);
+  const Geo g = geo(M, C, a.cap, a.threads, a.u);
+  kod_with_act(act, [&](auto actc) {
+    constexpr int ACT = decltype(actc)::value;
+#define KOD_BAPPLY(UU, LL, TT) hipLaunchKernelGGL((bn_silu_bwd_apply_kernel<ACT, UU, LL, TT>), dim3(g.grid), dim3(g.threads), LL ? 5 * C * sizeof(float) : 0, stream, \
+                     (const bf16_t*)dA, lda, dacoff, (bf16_t*)y_inout, ldy, scale, shift, coef, (bf16_t*)dI, ldi, dicoff, di_accum, M, C, g.rpb, slope)
+    KOD_APPLY_DISPATCH(KOD_BAPPLY);
+#undef KOD_BAPPLY
+  });
+  KOD_LAUNCH_CHECK(fn);
+  return KOD_OK;
+}
+
+int kodhip_bn_silu_apply(const void* y, int ldy, const float* scale, const float* shift,
+                         const void* residual, int ldr, int rcoff,
+                         void* out, int ldo, int ocoff, long M, int C, hipStream_t stream) {
+  return bn_apply("bn_silu_apply", y, ldy, scale, shift, residual, ldr, rcoff, out, ldo, ocoff, M, C, ACT_SILU, 0.f, stream);
+}
+
+int kodhip_bn_silu_bwd_reduce(const void* dA, int lda, int dacoff, const void* y, int ldy, const float* scale,
+                              const float* shift, const float* mean, const float* rstd, float* partials,
+                              long M, int C, hipStream_t stream) {
+  return bn_bwd_reduce("bn_silu_bwd_reduce", dA, lda, dacoff, y, ldy, scale, shift, mean, rstd, partials, M, C, ACT_SILU, 0.f, stream);
+}
+
 int kodhip_bn_silu_bwd_apply(const void* dA, int lda, int dacoff, void* y_inout, int ldy, const float* scale,
                              const float* shift, const float* coef, void* dI, int ldi, int dicoff, int di_accum,
                              long M, int C, hipStream_t stream) {
-  KOD_CHECK_ARG(dA && y_inout && scale && shift && coef && M > 0, "bn_silu_bwd_apply: bad args");
-  KOD_CHECK_ARG(C % 8 == 0 && C <= 2048 && lda % 8 == 0 && dacoff % 8 == 0 && dacoff + C <= lda, "bn_silu_bwd_apply: bad geometry");
-  KOD_CHECK_ARG(!dI || (ldi % 8 == 0 && dicoff % 8 == 0 && dicoff + C <= ldi), "bn_silu_bwd_apply: bad identity slice");
-  const ApplyShape a = apply_shape(M, C, true);
-  Geo g = geo(M, C, a.cap, a.threads, a.u);
-  KOD_CHECK_ARG(ldy % 8 == 0 && ldy >= C, "bn_silu_bwd_apply: bad row stride of y");
-#define KOD_BAPPLY(UU, LL, TT) hipLaunchKernelGGL((bn_silu_bwd_apply_kernel<UU, LL, TT>), dim3(g.grid), dim3(g.threads), LL ? 5 * C * sizeof(float) : 0, stream, \
-                     (const bf16_t*)dA, lda, dacoff, (bf16_t*)y_inout, ldy, scale, shift, coef, (bf16_t*)dI, ldi, dicoff, di_accum, M, C, g.rpb)
-  KOD_APPLY_DISPATCH(KOD_BAPPLY);
-#undef KOD_BAPPLY
-  KOD_LAUNCH_CHECK("bn_silu_bwd_apply");
-  return KOD_OK;
+  return bn_bwd_apply("bn_silu_bwd_apply", dA, lda, dacoff, y_inout, ldy, scale, shift, coef, dI, ldi, dicoff, di_accum, M, C,
+                      ACT_SILU, 0.f, stream);
 }
-
-// ---- the same three passes for an activation other than SiLU (see bn_act_apply_kernel): act = 0 SiLU (the tuned kernels
-// above), 1 ReLU, 2 LeakyReLU(slope), 3 Hardswish, 4 identity (activation_layer=None).  Arguments as in the SiLU entries.
-#define KOD_ACT_DISPATCH(KERNEL, ...)                                                             \
-  switch (act) {                                                                                  \
-    case ACT_RELU: hipLaunchKernelGGL(KERNEL<ACT_RELU>, __VA_ARGS__); break;                      \
-    case ACT_LEAKY: hipLaunchKernelGGL(KERNEL<ACT_LEAKY>, __VA_ARGS__); break;                    \
-    case ACT_HARDSWISH: hipLaunchKernelGGL(KERNEL<ACT_HARDSWISH>, __VA_ARGS__); break;            \
-    default: hipLaunchKernelGGL(KERNEL<ACT_IDENTITY>, __VA_ARGS__); break;                        \
-  }
 
 int kodhip_bn_act_apply(const void* y, int ldy, const float* scale, const float* shift, const void* residual, int ldr, int rcoff,
                         void* out, int ldo, int ocoff, long M, int C, int act, float slope, hipStream_t stream) {
-  if (act == ACT_SILU) return kodhip_bn_silu_apply(y, ldy, scale, shift, residual, ldr, rcoff, out, ldo, ocoff, M, C, stream);
-  KOD_CHECK_ARG(act >= 1 && act <= 4, "bn_act_apply: activation code %d", act);
-  KOD_CHECK_ARG(y && scale && shift && out && M > 0, "bn_act_apply: bad args");
-  KOD_CHECK_ARG(C % 8 == 0 && C <= 2048 && ldo % 8 == 0 && ocoff % 8 == 0 && ocoff + C <= ldo && ldy % 8 == 0 && ldy >= C, "bn_act_apply: bad channel geometry");
-  KOD_CHECK_ARG(!residual || (ldr % 8 == 0 && rcoff % 8 == 0 && rcoff + C <= ldr), "bn_act_apply: bad residual slice");
-  Geo g = geo(M, C, (M * C * 2 >= (128l << 20)) ? 16384 : 4096);
-  KOD_ACT_DISPATCH(bn_act_apply_kernel, dim3(g.grid), dim3(g.threads), 0, stream, (const bf16_t*)y, ldy, scale, shift, (const bf16_t*)residual,
-                   ldr, rcoff, (bf16_t*)out, ldo, ocoff, M, C, g.rpb, slope)
-  KOD_LAUNCH_CHECK("bn_act_apply");
-  return KOD_OK;
-}
-
-int kodhip_bn_act_bwd_apply(const void* dA, int lda, int dacoff, void* y_inout, int ldy, const float* scale, const float* shift,
-                            const float* coef, void* dI, int ldi, int dicoff, int di_accum, long M, int C, int act, float slope,
-                            hipStream_t stream) {
-  if (act == ACT_SILU) return kodhip_bn_silu_bwd_apply(dA, lda, dacoff, y_inout, ldy, scale, shift, coef, dI, ldi, dicoff, di_accum, M, C, stream);
-  KOD_CHECK_ARG(act >= 1 && act <= 4, "bn_act_bwd_apply: activation code %d", act);
-  KOD_CHECK_ARG(dA && y_inout && scale && shift && coef && M > 0, "bn_act_bwd_apply: bad args");
-  KOD_CHECK_ARG(C % 8 == 0 && C <= 2048 && lda % 8 == 0 && dacoff % 8 == 0 && dacoff + C <= lda && ldy % 8 == 0 && ldy >= C, "bn_act_bwd_apply: bad geometry");
-  KOD_CHECK_ARG(!dI || (ldi % 8 == 0 && dicoff % 8 == 0 && dicoff + C <= ldi), "bn_act_bwd_apply: bad identity slice");
-  Geo g = geo(M, C, (M * C * 2 >= (128l << 20)) ? 16384 : 4096);
-  KOD_ACT_DISPATCH(bn_act_bwd_apply_kernel, dim3(g.grid), dim3(g.threads), 0, stream, (const bf16_t*)dA, lda, dacoff, (bf16_t*)y_inout, ldy,
-                   scale, shift, coef, (bf16_t*)dI, ldi, dicoff, di_accum, M, C, g.rpb, slope)
-  KOD_LAUNCH_CHECK("bn_act_bwd_apply");
-  return KOD_OK;
+  return bn_apply("bn_act_apply", y, ldy, scale, shift, residual, ldr, rcoff, out, ldo, ocoff, M, C, act, slope, stream);
 }
 
 int kodhip_bn_act_bwd_reduce(const void* dA, int lda, int dacoff, const void* y, int ldy, const float* scale, const float* shift,
                              const float* mean, const float* rstd, float* partials, long M, int C, int act, float slope,
                              hipStream_t stream) {
-  if (act == ACT_SILU) return kodhip_bn_silu_bwd_reduce(dA, lda, dacoff, y, ldy, scale, shift, mean, rstd, partials, M, C, stream);
-  KOD_CHECK_ARG(act >= 1 && act <= 4, "bn_act_bwd_reduce: activation code %d", act);
-  KOD_CHECK_ARG(dA && y && scale && shift && mean && rstd && partials && M > 0, "bn_act_bwd_reduce: bad args");
-  KOD_CHECK_ARG(C % 8 == 0 && C <= 2048 && lda % 8 == 0 && dacoff % 8 == 0 && dacoff + C <= lda && ldy % 8 == 0 && ldy >= C, "bn_act_bwd_reduce: bad geometry");
-  Geo g = geo(M, C, bwd_reduce_blocks(M, C));
-  const size_t shm = (size_t)g.rpb * (C / 8) * 16 * sizeof(float);
-  KOD_ACT_DISPATCH(bn_act_bwd_reduce_kernel, dim3(g.grid), dim3(g.threads), shm, stream, (const bf16_t*)dA, lda, dacoff, (const bf16_t*)y, ldy,
-                   scale, shift, mean, rstd, partials, M, C, g.rpb, slope)
-  KOD_LAUNCH_CHECK("bn_act_bwd_reduce");
-  return KOD_OK;
+  return bn_bwd_reduce("bn_act_bwd_reduce", dA, lda, dacoff, y, ldy, scale, shift, mean, rstd, partials, M, C, act, slope, stream);
+}
+
+int kodhip_bn_act_bwd_apply(const void* dA, int lda, int dacoff, void* y_inout, int ldy, const float* scale, const float* shift,
+                            const float* coef, void* dI, int ldi, int dicoff, int di_accum, long M, int C, int act, float slope,
+                            hipStream_t stream) {
+  return bn_bwd_apply("bn_act_bwd_apply", dA, lda, dacoff, y_inout, ldy, scale, shift, coef, dI, ldi, dicoff, di_accum, M, C,
+                      act, slope, stream);
 }
 
 }  // extern "C"

@@ -104,19 +104,13 @@ struct ConvArgs {
   float slope;
 };
 
-// act(z) of the fused forward epilogue: SiLU as kodhip_bn_silu_apply forms it, the others as kod_act<> does
-template <int ACT> __device__ __forceinline__ float fused_act(float z, float slope) {
-  if constexpr (ACT == ACT_SILU) return z * kod_sigmoid_l2(KOD_NEG_LOG2E * z);
-  else return kod_act<ACT>(z, slope);
-}
-
 // One accumulator quad (4 consecutive channels of one pixel) through BatchNorm + activation: z = fma(S, scale, shift) on the
 // fp32 accumulator, ONE rounding to bf16
 template <int ACT>
 __device__ __forceinline__ bf16x4 fused_quad(const f32x16& acc, int g, const f32x4& sc, const f32x4& sh, float slope) {
   bf16x4 v;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = (bf16_t)fused_act<ACT>(__builtin_fmaf(acc[g * 4 + e], sc[e], sh[e]), slope);
+  for (int e = 0; e < 4; ++e) v[e] = (bf16_t)kod_act<ACT>(__builtin_fmaf(acc[g * 4 + e], sc[e], sh[e]), slope);
   return v;
 }
 
@@ -835,10 +829,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bid
             }
         };
         if constexpr (MODE == MODE_FUSED) stage(std::integral_constant<int, ACT_SILU>{});
-        else if (a.act == ACT_RELU) stage(std::integral_constant<int, ACT_RELU>{});
-        else if (a.act == ACT_LEAKY) stage(std::integral_constant<int, ACT_LEAKY>{});
-        else if (a.act == ACT_HARDSWISH) stage(std::integral_constant<int, ACT_HARDSWISH>{});
-        else stage(std::integral_constant<int, ACT_IDENTITY>{});
+        else kod_with_act<false>(a.act, stage);
       } else {
 #pragma unroll
       for (int i = 0; i < TN; ++i)
@@ -1202,10 +1193,7 @@ __device__ __forceinline__ void conv_stem_fwd_body(const ConvArgs& a) {
         }
       };
       if constexpr (MODE == MODE_FUSED) stage(std::integral_constant<int, ACT_SILU>{});
-      else if (a.act == ACT_RELU) stage(std::integral_constant<int, ACT_RELU>{});
-      else if (a.act == ACT_LEAKY) stage(std::integral_constant<int, ACT_LEAKY>{});
-      else if (a.act == ACT_HARDSWISH) stage(std::integral_constant<int, ACT_HARDSWISH>{});
-      else stage(std::integral_constant<int, ACT_IDENTITY>{});
+      else kod_with_act<false>(a.act, stage);
     } else {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
 
 typedef __bf16 bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -68,15 +69,39 @@ __device__ __forceinline__ float kod_silu_bwd(float g, float z, float sg) {
   return g * __builtin_fmaf(sg, t, sg);
 }
 
-// The activation slot of a conv+BN+act unit (`act` of the C ABI), shared by the plain passes of bn_act.hip and the fused
-// forward epilogue of conv_igemm.hip.  SiLU is formed by its callers as z * kod_sigmoid_l2(KOD_NEG_LOG2E * z); the others
-// follow torch's conventions at the kinks (see bn_act.hip).
+// The activation slot of a conv+BN+act unit (`act` of the C ABI): one template parameter of the three BatchNorm passes
+// of bn_act.hip and of the fused forward epilogue of conv_igemm.hip.  The reference's layers take any activation callable
+// (kod/nn/layers/csp.py:16-46, sppf.py:14-27, networks/yolov5.py:40-50) and its configs only ever use SiLUInplace; the others
+// are the elementwise activations torch offers for the slot - ReLU, LeakyReLU(slope), Hardswish, Identity
+// (activation_layer=None) - with torch's conventions at the kinks (aten/native/cpu/Activation.cpp: relu'(0) = 0, leaky_relu'
+// uses x > 0, hardswish' = 0 up to -3, x / 3 + 0.5 inside (-3, 3), 1 from 3 on).
 enum { ACT_SILU = 0, ACT_RELU = 1, ACT_LEAKY = 2, ACT_HARDSWISH = 3, ACT_IDENTITY = 4 };
 template <int ACT> __device__ __forceinline__ float kod_act(float z, float slope) {
+  if (ACT == ACT_SILU) return z * kod_sigmoid_l2(KOD_NEG_LOG2E * z);
   if (ACT == ACT_RELU) return z > 0.f ? z : 0.f;
   if (ACT == ACT_LEAKY) return z > 0.f ? z : z * slope;
   if (ACT == ACT_HARDSWISH) return z * fminf(fmaxf(z + 3.f, 0.f), 6.f) / 6.f;
   return z;
+}
+// g * act'(z)
+template <int ACT> __device__ __forceinline__ float kod_act_bwd(float g, float z, float slope) {
+  if (ACT == ACT_SILU) return kod_silu_bwd(g, z, kod_sigmoid_l2(KOD_NEG_LOG2E * z));
+  if (ACT == ACT_RELU) return z > 0.f ? g : 0.f;
+  if (ACT == ACT_LEAKY) return z > 0.f ? g : g * slope;
+  if (ACT == ACT_HARDSWISH) return z <= -3.f ? 0.f : (z < 3.f ? g * ((z / 3.f) + 0.5f) : g);     // (torch 2.x: 0 at -3, g at 3)
+  return g;
+}
+// Runtime `act` -> compile-time constant: calls f(std::integral_constant<int, ACT_*>{}) for the code `act` holds (anything
+// past Hardswish is the identity: entry points validate the range).  On the host it picks a kernel instance, on the device
+// it is a block-uniform switch.  SILU = false: the caller never holds ACT_SILU here and gets no instance for it.
+template <bool SILU = true, typename F> __host__ __device__ __forceinline__ void kod_with_act(int act, F&& f) {
+  if constexpr (SILU) {
+    if (act == ACT_SILU) return f(std::integral_constant<int, ACT_SILU>{});
+  }
+  if (act == ACT_RELU) f(std::integral_constant<int, ACT_RELU>{});
+  else if (act == ACT_LEAKY) f(std::integral_constant<int, ACT_LEAKY>{});
+  else if (act == ACT_HARDSWISH) f(std::integral_constant<int, ACT_HARDSWISH>{});
+  else f(std::integral_constant<int, ACT_IDENTITY>{});
 }
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -91,7 +91,7 @@ class Engine(ArenaMixin, BufferMixin, ForwardMixin, BackwardMixin):
 
     def set_activation(self, kind: int, slope: float = 0.0):
         """The conv units' activation (nn/graph_module.activation_code), to be set before the arenas are built.  Anything but
-        SiLU runs on the plain elementwise passes (kodhip_bn_act_*): the fused forms that carry SiLU's arithmetic - the
+        SiLU runs the elementwise passes (kodhip_bn_act_*) only: the fused forms that carry SiLU's arithmetic - the
         BatchNorm-backward reduction in the data gradients' epilogue, the fused stem backward - are off."""
         import dataclasses
         self.act_kind, self.act_slope = int(kind), float(slope)

@@ -56,9 +56,9 @@ ACT_SILU, ACT_RELU, ACT_LEAKY, ACT_HARDSWISH, ACT_IDENTITY = 0, 1, 2, 3, 4      
 
 def activation_code(activation_layer):
     """(code, negative slope) of the elementwise activation an `activation_layer` callable builds (torchvision's
-    Conv2dNormActivation semantics: None = no activation).  SiLU - the reference's only configured choice - runs on the
-    tuned kernels and fused epilogues; ReLU / LeakyReLU / Hardswish / identity on the plain passes (csrc/bn_act.hip
-    bn_act_*); anything else is refused rather than silently replaced."""
+    Conv2dNormActivation semantics: None = no activation).  SiLU - the reference's only configured choice - takes the
+    fused epilogues as well; ReLU / LeakyReLU / Hardswish / identity run the same elementwise kernels (csrc/bn_act.hip:
+    the activation is their template parameter) without them; anything else is refused rather than silently replaced."""
     if activation_layer is None:
         return ACT_IDENTITY, 0.0
     probe = activation_layer()

@@ -208,3 +208,88 @@ def relerr_bound(kind: int, z: torch.Tensor) -> torch.Tensor:
     if kind == SILU:
         return (sigmoid_rel_err(z) + U32) * torch.sigmoid(z.double()) * z.double().abs()
     return (4 if kind == HARDSWISH else 1) * U32 * z.double().abs()     # z*clamp(z+3)/6: three roundings; leaky: z*slope
+
+
+# ---------------------------------------------------------------- fp32 restatement of the elementwise kernels (acts 1 - 4)
+# ReLU, LeakyReLU, Hardswish and identity use only IEEE operations (the library is built without fast-math and without
+# contraction), so the apply and backward-apply passes can be restated operation by operation in fp32 and compared
+# bit for bit (tests/test_hip_bn_act_exact.py).  SiLU (hardware exp2 / rcp) is not restated.
+def _round_fraction_f32(v) -> float:
+    """Exact rational -> nearest fp32, ties to even."""
+    import numpy as np
+    f = np.float32(float(v))
+    from fractions import Fraction
+    best = None
+    for c in (np.nextafter(f, np.float32(-np.inf)), f, np.nextafter(f, np.float32(np.inf))):
+        d = abs(Fraction(float(c)) - v)
+        even = (int(np.float32(c).view(np.int32)) & 1) == 0
+        if best is None or d < best[0] or (d == best[0] and even and not best[2]):
+            best = (d, float(c), even)
+    return best[1]
+
+
+FMA_SLOW = [0]            # elements that took the exact path (tests report it)
+
+
+def fma32(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """fmaf(a, b, c) on fp32 tensors: one rounding.  a*b is exact in fp64 (48-bit product); where the fp64 sum with c is
+    exact too (TwoSum residual zero) its rounding to fp32 is the fma's.  Every other element is recomputed exactly with
+    fractions.Fraction - no element is left out."""
+    from fractions import Fraction
+    a, b, c = torch.broadcast_tensors(a.float(), b.float(), c.float())
+    p, cd = a.double() * b.double(), c.double()
+    s = p + cd
+    bb = s - p
+    resid = (p - (s - bb)) + (cd - bb)
+    out = s.float()
+    idx = (resid != 0).nonzero(as_tuple=False)
+    if idx.numel():
+        out = out.clone()
+        FMA_SLOW[0] += idx.shape[0]
+        for i in idx.tolist():
+            i = tuple(i)
+            v = Fraction(a[i].item()) * Fraction(b[i].item()) + Fraction(c[i].item())
+            out[i] = _round_fraction_f32(v)
+    return out
+
+
+def act32(kind: int, z: torch.Tensor, slope: float = 0.0) -> torch.Tensor:
+    """kod_act<> in fp32, in the kernel's operation order."""
+    z = z.float()
+    if kind == RELU:
+        return torch.where(z > 0, z, torch.zeros_like(z))
+    if kind == LEAKY:
+        return torch.where(z > 0, z, z * torch.tensor(slope, dtype=torch.float32))
+    if kind == HARDSWISH:
+        return z * torch.clamp(z + 3.0, 0.0, 6.0) / 6.0
+    assert kind == IDENTITY, kind
+    return z
+
+
+def act_bwd32(kind: int, g: torch.Tensor, z: torch.Tensor, slope: float = 0.0) -> torch.Tensor:
+    """kod_act_bwd<> (g * act'(z)) in fp32, in the kernel's operation order."""
+    g, z = g.float(), z.float()
+    if kind == RELU:
+        return torch.where(z > 0, g, torch.zeros_like(g))
+    if kind == LEAKY:
+        return torch.where(z > 0, g, g * torch.tensor(slope, dtype=torch.float32))
+    if kind == HARDSWISH:
+        return torch.where(z <= -3, torch.zeros_like(g), torch.where(z < 3, g * ((z / 3.0) + 0.5), g))
+    assert kind == IDENTITY, kind
+    return g
+
+
+def apply32(y, scale, shift, kind, slope=0.0, residual=None) -> torch.Tensor:
+    """The forward apply pass: z = fma(y, scale, shift), kod_act, + r, one rounding to bf16.  y / residual bf16 [M, C]."""
+    a = act32(kind, fma32(y.float(), scale, shift), slope)
+    if residual is not None:
+        a = a + residual.float()
+    return a.to(torch.bfloat16)
+
+
+def bwd_apply32(dA, y, scale, shift, coef, kind, slope=0.0) -> torch.Tensor:
+    """The backward apply pass: dY = fma(k1, dz, fma(k2, y, k3)), dz = kod_act_bwd(dA, fma(y, scale, shift)); bf16."""
+    C = y.shape[1]
+    yv = y.float()
+    dz = act_bwd32(kind, dA.float(), fma32(yv, scale, shift), slope)
+    return fma32(coef[:C], dz, fma32(coef[C:2 * C], yv, coef[2 * C:])).to(torch.bfloat16)

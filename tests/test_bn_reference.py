@@ -130,3 +130,68 @@ def test_error_model_bounds_fp32_sums():
     rm32 = R.f32(R.f32(0.97 * rm0.double()) + R.f32(0.03 * R.f32(m32)))
     rv32 = R.f32(R.f32(0.97 * rv0.double()) + R.f32(0.03 * unb32))
     assert ((rm32 - rm).abs() <= drm).all() and ((rv32 - rv).abs() <= drv).all()
+
+
+def _bf(t):
+    return t.to(torch.bfloat16).float()
+
+
+def test_fma32_is_one_rounding():
+    """fma32 on operands built to need the exact path - sums that fp64 cannot hold, one of them landing on an fp32
+    midpoint after fp64's rounding (the double-rounding case) - against expected values worked out by hand, and on
+    random operands against the definition of round-to-nearest-even, checked in exact rational arithmetic without the
+    rounding helper fma32 itself uses."""
+    import numpy as np
+    from fractions import Fraction
+    e = 2.0 ** -23
+    # (1 + e)^2 + 2^24 = 2^24 + 1 + 2^-22 + 2^-46: just above the midpoint 2^24 + 1 (fp32 spacing 2 there)  -> 2^24 + 2
+    # (1 + e)(1 - e) + 2^30 = 2^30 + 1 - 2^-46: fp32 spacing 128 there                                       -> 2^30
+    # (1 + e)(1 - e) + (2^24 + 2) = 2^24 + 3 - 2^-46: fp64 rounds it ONTO the midpoint 2^24 + 3, from which ties-to-even
+    #   would go up to 2^24 + 4; the exact value lies below the midpoint                                     -> 2^24 + 2
+    a = torch.tensor([1 + e, 1 + e, 1 + e]); b = torch.tensor([1 + e, 1 - e, 1 - e]); c = torch.tensor([2.0 ** 24, 2.0 ** 30, 2.0 ** 24 + 2])
+    slow0 = R.FMA_SLOW[0]
+    got = R.fma32(a, b, c)
+    assert R.FMA_SLOW[0] == slow0 + 3                             # all three took the exact path
+    assert got.tolist() == [2.0 ** 24 + 2, 2.0 ** 30, 2.0 ** 24 + 2]
+    g = torch.Generator().manual_seed(1)
+    a, b, c = (torch.randn(300, generator=g) * s for s in (1.0, 1.0, 1e-3))
+    got = R.fma32(a, b, c)
+    for i in range(a.numel()):
+        v = Fraction(a[i].item()) * Fraction(b[i].item()) + Fraction(c[i].item())
+        r = np.float32(got[i].item())
+        d = abs(Fraction(float(r)) - v)
+        for nb in (np.nextafter(r, np.float32(-np.inf)), np.nextafter(r, np.float32(np.inf))):
+            dn = abs(Fraction(float(nb)) - v)
+            assert d < dn or (d == dn and int(r.view(np.int32)) % 2 == 0), i
+
+
+@pytest.mark.parametrize("kind,slope", ACTS[1:])
+@pytest.mark.parametrize("res", [False, True])
+def test_fp32_restatement_within_the_fp64_reference(kind, slope, res):
+    """apply32 / bwd_apply32 against this file's fp64 reference, kinks 0, -3 and 3 included: the fp32 restatement
+    differs from the exact value by the activation's fp32 error (relerr_bound), one fma rounding of z carried through
+    the activation's Lipschitz constant, the add and the bf16 rounding."""
+    g = torch.Generator().manual_seed(11 + kind)
+    M, C = 64, 8
+    y = _bf(torch.randn(M, C, generator=g) * 3)
+    scale = _bf(torch.rand(C, generator=g) + 0.5); shift = _bf(torch.randn(C, generator=g))
+    y[0] = _bf((torch.tensor([0.0, -3.0, 3.0, 0.0, -3.0, 3.0, 1.0, -1.0]) - shift) / scale)   # near the kinks
+    scale[:3] = 1.0; shift[:3] = 0.0; y[1, :3] = torch.tensor([0.0, -3.0, 3.0])              # exactly on them
+    resid = _bf(torch.randn(M, C, generator=g)) if res else None
+    z = y.double() * scale.double() + shift.double()
+    want = R.act(kind, z, slope) + (resid.double() if res else 0.0)
+    got = R.apply32(y.bfloat16(), scale, shift, kind, slope, resid.bfloat16() if res else None).double()
+    L = R.act_lipschitz(kind, slope)
+    pre = R.relerr_bound(kind, z) + L * R.ulp32(z) + R.ulp32(want)
+    assert ((got - want).abs() <= pre + R.ulpbf16(want) / 2 + R.ulpbf16(pre)).all()
+    # backward: dz exact up to the side of a kink z's rounding fell on (none here: z is exact in fp32 for these operands
+    # except by one rounding, and the kink rows are exact), then two fmas
+    dA = _bf(torch.randn(M, C, generator=g))
+    coef = _bf(torch.randn(3 * C, generator=g))
+    z32 = R.fma32(y, scale, shift)
+    dz = dA.double() * R.act_grad(kind, z32.double(), slope)
+    wantb = coef[:C].double() * dz + coef[C:2 * C].double() * y.double() + coef[2 * C:].double()
+    gotb = R.bwd_apply32(dA.bfloat16(), y.bfloat16(), scale, shift, coef, kind, slope).double()
+    mag = (coef[:C].double() * dz).abs() + (coef[C:2 * C].double() * y.double()).abs() + coef[2 * C:].double().abs()
+    preb = 6 * R.U32 * mag
+    assert ((gotb - wantb).abs() <= preb + R.ulpbf16(wantb) / 2 + R.ulpbf16(preb)).all()

@@ -244,7 +244,7 @@ def _all_eval(m):
 @pytest.mark.parametrize("mix", ["all_eval", "short_eval", "relu_all_eval", "backbone_all_eval"])
 def test_modules_with_eval_batchnorm(mix):
     """CSPLayer with every unit eval / short_conv eval beside a train-mode main_conv (the paired coefficient launch with a
-    mode per job) / ReLU (the plain elementwise passes); the backbone module with every unit eval, its stem included (the stem's fused backward on eval-mode coefficients)."""
+    mode per job) / ReLU (the elementwise passes without the fused SiLU forms); the backbone module with every unit eval, its stem included (the stem's fused backward on eval-mode coefficients)."""
     from object_detection_cib_amd.nn.layers.csp import CSPLayer
     from object_detection_cib_amd.nn.backbones.yolov5 import StageConfig, Yolov5Backbone
     if mix.startswith("backbone"):

@@ -130,8 +130,8 @@ def _swap_activation(module, make):
 @pytest.mark.parametrize("act", ["relu", "leaky", "hardswish", "none"])
 def test_layers_with_other_activations(act):
     """`activation_layer` other than SiLU (kod/nn/layers/csp.py:16-46, sppf.py:14-27 take any callable): ReLU, LeakyReLU(0.1),
-    Hardswish and None (torchvision's Conv2dNormActivation: no activation) through the plain elementwise passes
-    (csrc/bn_act.hip bn_act_*; the fused SiLU epilogues are off for such a module) - a CSP layer with two blocks and an SPPF
+    Hardswish and None (torchvision's Conv2dNormActivation: no activation) through the elementwise passes instantiated for them
+    (csrc/bn_act.hip, kodhip_bn_act_*; the fused SiLU epilogues are off for such a module) - a CSP layer with two blocks and an SPPF
     block, forward, input gradient and parameter gradients against the oracle modules with the same activation."""
     make = {"relu": torch.nn.ReLU, "leaky": lambda: torch.nn.LeakyReLU(0.1), "hardswish": torch.nn.Hardswish, "none": None}[act]
     x = torch.randn(4, 64, 24, 40, generator=torch.Generator().manual_seed(31))
