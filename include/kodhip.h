@@ -144,8 +144,7 @@ int kodhip_conv_dgrad_dual_bnred(const void* dy1, const void* w1, const void* dy
 int kodhip_conv_plan_query(int op, int B, int H, int W, int ldx, int xcoff, int Cin,
                            int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
                            int ldy, int ycoff, int* out);
-int kodhip_conv_wgrad_splits(long M, int N, int Kp);     /* generic split-K kernel */
-/* split count of the kernel kodhip_conv_wgrad picks for this geometry (3x3 / stride 1 / pad 1 layers with whole
+/* Slab count of the kernel kodhip_conv_wgrad picks for this geometry (3x3 / stride 1 / pad 1 layers with whole
  * 32-channel chunks take a form that stages dY once per block and every input row once per kernel row): size the slab
  * region with this one.  H, W: input dims; ldx / ldy: row strides of x / dy in elements. */
 int kodhip_conv_wgrad_splits_geo(int B, int H, int W, int ldx, int Cin, int N, int KH, int KW, int SH, int SW, int PH, int PW,

@@ -55,7 +55,6 @@ SIGNATURES = {
     "kodhip_conv_dgrad_dual_bnred_slots": (i32, [i32] * 6),
     "kodhip_conv_dgrad_dual_bnred": (i32, [vp, vp, vp, vp, vp] + [i32] * 11 + [vp, vp, i32, i32, vp]),
     "kodhip_conv_plan_query": (i32, [i32] * 17 + [vp]),
-    "kodhip_conv_wgrad_splits": (i32, [i64, i32, i32]),
     "kodhip_conv_wgrad_splits_geo": (i32, [i32] * 14),
     "kodhip_conv_wgrad": (i32, [vp, vp, vp, vp] + [i32] * 18 + [f32, vp]),
     "kodhip_conv_wgrad_plan_query": (i32, [i32] * 15 + [vp]),

@@ -743,119 +743,93 @@ __global__ __launch_bounds__(64 * WN * 3 * WC) void conv_wgrad_row3_kernel(Wgrad
 }
 
 // grad[n][ci][kh][kw] = scale * sum_s part[s][n][k(kh,kw,ci)]   (stem: k = (kh, kw', dx, c4), see pack)
-// block = RK consecutive k x RL split lanes (RK * RL = 256): each lane streams RK*4-byte contiguous pieces of its
-// slabs with four independent partial sums (loads in flight), fixed-order LDS combine => deterministic.
+// block = 32 consecutive k (V = 1) or k quads (V = 4) x RED_L split lanes (256 threads): each lane streams contiguous pieces of
+// its slabs with four independent partial sums (loads in flight), fixed-order LDS combine => deterministic.
+// V = 4: 16-byte accesses, a thread owns FOUR consecutive k of one slab row (K and Kp are multiples of 4, so a quad never
+// crosses rows) for its split lane.  Per (n, k) the additions and their order are the same for both V (four chains over the
+// lane's splits, (s0 + s1) + (s2 + s3), then the eight lanes in order) => bit-identical gradients; V = 4 has a quarter of the
+// load instructions and 4 x the bytes in flight per thread.  Unaligned operands take V = 1.
 constexpr int RED_K = 32, RED_L = 8;    // measured: 16x16 0.65 ms, 32x8 0.45 ms, 64x4 0.50 ms, 128x2 0.71 ms per step
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* part, float* grad, int splits, int Nfull,
-                                                           int N, int K, int Kp, int Cin, int KK, int stem,
-                                                           float scale, float* grad2 = nullptr, int n_first = 1 << 30) {
-  __shared__ float sm[RED_L][RED_K + 1];
-  const int kx = threadIdx.x % RED_K, sl = threadIdx.x / RED_K;
-  const long idx = (long)blockIdx.x * RED_K + kx;
-  const long total = (long)N * K;
-  float s = 0.f;
-  int n = 0, k = 0;
-  if (idx < total) {
-    n = (int)(idx / K);
-    k = (int)(idx - (long)n * K);
-    const float* p = part + (size_t)n * Kp + k;
-    const size_t slab = (size_t)Nfull * Kp;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int i = sl;
-    for (; i + 3 * RED_L < splits; i += 4 * RED_L) {
-      s0 += p[(size_t)i * slab];
-      s1 += p[(size_t)(i + RED_L) * slab];
-      s2 += p[(size_t)(i + 2 * RED_L) * slab];
-      s3 += p[(size_t)(i + 3 * RED_L) * slab];
-    }
-    for (; i < splits; i += RED_L) s0 += p[(size_t)i * slab];
-    s = (s0 + s1) + (s2 + s3);
-  }
-  sm[sl][kx] = s;
-  __syncthreads();
-  if (sl == 0 && idx < total) {
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < RED_L; ++i) t += sm[i][kx];
-    if (stem) {
-      // k = (kh*3 + kwp)*8 + dx*4 + c, real weight [n][c(3)][kh(6)][kw = 2*kwp+dx (6)]
-      int c = k & 3, dx = (k >> 2) & 1, tt = k >> 3;
-      int kh = tt / 3, kwp = tt - kh * 3;
-      if (c < 3) grad[(size_t)n * 108 + c * 36 + kh * 6 + 2 * kwp + dx] = t * scale;
-    } else {
-      int tap = k / Cin;
-      int ci = k - tap * Cin;
-      float* dst = n >= n_first ? grad2 : grad;          // dual form: slab rows n_first .. belong to the second layer
-      if (n >= n_first) n -= n_first;
-      dst[(size_t)n * Cin * KK + ci * KK + tap] = t * scale;
-    }
+constexpr int RED_Q = 32;                // k quads per block (128 consecutive k)
+
+template <int V> struct RedVec { typedef float type; };
+template <> struct RedVec<4> { typedef f32x4 type; };
+template <int V>
+__device__ __forceinline__ typename RedVec<V>::type red_load(const float* p) {
+  if constexpr (V == 4) return kod_load_once<f32x4>(p);
+  else return *p;
+}
+
+// one summed element into the fp32 gradient: the stem's un-permute or [n][ci][tap]
+__device__ __forceinline__ void wgrad_scatter(float* dst, int n, int k, int Cin, int KK, int stem, float v) {
+  if (stem) {
+    // k = (kh*3 + kwp)*8 + dx*4 + c, real weight [n][c(3)][kh(6)][kw = 2*kwp+dx (6)]
+    const int c = k & 3, dx = (k >> 2) & 1, tt = k >> 3;
+    const int kh = tt / 3, kwp = tt - kh * 3;
+    if (c < 3) dst[(size_t)n * 108 + c * 36 + kh * 6 + 2 * kwp + dx] = v;
+  } else {
+    const int tap = k / Cin;
+    const int ci = k - tap * Cin;
+    dst[(size_t)n * Cin * KK + ci * KK + tap] = v;
   }
 }
 
-// The same reduction with 16-byte accesses: a thread owns FOUR consecutive k of one slab row (K and Kp are multiples of 4, so
-// a quad never crosses rows) for its split lane; per (n, k) the additions and their order are exactly wgrad_reduce_kernel's
-// (four chains over the lane's splits, (s0 + s1) + (s2 + s3), then the eight lanes in order) => bit-identical gradients,
-// a quarter of the load instructions and 4 x the bytes in flight per thread.  Unaligned operands take the scalar kernel.
-constexpr int RED_Q = 32;                // k quads per block (128 consecutive k)
-__global__ __launch_bounds__(256) void wgrad_reduce_v4_kernel(const float* part, float* grad, int splits, int Nfull,
-                                                              int N, int K, int Kp, int Cin, int KK, int stem,
-                                                              float scale, float* grad2 = nullptr, int n_first = 1 << 30) {
-  __shared__ f32x4 sm[RED_L][RED_Q];
-  const int qx = threadIdx.x % RED_Q, sl = threadIdx.x / RED_Q;
-  const int KQ = K >> 2;
-  const long q = (long)blockIdx.x * RED_Q + qx;
-  const long total = (long)N * KQ;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+template <int V>
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* part, float* grad, int splits, int Nfull, int N, int K,
+                                                           int Kp, int Cin, int KK, int stem, float scale, float* grad2,
+                                                           int n_first) {
+  typedef typename RedVec<V>::type T;
+  constexpr int RED_X = V == 4 ? RED_Q : RED_K;
+  __shared__ T sm[RED_L][V == 4 ? RED_X : RED_X + 1];
+  const int qx = threadIdx.x % RED_X, sl = threadIdx.x / RED_X;
+  const int KV = K / V;
+  const long q = (long)blockIdx.x * RED_X + qx;
+  const long total = (long)N * KV;
+  T s = {};
   int n = 0, k = 0;
   if (q < total) {
-    n = (int)(q / KQ);
-    k = (int)(q - (long)n * KQ) * 4;
+    n = (int)(q / KV);
+    k = (int)(q - (long)n * KV) * V;
     const float* p = part + (size_t)n * Kp + k;
     const size_t slab = (size_t)Nfull * Kp;
-    f32x4 s0 = s, s1 = s, s2 = s, s3 = s;
+    T s0 = s, s1 = s, s2 = s, s3 = s;
     int i = sl;
     for (; i + 3 * RED_L < splits; i += 4 * RED_L) {
-      const f32x4 a0 = kod_load_once<f32x4>(p + (size_t)i * slab);
-      const f32x4 a1 = kod_load_once<f32x4>(p + (size_t)(i + RED_L) * slab);
-      const f32x4 a2 = kod_load_once<f32x4>(p + (size_t)(i + 2 * RED_L) * slab);
-      const f32x4 a3 = kod_load_once<f32x4>(p + (size_t)(i + 3 * RED_L) * slab);
+      const T a0 = red_load<V>(p + (size_t)i * slab);
+      const T a1 = red_load<V>(p + (size_t)(i + RED_L) * slab);
+      const T a2 = red_load<V>(p + (size_t)(i + 2 * RED_L) * slab);
+      const T a3 = red_load<V>(p + (size_t)(i + 3 * RED_L) * slab);
       s0 += a0; s1 += a1; s2 += a2; s3 += a3;
     }
-    for (; i < splits; i += RED_L) s0 += kod_load_once<f32x4>(p + (size_t)i * slab);
+    for (; i < splits; i += RED_L) s0 += red_load<V>(p + (size_t)i * slab);
     s = (s0 + s1) + (s2 + s3);
   }
   sm[sl][qx] = s;
   __syncthreads();
   if (sl == 0 && q < total) {
-    f32x4 t = {0.f, 0.f, 0.f, 0.f};
+    T t = {};
 #pragma unroll
     for (int i = 0; i < RED_L; ++i) t += sm[i][qx];
     float* dst = n >= n_first ? grad2 : grad;            // dual form: slab rows n_first .. belong to the second layer
     if (n >= n_first) n -= n_first;
+    if constexpr (V == 4) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int kk = k + e;
-      if (stem) {
-        const int c = kk & 3, dx = (kk >> 2) & 1, tt = kk >> 3;
-        const int kh = tt / 3, kwp = tt - kh * 3;
-        if (c < 3) dst[(size_t)n * 108 + c * 36 + kh * 6 + 2 * kwp + dx] = t[e] * scale;
-      } else {
-        const int tap = kk / Cin;
-        const int ci = kk - tap * Cin;
-        dst[(size_t)n * Cin * KK + ci * KK + tap] = t[e] * scale;
-      }
+      for (int e = 0; e < 4; ++e) wgrad_scatter(dst, n, k + e, Cin, KK, stem, t[e] * scale);
+    } else {
+      wgrad_scatter(dst, n, k, Cin, KK, stem, t * scale);
     }
   }
 }
 
+// grad2 / n_first: the dual form's second layer (nullptr / 1 << 30: one layer)
 static int launch_wgrad_reduce(const float* part, float* grad, int splits, int Nfull, int N, int K, int Kp, int Cin, int KK,
                                int stem, float scale, float* grad2, int n_first, hipStream_t stream) {
   if (K % 4 == 0 && Kp % 4 == 0 && (reinterpret_cast<uintptr_t>(part) & 15) == 0)
-    hipLaunchKernelGGL(wgrad_reduce_v4_kernel, dim3(cdiv((long)N * (K >> 2), RED_Q)), dim3(256), 0, stream, part, grad, splits, Nfull, N, K,
-                       Kp, Cin, KK, stem, scale, grad2, n_first);
+    hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3(cdiv((long)N * (K >> 2), RED_Q)), dim3(256), 0, stream, part, grad, splits, Nfull, N,
+                       K, Kp, Cin, KK, stem, scale, grad2, n_first);
   else
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv((long)N * K, RED_K)), dim3(256), 0, stream, part, grad, splits, Nfull, N, K, Kp, Cin,
-                       KK, stem, scale, grad2, n_first);
+    hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3(cdiv((long)N * K, RED_K)), dim3(256), 0, stream, part, grad, splits, Nfull, N, K, Kp,
+                       Cin, KK, stem, scale, grad2, n_first);
   KOD_LAUNCH_CHECK("wgrad_reduce");
   return KOD_OK;
 }
@@ -869,36 +843,146 @@ static int launch_wgrad_reduce(const float* part, float* grad, int splits, int N
 constexpr int WGRAD_STAGES = WG_NST;     // LDS ring depth
 constexpr int WGRAD_ROWS = WG_RS;        // reduction rows per ring stage
 
+// ---- the launch plan: ONE place decides a layer's weight-gradient launch ------------------------------------------------
+// The launchers (kodhip_conv_wgrad, kodhip_conv_wgrad_dual), the slab-sizing queries (kodhip_conv_wgrad_splits_geo,
+// kodhip_conv_wgrad_dual_splits) and kodhip_conv_wgrad_plan_query all read wgrad_plan(); the stem's fused backward and its block
+// query read stem_bwd_plan().  engine/buffers.py sizes the shared slab scratch from the queries, so a slab count that disagreed
+// with the launcher would be an out-of-bounds write.
+
+// The A/B knobs, read once per process on first use.
+struct WgradKnobs {
+  bool dma;            // KODHIP_WGRAD_DMA: a value that starts with 'n' selects the register-staged kernel
+  int row3;            // KODHIP_WGRAD_ROW3: 0 = off, 1 (default) = where it measured faster, 2 = every eligible layer
+  int slots;           // KODHIP_WGRAD_SLOTS: resident-block target of the generic and dual forms (default 512)
+  int row3_slots;      // KODHIP_WGRAD_ROW3_SLOTS: resident-wave target of the ROW3 form (default 3072)
+  int stem_tw;         // KODHIP_STEM_BWD_TW: 80 (default) | 160
+  int stem_blocks;     // KODHIP_STEM_BWD_BLOCKS: block target of the fused stem backward (0 = every resident slot of the chip)
+};
+const WgradKnobs& wgrad_knobs() {
+  static const WgradKnobs k = [] {
+    auto num = [](const char* e, int dflt) { return e ? atoi(e) : dflt; };
+    WgradKnobs v;
+    const char* mode = getenv("KODHIP_WGRAD_DMA");
+    v.dma = !(mode && mode[0] == 'n');
+    v.row3 = num(getenv("KODHIP_WGRAD_ROW3"), 1);
+    v.slots = num(getenv("KODHIP_WGRAD_SLOTS"), 512);
+    if (v.slots < 8) v.slots = 512;
+    v.row3_slots = num(getenv("KODHIP_WGRAD_ROW3_SLOTS"), 3072);
+    if (v.row3_slots < 96) v.row3_slots = 3072;
+    v.stem_tw = num(getenv("KODHIP_STEM_BWD_TW"), 80);
+    if (v.stem_tw != 80 && v.stem_tw != 160) v.stem_tw = 80;
+    v.stem_blocks = num(getenv("KODHIP_STEM_BWD_BLOCKS"), 0);
+    if (v.stem_blocks < 1) v.stem_blocks = 0;
+    return v;
+  }();
+  return k;
+}
+
 // operands within the 32-bit range of a raw buffer (the LDS-DMA kernels, ROW3 and dual forms need it)
 bool wgrad_in_range(long x_bytes, long dy_bytes) { return x_bytes < (1l << 32) - 64 && dy_bytes < (1l << 32) - 64; }
 
-// LDS-DMA ring (default) or the register-staged kernel (KODHIP_WGRAD_DMA=none, or an operand beyond the buffer range)
-bool wgrad_uses_dma(long x_bytes, long dy_bytes) {
-  static const char* mode = getenv("KODHIP_WGRAD_DMA");
-  return !(mode && mode[0] == 'n') && wgrad_in_range(x_bytes, dy_bytes);
+enum WgradForm { WG_GENERIC, WG_ROW3, WG_DUAL };
+struct WgradPlan {
+  WgradForm form;
+  int tn, tk;                  // a block's tile: output rows x K columns (ROW3: 32 wn rn rows x 32 wc channels of all nine taps)
+  int wn, rn, wc;              // ROW3 template parameters (0 otherwise)
+  int tiles_n, tiles_k;        // dual: tiles_n counts both layers' n tiles
+  int m_per_split, splits;     // splits = slab count; 0: the dual form does not apply to this geometry
+  bool dma;                    // LDS-DMA ring (ROW3 always) / register-staged conv_wgrad_kernel
+  int Ho, Wo;
+  long M, x_bytes, dy_bytes;
+};
+
+// ROW3 form (conv_wgrad_row3_kernel): 3x3 / stride 1 / pad 1 with whole 32-channel chunks.
+// Measured at B = 64 / 640 px (profiles/r03_convbench.txt, generic -> ROW3): 32->32 @160 138 -> 125 us, 256->256 @20
+// 93 -> 77 us, but 64->64 @80 92 -> 104 us and 128->128 @40 58 -> 75 us: a block that owns all nine taps has a 4.5x larger
+// output tile, so the same number of resident blocks writes 4.5x the split-K slab bytes (75 MB against 15-33 MB for
+// the two middle layers, whose whole operand traffic is 52-105 MB).  It pays where the slab is small against the
+// operands (N <= 32) or where the generic kernel's tile count leaves it few rows per block (Cin >= 256).
+bool row3_eligible(int N, int Cin, int KH, int KW, int SH, int SW, int PH, int PW) {
+  const int mode = wgrad_knobs().row3;
+  if (!mode || KH != 3 || KW != 3 || SH != 1 || SW != 1 || PH != 1 || PW != 1 || Cin % 32 != 0 || N % 8 != 0) return false;
+  // mode 1 (default): where the form measured faster than the generic split-K kernel IN THE STEP: narrow outputs (N <= 32) and
+  // Cin >= 256 as long as the nine-tap output tile stays small (N <= 256: 256 -> 256 @20 79 vs 94 us; yv5m's 384 -> 384 @20
+  // 256 vs 198 us - round 3's rule took the form there).  (96 -> 96 @80 gains alone, 174 vs 197 us, and loses in the yv5m step:
+  // 2 220 vs 2 232 img/s - its larger slabs cost the co-running main chain more than the kernel saves.)
+  return mode != 1 || N <= 32 || (Cin >= 256 && N <= 256);
+}
+
+void tile_shape(int N, int Kp, int* tn, int* tk) {
+  *tn = N > 64 ? 128 : (N > 32 ? 64 : 32);
+  // yv5m widths: N = 192 as three 64-row tiles (all used) instead of two 128-row tiles (a quarter idle)
+  // (measured, profiles/r04_convbench_yv5m_tiles.txt: 192 -> 192 3x3 @40 234 -> 191 us, 96 -> 192 s2 431 -> 337, 384 -> 192 1x1 49 -> 34)
+  // (N = 96 as three 32-row tiles instead of one 128-row tile: 198 -> 296 us, not taken)
+  if (N > 128 && N <= 192) *tn = 64;
+  *tk = Kp > 64 ? 128 : (Kp > 32 ? 64 : 32);
+  // narrow outputs: let one block cover all of K so dY is streamed once
+  if (*tn == 32 && (Kp == 160 || Kp == 288)) *tk = Kp;
+}
+
+// Rows of the reduction per split: as many splits as fill `resident_blocks` with `tiles` blocks each, at least one and at most one
+// per 256 rows, in whole 32-row ring stages.
+int rows_per_split(long M, int tiles, int resident_blocks) {
+  int s = resident_blocks / tiles;
+  const long maxs = (M + 255) / 256;
+  if (s > maxs) s = (int)maxs;
+  if (s < 1) s = 1;
+  const int rows = cdiv(cdiv(M, s), 32) * 32;
+  return rows < 32 ? 32 : rows;        // (an empty geometry: never a zero divisor)
+}
+
+// N: output channels of one layer (dual: of each of the two); dual ignores KH .. PW (pointwise)
+WgradPlan wgrad_plan(int B, int H, int W, int ldx, int Cin, int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp, int ldy,
+                     bool dual) {
+  const WgradKnobs& kn = wgrad_knobs();
+  if (dual) { KH = KW = SH = SW = 1; PH = PW = 0; }
+  WgradPlan p = {};
+  p.Ho = (H + 2 * PH - KH) / SH + 1; p.Wo = (W + 2 * PW - KW) / SW + 1;
+  p.M = (long)B * p.Ho * p.Wo;
+  p.x_bytes = (long)B * H * W * ldx * 2; p.dy_bytes = p.M * ldy * 2;
+  const bool in_range = wgrad_in_range(p.x_bytes, p.dy_bytes);
+  int resident;
+  if (!dual && in_range && row3_eligible(N, Cin, KH, KW, SH, SW, PH, PW)) {
+    p.form = WG_ROW3;
+    p.wn = N <= 64 ? 1 : 2; p.rn = N <= 32 ? 1 : 2; p.wc = Cin >= 64 ? 2 : 1;
+    p.tn = p.wn * p.rn * 32; p.tk = p.wc * 32;
+    p.tiles_n = cdiv(N, p.tn); p.tiles_k = cdiv(Cin, p.tk);            // tiles = n tiles x channel chunks
+    p.dma = true;
+    resident = kn.row3_slots / (p.wn * 3 * p.wc);                       // resident blocks: 1024 (3 waves), 512 (6), 256 (12)
+  } else {
+    p.form = dual ? WG_DUAL : WG_GENERIC;
+    tile_shape(N, Kp, &p.tn, &p.tk);
+    p.tiles_n = (dual ? 2 : 1) * cdiv(N, p.tn); p.tiles_k = cdiv(Kp, p.tk);
+    // LDS-DMA ring by default: +4-5 % on the whole training step over the register-staged kernel (in the network the
+    // operands come from HBM and the deeper prefetch pays; back-to-back microbenchmarks with L2-hot operands show
+    // mixed results for the 3x3 layers because an LDS-DMA piece costs 60+ issue cycles).  KODHIP_WGRAD_DMA=none
+    // selects the register-staged kernel for A/B runs; an operand that does not fit a 32-bit buffer range always
+    // takes it.  The dual form exists on the DMA kernel only.
+    p.dma = kn.dma && in_range;
+    resident = kn.slots;
+  }
+  if (dual && !p.dma) return p;                                          // splits = 0: the caller launches kodhip_conv_wgrad twice
+  p.m_per_split = rows_per_split(p.M, p.tiles_n * p.tiles_k, resident);
+  p.splits = cdiv(p.M, p.m_per_split);
+  return p;
 }
 
 template <int WN, int WK, int RN, int RK>
-int launch_cfg(WgradArgs a, hipStream_t stream) {
+int launch_cfg(WgradArgs a, const WgradPlan& p, hipStream_t stream) {
   constexpr int TNB = WN * RN * 32, TKB = WK * RK * 32;
-  a.tiles_n = a.n_half ? 2 * cdiv(a.n_half, TNB) : cdiv(a.N, TNB);
-  a.tiles_k = cdiv(a.Kp, TKB);
-  int grid = wg_grid(a);
-  // LDS-DMA ring by default: +4-5 % on the whole training step over the register-staged kernel (in the network the
-  // operands come from HBM and the deeper prefetch pays; back-to-back microbenchmarks with L2-hot operands show
-  // mixed results for the 3x3 layers because an LDS-DMA piece costs 60+ issue cycles).  KODHIP_WGRAD_DMA=none
-  // selects the register-staged kernel for A/B runs; an operand that does not fit a 32-bit buffer range always
-  // takes it.
-  const long xb = (long)a.B * a.Hs * a.Ws * a.ldx * 2, yb = (long)a.M * a.ldy * 2;
-  if (wgrad_uses_dma(xb, yb)) {
+  KOD_CHECK_ARG(p.tn == TNB && p.tk == TKB && p.tiles_k == cdiv(a.Kp, TKB) &&
+                p.tiles_n == (a.n_half ? 2 * cdiv(a.n_half, TNB) : cdiv(a.N, TNB)), "conv_wgrad: plan and kernel instance disagree");
+  const int grid = wg_grid(a);
+  const dim3 g(grid), b(64 * WN * WK);
+  if (p.dma) {
     const bool pw = a.KH == 1 && a.KW == 1 && a.SH == 1 && a.SW == 1 && a.PH == 0 && a.PW == 0;
-    const dim3 g(grid), b(64 * WN * WK);
-    if (pw) hipLaunchKernelGGL((conv_wgrad_dma_kernel<WN, WK, RN, RK, WGRAD_STAGES, WGRAD_ROWS, 1>), g, b, 0, stream, a, (uint32_t)xb, (uint32_t)yb);
-    else hipLaunchKernelGGL((conv_wgrad_dma_kernel<WN, WK, RN, RK, WGRAD_STAGES, WGRAD_ROWS, 0>), g, b, 0, stream, a, (uint32_t)xb, (uint32_t)yb);
+    const uint32_t xb = (uint32_t)p.x_bytes, yb = (uint32_t)p.dy_bytes;
+    if (pw) hipLaunchKernelGGL((conv_wgrad_dma_kernel<WN, WK, RN, RK, WGRAD_STAGES, WGRAD_ROWS, 1>), g, b, 0, stream, a, xb, yb);
+    else hipLaunchKernelGGL((conv_wgrad_dma_kernel<WN, WK, RN, RK, WGRAD_STAGES, WGRAD_ROWS, 0>), g, b, 0, stream, a, xb, yb);
     KOD_LAUNCH_CHECK("conv_wgrad_dma");
     return KOD_OK;
   }
-  hipLaunchKernelGGL((conv_wgrad_kernel<WN, WK, RN, RK>), dim3(grid), dim3(64 * WN * WK), 0, stream, a);
+  hipLaunchKernelGGL((conv_wgrad_kernel<WN, WK, RN, RK>), g, b, 0, stream, a);
   KOD_LAUNCH_CHECK("conv_wgrad");
   return KOD_OK;
 }
@@ -1102,160 +1186,97 @@ __global__ __launch_bounds__(320, NT == 2 ? 3 : (TW == 160 ? 3 : 5)) void conv_s
     }
 }
 
-// ROW3 form (conv_wgrad_row3_kernel): 3x3 / stride 1 / pad 1 with whole 32-channel chunks.
-// KODHIP_WGRAD_ROW3: 0 = off, 1 (default) = where it measured faster, 2 = every eligible layer.
-// Measured at B = 64 / 640 px (profiles/r03_convbench.txt, generic -> ROW3): 32->32 @160 138 -> 125 us, 256->256 @20
-// 93 -> 77 us, but 64->64 @80 92 -> 104 us and 128->128 @40 58 -> 75 us: a block that owns all nine taps has a 4.5x larger
-// output tile, so the same number of resident blocks writes 4.5x the split-K slab bytes (75 MB against 15-33 MB for
-// the two middle layers, whose whole operand traffic is 52-105 MB).  It pays where the slab is small against the
-// operands (N <= 32) or where the generic kernel's tile count leaves it few rows per block (Cin >= 256).
-struct Row3Cfg { bool on; int wn, rn, wc, tnb; };
-Row3Cfg row3_cfg(int N, int Cin, int KH, int KW, int SH, int SW, int PH, int PW) {
-  static int mode = -1;
-  if (mode < 0) { const char* e = getenv("KODHIP_WGRAD_ROW3"); mode = e ? atoi(e) : 1; }
-  Row3Cfg c = {false, 0, 0, 0, 0};
-  if (!mode || KH != 3 || KW != 3 || SH != 1 || SW != 1 || PH != 1 || PW != 1 || Cin % 32 != 0 || N % 8 != 0) return c;
-  // mode 1 (default): where the form measured faster than the generic split-K kernel IN THE STEP: narrow outputs (N <= 32) and
-  // Cin >= 256 as long as the nine-tap output tile stays small (N <= 256: 256 -> 256 @20 79 vs 94 us; yv5m's 384 -> 384 @20
-  // 256 vs 198 us - round 3's rule took the form there).  (96 -> 96 @80 gains alone, 174 vs 197 us, and loses in the yv5m step:
-  // 2 220 vs 2 232 img/s - its larger slabs cost the co-running main chain more than the kernel saves.)
-  if (mode == 1 && !(N <= 32 || (Cin >= 256 && N <= 256))) return c;
-  c.on = true;
-  if (N <= 32) { c.wn = 1; c.rn = 1; }
-  else if (N <= 64) { c.wn = 1; c.rn = 2; }
-  else { c.wn = 2; c.rn = 2; }
-  c.wc = Cin >= 64 ? 2 : 1;
-  c.tnb = c.wn * c.rn * 32;
-  return c;
-}
-
 template <int WN, int RN, int WC>
-int launch_row3(WgradArgs a, hipStream_t stream) {
+int launch_row3(WgradArgs a, const WgradPlan& p, hipStream_t stream) {
   // ring depth: 4 stages where two 6-wave / one 12-wave block still fit a CU's 160 KB, 3 stages for the 3-wave blocks
   // (4 resident) and the widest 6-wave stage
   constexpr int NST = (WN * 3 * WC == 3 || (WN == 1 && RN == 2 && WC == 2)) ? 3 : 4;
-  const long xb = (long)a.B * a.Hs * a.Ws * a.ldx * 2, yb = (long)a.M * a.ldy * 2;
+  KOD_CHECK_ARG(p.tiles_n == cdiv(a.N, WN * RN * 32) && p.tiles_k == cdiv(a.Cin, WC * 32), "conv_wgrad: plan and ROW3 instance disagree");
   const int grid = wg_grid(a);
-  hipLaunchKernelGGL((conv_wgrad_row3_kernel<WN, RN, WC, NST>), dim3(grid), dim3(64 * WN * 3 * WC), 0, stream, a, (uint32_t)xb, (uint32_t)yb);
+  hipLaunchKernelGGL((conv_wgrad_row3_kernel<WN, RN, WC, NST>), dim3(grid), dim3(64 * WN * 3 * WC), 0, stream, a, (uint32_t)p.x_bytes,
+                     (uint32_t)p.dy_bytes);
   KOD_LAUNCH_CHECK("conv_wgrad_row3");
   return KOD_OK;
 }
 
-// the ROW3 form as launched: eligible by shape and knob, operands within the buffer range
-Row3Cfg row3_form(int N, int Cin, int KH, int KW, int SH, int SW, int PH, int PW, long x_bytes, long dy_bytes) {
-  Row3Cfg c = row3_cfg(N, Cin, KH, KW, SH, SW, PH, PW);
-  if (!wgrad_in_range(x_bytes, dy_bytes)) c.on = false;
-  return c;
+// The kernel instances: (tn, tk) of the generic and dual forms, (wn, rn, wc) of the ROW3 form.  A plan that names no row is an error.
+typedef int (*WgradLaunch)(WgradArgs, const WgradPlan&, hipStream_t);
+struct WgradTile { int tn, tk; WgradLaunch launch; };
+const WgradTile WGRAD_TILES[] = {
+    {128, 128, launch_cfg<2, 2, 2, 2>}, {64, 128, launch_cfg<2, 2, 1, 2>}, {32, 160, launch_cfg<1, 5, 1, 1>},
+    {32, 288, launch_cfg<1, 9, 1, 1>},  {32, 128, launch_cfg<1, 4, 1, 1>}, {128, 64, launch_cfg<2, 2, 2, 1>},
+    {64, 64, launch_cfg<2, 2, 1, 1>},   {32, 64, launch_cfg<1, 2, 1, 1>},  {128, 32, launch_cfg<4, 1, 1, 1>},
+    {64, 32, launch_cfg<2, 1, 1, 1>},   {32, 32, launch_cfg<1, 1, 1, 1>},
+};
+struct WgradRow3 { int wn, rn, wc; WgradLaunch launch; };
+const WgradRow3 WGRAD_ROW3[] = {
+    {1, 1, 1, launch_row3<1, 1, 1>}, {1, 1, 2, launch_row3<1, 1, 2>}, {1, 2, 1, launch_row3<1, 2, 1>},
+    {1, 2, 2, launch_row3<1, 2, 2>}, {2, 2, 1, launch_row3<2, 2, 1>}, {2, 2, 2, launch_row3<2, 2, 2>},
+};
+
+// Fills the kernel arguments from the geometry and the plan and launches the plan's instance: slabs [splits][a.N][Kp] into
+// partials.  dy2 != nullptr: the dual form (N slab rows per layer, a.N = 2 N).
+int wgrad_partial(WgradArgs& a, const char* who, const void* x, const void* dy, const void* dy2, float* partials, int B, int H, int W,
+                  int ldx, int xcoff, int Cin, int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp, int ldy, int ycoff,
+                  hipStream_t stream) {
+  const bool dual = dy2 != nullptr;
+  KOD_CHECK_ARG(x && dy && partials, "%s: null pointer", who);
+  KOD_CHECK_ARG(Cin % 8 == 0 && ldx % 8 == 0 && xcoff % 8 == 0 && xcoff + Cin <= ldx, "%s: bad input slice", who);
+  KOD_CHECK_ARG(N % 8 == 0 && ldy % 8 == 0 && ycoff % 8 == 0 && ycoff + N <= ldy, "%s: bad dy slice (N=%d ldy=%d)", who, N, ldy);
+  KOD_CHECK_ARG(Kp % 32 == 0 && Kp >= KH * KW * Cin, "%s: bad Kp", who);
+  const WgradPlan p = wgrad_plan(B, H, W, ldx, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, dual);
+  KOD_CHECK_ARG(p.M < (1l << 31) && (long)B * H * W < (1l << 31), "%s: pixel count overflows int32", who);
+  KOD_CHECK_ARG(p.splits > 0, "%s: not available for this geometry (kodhip_conv_wgrad_dual_splits == 0)", who);
+  a = WgradArgs{};
+  a.x = (const bf16_t*)x; a.dy = (const bf16_t*)dy; a.dy2 = (const bf16_t*)dy2; a.part = partials;
+  a.B = B; a.Hs = H; a.Ws = W; a.ldx = ldx; a.xcoff = xcoff; a.Cin = Cin;
+  a.Ho = p.Ho; a.Wo = p.Wo; a.M = (int)p.M;
+  a.N = dual ? 2 * N : N; a.n_half = dual ? N : 0; a.K = KH * KW * Cin; a.Kp = Kp;
+  a.KH = KH; a.KW = KW; a.SH = SH; a.SW = SW; a.PH = PH; a.PW = PW; a.ldy = ldy; a.ycoff = ycoff;
+  a.magic_cin = magic_u32((uint32_t)Cin); a.magic_kw = magic_u32((uint32_t)KW);
+  a.magic_hwo = magic_u32((uint32_t)(a.Ho * a.Wo)); a.magic_wo = magic_u32((uint32_t)a.Wo);
+  a.m_per_split = p.m_per_split; a.splits = p.splits;
+  a.tiles_n = p.tiles_n; a.tiles_k = p.tiles_k;
+  if (p.form == WG_ROW3) {
+    for (const WgradRow3& r : WGRAD_ROW3)
+      if (r.wn == p.wn && r.rn == p.rn && r.wc == p.wc) return r.launch(a, p, stream);
+  } else {
+    for (const WgradTile& t : WGRAD_TILES)
+      if (t.tn == p.tn && t.tk == p.tk) return t.launch(a, p, stream);
+  }
+  KOD_CHECK_ARG(false, "%s: no kernel instance for the plan's tile %d x %d", who, p.tn, p.tk);
+  return KOD_EARG;
 }
 
-void tile_shape(int N, int Kp, int* tn, int* tk) {
-  *tn = N > 64 ? 128 : (N > 32 ? 64 : 32);
-  // yv5m widths: N = 192 as three 64-row tiles (all used) instead of two 128-row tiles (a quarter idle)
-  // (measured, profiles/r04_convbench_yv5m_tiles.txt: 192 -> 192 3x3 @40 234 -> 191 us, 96 -> 192 s2 431 -> 337, 384 -> 192 1x1 49 -> 34)
-  // (N = 96 as three 32-row tiles instead of one 128-row tile: 198 -> 296 us, not taken)
-  if (N > 128 && N <= 192) *tn = 64;
-  *tk = Kp > 64 ? 128 : (Kp > 32 ? 64 : 32);
-  // narrow outputs: let one block cover all of K so dY is streamed once
-  if (*tn == 32 && (Kp == 160 || Kp == 288)) *tk = Kp;
+// The fused stem backward's launch (conv_stem_bwd_fused_kernel): row-aligned tiles of TW output pixels dealt to `blocks` blocks,
+// a slab of slab_rows x 160 floats per block.
+// tile width: 80 pixels (four 5-wave blocks per CU; measured 336 us at B = 64 / 640 px against 443 us for 160-pixel tiles
+// with two blocks per CU); KODHIP_STEM_BWD_TW = 80 | 160 is the A/B knob (the two-tile form, N > 32, exists for 80-pixel tiles only)
+struct StemBwdPlan { int TW, tiles_per_row, tiles, blocks, tiles_per_block, slab_rows; };
+StemBwdPlan stem_bwd_plan(int B, int H, int Wp, int N) {
+  const WgradKnobs& kn = wgrad_knobs();
+  StemBwdPlan p;
+  p.TW = (N > 32 || Wp <= 80) ? 80 : kn.stem_tw;
+  p.tiles_per_row = cdiv(Wp, p.TW);
+  const long tiles = (long)B * (H / 2) * p.tiles_per_row;
+  // KODHIP_STEM_BWD_BLOCKS: A/B knob; default: every resident slot of the chip (2 / 2 / 4 blocks per CU)
+  const int want = kn.stem_blocks ? kn.stem_blocks : (N > 32 ? 512 : (p.TW == 160 ? 512 : 1024));
+  p.tiles = (int)tiles;
+  p.blocks = cdiv(tiles, cdiv(tiles, want));
+  p.tiles_per_block = cdiv(tiles, p.blocks);
+  p.slab_rows = N > 32 ? 64 : 32;
+  return p;
 }
 
 }  // namespace
 
 extern "C" {
 
-static int wgrad_splits_target(long M, int N, int Kp) {
-  int tn, tk;
-  tile_shape(N, Kp, &tn, &tk);
-  int tiles = cdiv(N, tn) * cdiv(Kp, tk);
-  static int slots = 0;                  // resident-block target (KODHIP_WGRAD_SLOTS: A/B knob)
-  if (!slots) { const char* e = getenv("KODHIP_WGRAD_SLOTS"); slots = e ? atoi(e) : 512; if (slots < 8) slots = 512; }
-  int s = slots / tiles;
-  if (s < 1) s = 1;
-  long maxs = (M + 255) / 256;
-  if (s > maxs) s = (int)maxs;
-  if (s < 1) s = 1;
-  return s;
-}
-
-static int wgrad_rows_per_split(long M, int N, int Kp) {
-  return cdiv(cdiv(M, wgrad_splits_target(M, N, Kp)), 32) * 32;
-}
-
-// rows per split for a given geometry: the ROW3 form has its own block count (tiles = n tiles x channel chunks)
-static int wgrad_rows_per_split_geo(long M, int N, int Cin, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
-                                    long x_bytes, long dy_bytes) {
-  const Row3Cfg c = row3_form(N, Cin, KH, KW, SH, SW, PH, PW, x_bytes, dy_bytes);
-  if (!c.on) return wgrad_rows_per_split(M, N, Kp);
-  const int tiles = cdiv(N, c.tnb) * cdiv(Cin, c.wc * 32);
-  static int wave_slots = 0;                            // KODHIP_WGRAD_ROW3_SLOTS: resident-wave target (A/B knob; default 3072)
-  if (!wave_slots) { const char* e = getenv("KODHIP_WGRAD_ROW3_SLOTS"); wave_slots = e ? atoi(e) : 3072; if (wave_slots < 96) wave_slots = 3072; }
-  const int slots = wave_slots / (c.wn * 3 * c.wc);    // resident blocks: 1024 (3 waves), 512 (6), 256 (12)
-  int sp = slots / tiles;
-  if (sp < 1) sp = 1;
-  const long maxs = (M + 255) / 256;
-  if (sp > maxs) sp = (int)maxs;
-  if (sp < 1) sp = 1;
-  return cdiv(cdiv(M, sp), 32) * 32;
-}
-
-// Exact split count for a layer geometry (ldx / ldy: row strides of the operands, for the 32-bit range test).
+// Exact slab count for a layer geometry (ldx / ldy: row strides of the operands, for the 32-bit range test): the partials
+// region must hold that many [N][Kp] float slabs.
 int kodhip_conv_wgrad_splits_geo(int B, int H, int W, int ldx, int Cin, int N, int KH, int KW, int SH, int SW, int PH, int PW,
                                  int Kp, int ldy) {
-  const int Ho = (H + 2 * PH - KH) / SH + 1, Wo = (W + 2 * PW - KW) / SW + 1;
-  const long M = (long)B * Ho * Wo;
-  const long xb = (long)B * H * W * ldx * 2, yb = M * ldy * 2;
-  return (int)cdiv(M, (long)wgrad_rows_per_split_geo(M, N, Cin, KH, KW, SH, SW, PH, PW, Kp, xb, yb));
-}
-
-// Number of reduction splits the launcher uses (exact; the partials region must hold splits * N * Kp floats).
-int kodhip_conv_wgrad_splits(long M, int N, int Kp) { return (int)cdiv(M, (long)wgrad_rows_per_split(M, N, Kp)); }
-
-static int wgrad_partial(WgradArgs& a, const void* x, const void* dy, float* partials,
-                         int B, int H, int W, int ldx, int xcoff, int Cin,
-                         int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
-                         int ldy, int ycoff, hipStream_t stream) {
-  KOD_CHECK_ARG(x && dy && partials, "conv_wgrad: null pointer");
-  KOD_CHECK_ARG(Cin % 8 == 0 && ldx % 8 == 0 && xcoff % 8 == 0 && xcoff + Cin <= ldx, "conv_wgrad: bad input slice");
-  KOD_CHECK_ARG(N % 8 == 0 && ldy % 8 == 0 && ycoff % 8 == 0 && ycoff + N <= ldy, "conv_wgrad: bad dy slice (N=%d ldy=%d)", N, ldy);
-  KOD_CHECK_ARG(Kp % 32 == 0 && Kp >= KH * KW * Cin, "conv_wgrad: bad Kp");
-  a = WgradArgs{};
-  a.x = (const bf16_t*)x; a.dy = (const bf16_t*)dy; a.part = partials;
-  a.B = B; a.Hs = H; a.Ws = W; a.ldx = ldx; a.xcoff = xcoff; a.Cin = Cin;
-  a.Ho = (H + 2 * PH - KH) / SH + 1; a.Wo = (W + 2 * PW - KW) / SW + 1;
-  long M = (long)B * a.Ho * a.Wo;
-  KOD_CHECK_ARG(M < (1l << 31) && (long)B * H * W < (1l << 31), "conv_wgrad: pixel count overflows int32");
-  a.M = (int)M; a.N = N; a.K = KH * KW * Cin; a.Kp = Kp;
-  a.KH = KH; a.KW = KW; a.SH = SH; a.SW = SW; a.PH = PH; a.PW = PW; a.ldy = ldy; a.ycoff = ycoff;
-  a.magic_cin = magic_u32((uint32_t)Cin); a.magic_kw = magic_u32((uint32_t)KW);
-  a.magic_hwo = magic_u32((uint32_t)(a.Ho * a.Wo)); a.magic_wo = magic_u32((uint32_t)a.Wo);
-  const long xb = (long)B * H * W * ldx * 2, yb = M * ldy * 2;
-  a.m_per_split = wgrad_rows_per_split_geo(M, N, Cin, KH, KW, SH, SW, PH, PW, Kp, xb, yb);
-  a.splits = cdiv(M, a.m_per_split);
-  const Row3Cfg r3 = row3_form(N, Cin, KH, KW, SH, SW, PH, PW, xb, yb);
-  if (r3.on) {
-    a.tiles_n = cdiv(N, r3.tnb);
-    a.tiles_k = cdiv(Cin, r3.wc * 32);
-    if (r3.wn == 1 && r3.rn == 1 && r3.wc == 1) return launch_row3<1, 1, 1>(a, stream);
-    if (r3.wn == 1 && r3.rn == 1) return launch_row3<1, 1, 2>(a, stream);
-    if (r3.wn == 1 && r3.wc == 1) return launch_row3<1, 2, 1>(a, stream);
-    if (r3.wn == 1) return launch_row3<1, 2, 2>(a, stream);
-    if (r3.wc == 1) return launch_row3<2, 2, 1>(a, stream);
-    return launch_row3<2, 2, 2>(a, stream);
-  }
-  int tn, tk, rc;
-  tile_shape(N, Kp, &tn, &tk);
-  if (tn == 128 && tk == 128) rc = launch_cfg<2, 2, 2, 2>(a, stream);
-  else if (tn == 64 && tk == 128) rc = launch_cfg<2, 2, 1, 2>(a, stream);
-  else if (tn == 32 && tk == 160) rc = launch_cfg<1, 5, 1, 1>(a, stream);
-  else if (tn == 32 && tk == 288) rc = launch_cfg<1, 9, 1, 1>(a, stream);
-  else if (tn == 32 && tk == 128) rc = launch_cfg<1, 4, 1, 1>(a, stream);
-  else if (tn == 128 && tk == 64) rc = launch_cfg<2, 2, 2, 1>(a, stream);
-  else if (tn == 64 && tk == 64) rc = launch_cfg<2, 2, 1, 1>(a, stream);
-  else if (tn == 32 && tk == 64) rc = launch_cfg<1, 2, 1, 1>(a, stream);
-  else if (tn == 128 && tk == 32) rc = launch_cfg<4, 1, 1, 1>(a, stream);
-  else if (tn == 64 && tk == 32) rc = launch_cfg<2, 1, 1, 1>(a, stream);
-  else rc = launch_cfg<1, 1, 1, 1>(a, stream);
-  return rc;
+  return wgrad_plan(B, H, W, ldx, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, false).splits;
 }
 
 int kodhip_conv_wgrad(const void* x, const void* dy, float* partials, float* grad,
@@ -1265,7 +1286,9 @@ int kodhip_conv_wgrad(const void* x, const void* dy, float* partials, float* gra
   KOD_CHECK_ARG(grad, "conv_wgrad: null pointer");
   KOD_CHECK_ARG(n_valid > 0 && n_valid <= N, "conv_wgrad: bad n_valid");
   WgradArgs a;
-  if (int rc = wgrad_partial(a, x, dy, partials, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff, stream)) return rc;
+  if (int rc = wgrad_partial(a, "conv_wgrad", x, dy, nullptr, partials, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff,
+                             stream))
+    return rc;
   return launch_wgrad_reduce((const float*)partials, grad, a.splits, N, n_valid, a.K, Kp, stem ? 8 : Cin, KH * KW, stem, scale,
                              nullptr, 1 << 30, stream);
 }
@@ -1276,30 +1299,18 @@ int kodhip_conv_wgrad(const void* x, const void* dy, float* partials, float* gra
 // both layers (these launches are HBM-bound: 64 -> 32 @160 moves 315 MB per layer, 210 MB of it the shared input).
 // kodhip_conv_wgrad_dual_splits: slab count (partials: splits * 2N * Kp floats), 0 when the form does not apply (operands
 // beyond the 32-bit buffer range, KODHIP_WGRAD_DMA=none) - the caller then launches kodhip_conv_wgrad twice.
-static bool wgrad_dual_ok(long M, int B, int H, int W, int ldx, int ldy) {
-  const long xb = (long)B * H * W * ldx * 2, yb = M * ldy * 2;
-  return wgrad_uses_dma(xb, yb);
-}
-
-static int wgrad_rows_per_split_dual(long M, int N, int Kp) {
-  int tn, tk;
-  tile_shape(N, Kp, &tn, &tk);
-  const int tiles = 2 * cdiv(N, tn) * cdiv(Kp, tk);
-  static int slots = 0;
-  if (!slots) { const char* e = getenv("KODHIP_WGRAD_SLOTS"); slots = e ? atoi(e) : 512; if (slots < 8) slots = 512; }
-  int s = slots / tiles;
-  if (s < 1) s = 1;
-  const long maxs = (M + 255) / 256;
-  if (s > maxs) s = (int)maxs;
-  if (s < 1) s = 1;
-  return cdiv(cdiv(M, s), 32) * 32;
-}
-
 int kodhip_conv_wgrad_dual_splits(int B, int H, int W, int ldx, int Cin, int N, int Kp, int ldy) {
-  (void)Cin;
-  const long M = (long)B * H * W;
-  if (!wgrad_dual_ok(M, B, H, W, ldx, ldy)) return 0;
-  return (int)cdiv(M, (long)wgrad_rows_per_split_dual(M, N, Kp));
+  return wgrad_plan(B, H, W, ldx, Cin, N, 1, 1, 1, 1, 0, 0, Kp, ldy, true).splits;
+}
+
+int kodhip_conv_wgrad_dual(const void* x, const void* dy1, const void* dy2, float* partials, float* grad1, float* grad2,
+                           int B, int H, int W, int ldx, int xcoff, int Cin, int N, int Kp, int ldy, int ycoff,
+                           float scale, hipStream_t stream) {
+  KOD_CHECK_ARG(dy2 && grad1 && grad2, "conv_wgrad_dual: null pointer");
+  WgradArgs a;
+  if (int rc = wgrad_partial(a, "conv_wgrad_dual", x, dy1, dy2, partials, B, H, W, ldx, xcoff, Cin, N, 1, 1, 1, 1, 0, 0, Kp, ldy, ycoff, stream))
+    return rc;
+  return launch_wgrad_reduce((const float*)partials, grad1, a.splits, 2 * N, 2 * N, a.K, Kp, Cin, 1, 0, scale, grad2, N, stream);
 }
 
 // Read-only view of the launch plan of kodhip_conv_wgrad (dual = 0) / kodhip_conv_wgrad_dual (dual = 1: KH .. PW ignored) for
@@ -1311,54 +1322,11 @@ int kodhip_conv_wgrad_plan_query(int B, int H, int W, int ldx, int Cin, int N, i
                                  int Kp, int ldy, int dual, int* out) {
   KOD_CHECK_ARG(out, "conv_wgrad_plan_query: null output");
   KOD_CHECK_ARG(B > 0 && H > 0 && W > 0 && N > 0 && Cin > 0 && Kp > 0, "conv_wgrad_plan_query: bad dims");
-  if (dual) { KH = KW = SH = SW = 1; PH = PW = 0; }
-  const int Ho = (H + 2 * PH - KH) / SH + 1, Wo = (W + 2 * PW - KW) / SW + 1;
-  const long M = (long)B * Ho * Wo;
-  const long xb = (long)B * H * W * ldx * 2, yb = M * ldy * 2;
-  const Row3Cfg r3 = dual ? Row3Cfg{false, 0, 0, 0, 0} : row3_form(N, Cin, KH, KW, SH, SW, PH, PW, xb, yb);
-  int tn, tk;
-  tile_shape(N, Kp, &tn, &tk);
-  const bool row3 = r3.on;
-  out[0] = row3 ? r3.tnb : tn; out[1] = row3 ? r3.wc * 32 : tk; out[2] = row3 ? 1 : 0;
-  out[3] = row3 ? r3.wn : 0; out[4] = row3 ? r3.rn : 0; out[5] = row3 ? r3.wc : 0;
-  out[6] = dual ? (wgrad_dual_ok(M, B, H, W, ldx, ldy) ? (int)cdiv(M, (long)wgrad_rows_per_split_dual(M, N, Kp)) : 0)
-                : (int)cdiv(M, (long)wgrad_rows_per_split_geo(M, N, Cin, KH, KW, SH, SW, PH, PW, Kp, xb, yb));
-  out[7] = (row3 || wgrad_uses_dma(xb, yb)) ? 1 : 0;
+  const WgradPlan p = wgrad_plan(B, H, W, ldx, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, dual != 0);
+  out[0] = p.tn; out[1] = p.tk; out[2] = p.form == WG_ROW3 ? 1 : 0;
+  out[3] = p.wn; out[4] = p.rn; out[5] = p.wc;
+  out[6] = p.splits; out[7] = p.dma ? 1 : 0;
   return KOD_OK;
-}
-
-int kodhip_conv_wgrad_dual(const void* x, const void* dy1, const void* dy2, float* partials, float* grad1, float* grad2,
-                           int B, int H, int W, int ldx, int xcoff, int Cin, int N, int Kp, int ldy, int ycoff,
-                           float scale, hipStream_t stream) {
-  KOD_CHECK_ARG(x && dy1 && dy2 && partials && grad1 && grad2, "conv_wgrad_dual: null pointer");
-  KOD_CHECK_ARG(Cin % 8 == 0 && ldx % 8 == 0 && xcoff % 8 == 0 && xcoff + Cin <= ldx, "conv_wgrad_dual: bad input slice");
-  KOD_CHECK_ARG(N % 8 == 0 && ldy % 8 == 0 && ycoff % 8 == 0 && ycoff + N <= ldy, "conv_wgrad_dual: bad dy slice (N=%d ldy=%d)", N, ldy);
-  KOD_CHECK_ARG(Kp % 32 == 0 && Kp >= Cin, "conv_wgrad_dual: bad Kp");
-  const long M = (long)B * H * W;
-  KOD_CHECK_ARG(M < (1l << 31), "conv_wgrad_dual: pixel count overflows int32");
-  KOD_CHECK_ARG(wgrad_dual_ok(M, B, H, W, ldx, ldy), "conv_wgrad_dual: not available for this geometry (kodhip_conv_wgrad_dual_splits == 0)");
-  WgradArgs a = {};
-  a.x = (const bf16_t*)x; a.dy = (const bf16_t*)dy1; a.dy2 = (const bf16_t*)dy2; a.part = partials;
-  a.B = B; a.Hs = H; a.Ws = W; a.ldx = ldx; a.xcoff = xcoff; a.Cin = Cin;
-  a.Ho = H; a.Wo = W; a.M = (int)M; a.N = 2 * N; a.n_half = N; a.K = Cin; a.Kp = Kp;
-  a.KH = a.KW = a.SH = a.SW = 1; a.PH = a.PW = 0; a.ldy = ldy; a.ycoff = ycoff;
-  a.magic_cin = magic_u32((uint32_t)Cin); a.magic_kw = magic_u32(1u);
-  a.magic_hwo = magic_u32((uint32_t)(H * W)); a.magic_wo = magic_u32((uint32_t)W);
-  a.m_per_split = wgrad_rows_per_split_dual(M, N, Kp);
-  a.splits = cdiv(M, a.m_per_split);
-  int tn, tk, rc;
-  tile_shape(N, Kp, &tn, &tk);
-  if (tn == 128 && tk == 128) rc = launch_cfg<2, 2, 2, 2>(a, stream);
-  else if (tn == 64 && tk == 128) rc = launch_cfg<2, 2, 1, 2>(a, stream);
-  else if (tn == 32 && tk == 128) rc = launch_cfg<1, 4, 1, 1>(a, stream);
-  else if (tn == 128 && tk == 64) rc = launch_cfg<2, 2, 2, 1>(a, stream);
-  else if (tn == 64 && tk == 64) rc = launch_cfg<2, 2, 1, 1>(a, stream);
-  else if (tn == 32 && tk == 64) rc = launch_cfg<1, 2, 1, 1>(a, stream);
-  else if (tn == 128 && tk == 32) rc = launch_cfg<4, 1, 1, 1>(a, stream);
-  else if (tn == 64 && tk == 32) rc = launch_cfg<2, 1, 1, 1>(a, stream);
-  else rc = launch_cfg<1, 1, 1, 1>(a, stream);
-  if (rc) return rc;
-  return launch_wgrad_reduce((const float*)partials, grad1, a.splits, 2 * N, 2 * N, a.K, Kp, Cin, 1, 0, scale, grad2, N, stream);
 }
 
 // The stem's BatchNorm/SiLU backward + weight gradient as one kernel (conv_stem_bwd_fused_kernel) followed by the slab
@@ -1367,23 +1335,7 @@ int kodhip_conv_wgrad_dual(const void* x, const void* dy1, const void* dy2, floa
 // convolution_backward dW).  x: pixel pairs [B][H][Wp][8] bf16 (Wp = image width / 2), dA / y: [B * H/2 * Wp][N] slices,
 // coef = kodhip_bn_bwd_coeffs*'s k1 | k2 | k3; partials: kodhip_stem_bwd_fused_blocks(B, H, Wp, N) * (N <= 32 ? 32 : 64) * 160
 // floats; grad: fp32 [N][3][6][6].  y is left untouched (dY is never materialised).  N <= 64.
-// tile width: 80 pixels (four 5-wave blocks per CU; measured 336 us at B = 64 / 640 px against 443 us for 160-pixel tiles
-// with two blocks per CU); KODHIP_STEM_BWD_TW = 80 | 160 is the A/B knob
-static int stem_bwd_tw(int Wp) {
-  static int tw = 0;
-  if (!tw) { const char* e = getenv("KODHIP_STEM_BWD_TW"); tw = e ? atoi(e) : 80; if (tw != 80 && tw != 160) tw = 80; }
-  return Wp <= 80 ? 80 : tw;
-}
-
-int kodhip_stem_bwd_fused_blocks(int B, int H, int Wp, int N) {
-  const int TW = N > 32 ? 80 : stem_bwd_tw(Wp);
-  const long tiles = (long)B * (H / 2) * cdiv(Wp, TW);
-  static int slots = 0;                  // KODHIP_STEM_BWD_BLOCKS: A/B knob (default: every resident slot of the chip)
-  if (!slots) { const char* e = getenv("KODHIP_STEM_BWD_BLOCKS"); slots = e ? atoi(e) : 0; if (slots < 1) slots = 0; }
-  const int want = slots ? slots : (N > 32 ? 512 : (TW == 160 ? 512 : 1024));      // resident blocks: 2 / 2 / 4 per CU
-  const int tpb = cdiv(tiles, want);
-  return cdiv(tiles, tpb);
-}
+int kodhip_stem_bwd_fused_blocks(int B, int H, int Wp, int N) { return stem_bwd_plan(B, H, Wp, N).blocks; }
 
 int kodhip_stem_bwd_fused(const void* x, const void* dA, int lda, int dacoff, const void* y, int ldy,
                           const float* scale, const float* shift, const float* coef, float* partials, float* grad,
@@ -1399,16 +1351,13 @@ int kodhip_stem_bwd_fused(const void* x, const void* dA, int lda, int dacoff, co
   const long xb = (long)B * H * Wp * 16, gb = M * lda * 2, yb = M * ldy * 2;
   KOD_CHECK_ARG(xb < (1l << 32) - 64 && gb < (1l << 32) - 64 && yb < (1l << 32) - 64, "stem_bwd_fused: tensor beyond the 32-bit buffer range");
   a.x_bytes = (uint32_t)xb; a.da_bytes = (uint32_t)gb; a.y_bytes = (uint32_t)yb;
-  const int TW = N > 32 ? 80 : stem_bwd_tw(Wp);                 // (the two-tile form exists for 80-pixel tiles only)
-  a.tiles_per_row = cdiv(a.Wo, TW);
-  a.tiles = B * a.Ho * a.tiles_per_row;
-  const int blocks = kodhip_stem_bwd_fused_blocks(B, H, Wp, N);
-  a.tiles_per_block = cdiv(a.tiles, blocks);
-  if (N > 32) hipLaunchKernelGGL((conv_stem_bwd_fused_kernel<80, 2>), dim3(blocks), dim3(320), 0, stream, a);
-  else if (TW == 160) hipLaunchKernelGGL((conv_stem_bwd_fused_kernel<160, 1>), dim3(blocks), dim3(320), 0, stream, a);
-  else hipLaunchKernelGGL((conv_stem_bwd_fused_kernel<80, 1>), dim3(blocks), dim3(320), 0, stream, a);
+  const StemBwdPlan p = stem_bwd_plan(B, H, Wp, N);
+  a.tiles_per_row = p.tiles_per_row; a.tiles = p.tiles; a.tiles_per_block = p.tiles_per_block;
+  if (N > 32) hipLaunchKernelGGL((conv_stem_bwd_fused_kernel<80, 2>), dim3(p.blocks), dim3(320), 0, stream, a);
+  else if (p.TW == 160) hipLaunchKernelGGL((conv_stem_bwd_fused_kernel<160, 1>), dim3(p.blocks), dim3(320), 0, stream, a);
+  else hipLaunchKernelGGL((conv_stem_bwd_fused_kernel<80, 1>), dim3(p.blocks), dim3(320), 0, stream, a);
   KOD_LAUNCH_CHECK("stem_bwd_fused");
-  return launch_wgrad_reduce((const float*)partials, grad, blocks, N > 32 ? 64 : 32, N, 144, 160, 8, 18, 1, gscale, nullptr, 1 << 30, stream);
+  return launch_wgrad_reduce((const float*)partials, grad, p.blocks, p.slab_rows, N, 144, 160, 8, 18, 1, gscale, nullptr, 1 << 30, stream);
 }
 
 }  // extern "C"

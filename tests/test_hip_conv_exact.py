@@ -460,7 +460,7 @@ def wref(geo):
 def test_wgrad_every_launch_configuration(geo, cfg):
     """One case per (tn, tk) of wgrad_partial; scale 1 and 2^-7; n_valid < N into a sentinel-filled grad (exactly
     n_valid * Cin * KH * KW floats are written - include/kodhip.h); partials offset by one float: the scalar
-    wgrad_reduce_kernel, bit-identical to the v4 route."""
+    wgrad_reduce_kernel<1>, bit-identical to the 16-byte wgrad_reduce_kernel<4>."""
     B, Cin, H, W, N, k, s, p = geo
     got = wgrad_plan(*geo)
     assert (got["tn"], got["tk"], got["row3"]) == (*cfg, 0), got
@@ -500,9 +500,14 @@ def test_wgrad_row3_templates(cn, tpl):
         assert bool((grad[-64:] == FS).all())
 
 
+# (B, Cin, H, W, N) -> (tn, tk) of the dual form; the last two (the small shape of the ROW3 list: 480 rows): N <= 32 with
+# Kp = 160 / 288, one block over all of K, the <1, 5, 1, 1> / <1, 9, 1, 1> instances as the single form launches them.
+WGRAD_DUAL = [((2, 64, 70, 65, 32), (32, 64)), ((2, 96, 9, 7, 48), (64, 128)), ((1, 256, 30, 20, 128), (128, 128)),
+              ((2, 160, 20, 12, 32), (32, 160)), ((2, 288, 20, 12, 16), (32, 288))]
+
+
 @gpu
-@pytest.mark.parametrize("geo,cfg", [((2, 64, 70, 65, 32), (32, 64)), ((2, 96, 9, 7, 48), (64, 128)), ((1, 256, 30, 20, 128), (128, 128))],
-                         ids=lambda v: "x".join(map(str, v)))
+@pytest.mark.parametrize("geo,cfg", WGRAD_DUAL, ids=lambda v: "x".join(map(str, v)))
 def test_wgrad_dual_exact(geo, cfg):
     """kodhip_conv_wgrad_dual: two pointwise layers over one input (a channel slice), one launch; 48-channel pair: n tiles wider
     than a layer."""
