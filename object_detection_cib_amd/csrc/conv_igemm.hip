@@ -1284,11 +1284,61 @@ void conv_igemm_x4_kernel(ConvArgs4 p) {
   conv_igemm_body<BM, BN, WAVES_M, WAVES_N, MODE, FAST, false, F32ACC>(p.c[cls], bid - q * p.per_class);
 }
 
-// ---- launch planning --------------------------------------------------------------------------------
+// ---- the launch plan: ONE place decides a convolution's launch -------------------------------------------------------
+// conv_plan() (one problem) and conv_plan_x4() (the merged four-class stride-2 data gradient) fill a ConvPlan from the geometric
+// fields of ConvArgs.  The launcher launch<>(), the slot queries (kodhip_conv_dgrad_bnred_slots, kodhip_conv_dgrad_s2f_bnred_slots,
+// kodhip_conv_dgrad_dual_bnred_slots) and kodhip_conv_plan_query only read it.  engine/buffers.py sizes the BatchNorm-backward
+// partial buffers from the slot queries, so a query that disagreed with its launcher would be an out-of-bounds write, or a launch
+// refused inside a captured step.  Outside the plan stay only the launcher's refusals that depend on the mode, and each class's
+// slot_base, which it derives from the plan's groups_m.
+
+// The A/B knobs, read once per process on first use.
+struct ConvKnobs {
+  int force_bn, force_bm;      // KODHIP_FORCE_BN / KODHIP_FORCE_BM: the channel / pixel tile wherever the geometry allows it (0 = off)
+  int row3;                    // KODHIP_ROW3: 0 = off, 1 = only where the plan takes 128-pixel tiles anyway, 2 (default) = wherever eligible
+  int s2_fold_maxc;            // KODHIP_S2_FOLD_MAXC: widest Cin that takes the folded stride-2 data gradient (default 64, 0 = never)
+  bool no_fast;                // KODHIP_NO_FAST: the register-staged kernels everywhere
+  bool s2_separate;            // KODHIP_S2_SEPARATE: the four parity classes as four launches
+  bool no_bnred;               // KODHIP_NO_BNRED: no data gradient carries the BatchNorm-backward reduction
+};
+const ConvKnobs& conv_knobs() {
+  static const ConvKnobs k = [] {
+    auto num = [](const char* e, int dflt) { return e ? atoi(e) : dflt; };
+    ConvKnobs v;
+    v.force_bn = num(getenv("KODHIP_FORCE_BN"), 0);
+    v.force_bm = num(getenv("KODHIP_FORCE_BM"), 0);
+    v.row3 = num(getenv("KODHIP_ROW3"), 2);
+    v.s2_fold_maxc = num(getenv("KODHIP_S2_FOLD_MAXC"), 64);
+    v.no_fast = getenv("KODHIP_NO_FAST") != nullptr;
+    v.s2_separate = getenv("KODHIP_S2_SEPARATE") != nullptr;
+    v.no_bnred = getenv("KODHIP_NO_BNRED") != nullptr;
+    return v;
+  }();
+  return k;
+}
+
+enum ConvForm { CONV_FAST, CONV_REG, CONV_ROW3, CONV_STEM_BODY, CONV_STEM, CONV_X4 };
+struct ConvPlan {
+  ConvForm form;               // generic LDS-DMA / register-staged / ROW3 / stem rows inside the generic body / the stem's own kernel / merged
+  bool fast;                   // LDS-DMA path (every form but CONV_REG)
+  int bm, bn, waves_m, waves_n;
+  int tiles_m, tiles_n, groups_m;
+  int per_class, grid, block;  // blocks of one problem; of the launch (x4: 4 per_class; CONV_STEM: at most 768 and the slot count)
+  int pointwise;               // ConvArgs::pointwise
+  uint32_t x_bytes, w_bytes[4];        // ConvArgs::x_bytes / w_bytes (x4: the classes share the source; [c] = class c's pack)
+  int bnred_slots;             // partial slots a MODE_PLAIN_BN launch of this plan writes (0: off the FAST path, it cannot run)
+};
+
+long x_extent(const ConvArgs& a) { return (long)a.B * a.Hs * a.Ws * a.ldx * 2; }
+long w_extent(const ConvArgs& a) { return (long)a.N * a.Kp * 2; }          // byte extents of the gather source and the weight pack
+
+bool fast_eligible(const ConvArgs& a) {
+  return (a.cin_step % 32 == 0) && (a.sh_shift | a.sw_shift) == 0 && a.K == a.Kp && x_extent(a) < (1l << 32) - 64 &&
+         w_extent(a) < (1l << 32) - 64 && !conv_knobs().no_fast;
+}
+
 // Resident blocks per chip (256 CUs) for each tile shape (FAST path: register-bound at 4 x 4 waves or 2 x 8 waves
 // per CU; register-staged path: LDS-bound, 2 stages of (128+BN)*80 B).
-struct Plan { int bm, bn, groups_m, tiles_m, tiles_n, grid; };
-
 int slots_for(int bm, int bn, bool fast) {
   if (bm == 256) return 512;
   if (fast) return 1024;                        // 4 blocks per CU (128-VGPR launch bound)
@@ -1296,20 +1346,26 @@ int slots_for(int bm, int bn, bool fast) {
 }
 
 constexpr int MAX_STATS_SLOTS = 1024;
+int stats_slots(long M) {
+  long tiles_m = (M + 127) / 128;                  // upper bound over every tile shape the launcher may pick
+  return tiles_m < MAX_STATS_SLOTS ? (int)tiles_m : MAX_STATS_SLOTS;
+}
 
+// 64 < N < 128 (yv5m's 96): one 128-column tile (three quarters used) stages every pixel tile once, two 64-column tiles twice
+int widest_bn(int N) { return N > 64 ? 128 : (N > 32 ? 64 : 32); }
 
-// Tile shape: the widest channel tile that fits N (or the next narrower one when that removes a badly quantised
-// last round).  256-pixel tiles (8 waves, 3-stage ring) when the reduction is long enough to amortise their deeper
+// 256-pixel tiles (256 x 128 and 256 x 64; 8 waves, 3-stage ring) when the reduction is long enough to amortise their deeper
 // pipeline fill (measured on gfx950: 3x3 layers with N >= 128 gain 15-25 %, short-K 1x1 layers lose ~5 %).
-Plan make_plan(long M, int N, int K, bool fast, bool row3 = false) {
-  static int force_bn = -1, force_bm = -1;
-  if (force_bn < 0) { const char* e = getenv("KODHIP_FORCE_BN"); force_bn = e ? atoi(e) : 0; }
-  if (force_bm < 0) { const char* e = getenv("KODHIP_FORCE_BM"); force_bm = e ? atoi(e) : 0; }
-  // 64 < N < 128 (yv5m's 96): one 128-column tile (three quarters used) stages every pixel tile once, two 64-column tiles twice
-  const int widest = N > 64 ? 128 : (N > 32 ? 64 : 32);
-  const bool can256 = fast && widest >= 64 && M >= 256 * 64;       // 256 x 128 and 256 x 64 tiles
-  const int bm = !row3 && can256 && (force_bm ? force_bm == 256 : K >= 512) ? 256 : 128;
-  Plan best = {};
+bool takes_256(long M, int N, int K, bool fast) {
+  const int force_bm = conv_knobs().force_bm;
+  return fast && widest_bn(N) >= 64 && M >= 256 * 64 && (force_bm ? force_bm == 256 : K >= 512);
+}
+
+// Tile shape: the widest channel tile that fits N (or the next narrower one when that removes a badly quantised last round)
+void make_plan(ConvPlan& p, long M, int N, int K, bool fast, bool row3 = false) {
+  const int force_bn = conv_knobs().force_bn;
+  const int widest = widest_bn(N);
+  const int bm = !row3 && takes_256(M, N, K, fast) ? 256 : 128;
   double best_cost = 1e30;
   // (128 < N <= 192 as three 64-column tiles instead of two 128-column ones: 3x3 + 5 %, stride-2 forward - 39 %, 1x1 - 10 %: not taken)
   for (int bn = widest; bn >= 32 && bn >= widest / 2; bn >>= 1) {
@@ -1325,175 +1381,154 @@ Plan make_plan(long M, int N, int K, bool fast, bool row3 = false) {
       int target = slots / (int)tiles_n;
       if (target < 8) target = 8;
       if (target > MAX_STATS_SLOTS) target = MAX_STATS_SLOTS;
-      int gm = tiles_m < target ? (int)tiles_m : target;
-      best = {bm, bn, gm, (int)tiles_m, (int)tiles_n, cdiv(gm, 8) * 8 * (int)tiles_n};
+      p.bm = bm; p.bn = bn; p.tiles_m = (int)tiles_m; p.tiles_n = (int)tiles_n;
+      p.groups_m = tiles_m < target ? (int)tiles_m : target;
+      p.per_class = p.grid = cdiv(p.groups_m, 8) * 8 * (int)tiles_n;
     }
   }
-  return best;
+  p.waves_m = p.bm == 256 || p.bn == 32 ? 4 : 2; p.waves_n = p.bn == 32 ? 1 : 2;
+  p.block = 64 * p.waves_m * p.waves_n;
 }
 
-bool fast_eligible(const ConvArgs& a);
+// The plan of one problem.  `mode` matters in one respect: only a conv unit's forward (MODE_RAW, the fused modes) has the stem forms.
+ConvPlan conv_plan(const ConvArgs& a, int mode) {
+  ConvPlan p = {};
+  p.fast = fast_eligible(a);
+  const int K = a.nk1 ? 2 * a.K : a.K;
+  // ROW3 form (conv_igemm_body): 3x3 / stride 1 / pad 1 gathers of same-size images on the FAST path
+  const int row3_mode = conv_knobs().row3;
+  const bool row3 = p.fast && row3_mode && a.KH == 3 && a.KW == 3 && a.mul_h == 1 && a.mul_w == 1 && a.Ho == a.Hs && a.Wo == a.Ws &&
+                    a.add_h == -a.tap_sign && a.add_w == -a.tap_sign && a.wide_px == 1 && a.nk1 == 0 && a.d2s_C == 0 &&
+                    a.out_mul == 1 && a.head_A == 0 && !(row3_mode == 1 && takes_256(a.M, a.N, K, p.fast));
+  make_plan(p, a.M, a.N, K, p.fast, row3);
+  p.form = row3 ? CONV_ROW3 : (p.fast ? CONV_FAST : CONV_REG);
+  p.x_bytes = (uint32_t)x_extent(a); p.w_bytes[0] = (uint32_t)w_extent(a);
+  p.pointwise = (p.fast && a.KH == 1 && a.KW == 1 && a.mul_h == 1 && a.mul_w == 1 && a.add_h == 0 && a.add_w == 0 &&
+                 a.Ho == a.Hs && a.Wo == a.Ws && a.wide_px == 1 && (a.sh_shift | a.sw_shift) == 0) ? 1 : 0;
+  p.bnred_slots = p.fast ? (a.d2s_C ? 4 : 1) * p.groups_m : 0;
+  if ((mode == MODE_RAW || mode_is_fused(mode)) && p.fast && !row3 && a.wide_px == 4 && a.KW == 1 && a.mul_w == 1 && a.add_w == -1 &&
+      a.ldx == 8 && a.xcoff == 0 && p.bm == 128 && (p.bn == 32 || p.bn == 64) && (long)a.M + 256 < (1l << 31)) {
+    p.form = CONV_STEM_BODY;       // the stem's wide-pixel form: row-shared staging inside the generic body, or for N <= 32 its own kernel
+    if (p.bn == 32 && a.N <= 32 && a.KH == 6 && a.ycoff % 8 == 0) {
+      p.form = CONV_STEM;
+      p.grid = p.tiles_m < 768 ? p.tiles_m : 768;                   // 3 resident blocks per CU (48 KB of LDS each)
+      if (p.grid > a.stats_slots) p.grid = a.stats_slots;           // (the fused modes keep the raw mode's grid: same slot count)
+      p.per_class = p.grid; p.block = 256;
+    }
+  }
+  return p;
+}
 
-// ROW3 form (conv_igemm_body): 3x3 / stride 1 / pad 1 gathers of same-size images on the FAST path.
-// KODHIP_ROW3: 0 = off, 1 = only where the plan would use 128-pixel tiles anyway, 2 (default) = every eligible layer.
-bool row3_eligible(const ConvArgs& a, bool fast) {
-  static int mode = -1;
-  if (mode < 0) { const char* e = getenv("KODHIP_ROW3"); mode = e ? atoi(e) : 2; }
-  if (!mode || !fast) return false;
-  const bool shape = a.KH == 3 && a.KW == 3 && a.mul_h == 1 && a.mul_w == 1 && a.Ho == a.Hs && a.Wo == a.Ws &&
-                     a.add_h == -a.tap_sign && a.add_w == -a.tap_sign && a.wide_px == 1 && a.nk1 == 0 && a.d2s_C == 0 &&
-                     a.out_mul == 1 && a.head_out == nullptr;
-  if (!shape) return false;
-  if (mode == 1 && make_plan(a.M, a.N, a.K, fast).bm != 128) return false;
+// The plan of the merged launch of four FAST problems that share M and N (a stride-2 data gradient's parity classes), its tiles chosen
+// for the longest reduction.  false: the four do not merge (KODHIP_S2_SEPARATE, a class off the FAST path) and each is its own launch.
+bool conv_plan_x4(const ConvArgs c[4], ConvPlan& p) {
+  p = ConvPlan{};
+  int kmax = 0;
+  for (int i = 0; i < 4; ++i) {
+    if (conv_knobs().s2_separate || !fast_eligible(c[i])) return false;
+    kmax = c[i].K > kmax ? c[i].K : kmax;
+    p.w_bytes[i] = (uint32_t)w_extent(c[i]);
+  }
+  p.form = CONV_X4; p.fast = true;
+  make_plan(p, c[0].M, c[0].N, kmax, true);
+  p.grid = 4 * p.per_class;
+  p.x_bytes = (uint32_t)x_extent(c[0]);
+  p.bnred_slots = 4 * p.groups_m;               // the four classes reduce into disjoint slot ranges of the same buffers
   return true;
 }
 
-Plan plan_conv(const ConvArgs& a, bool fast, bool& row3) {
-  row3 = row3_eligible(a, fast);
-  return make_plan(a.M, a.N, a.nk1 ? 2 * a.K : a.K, fast, row3);
+// ---- kernel instances: one (bm, bn, waves) ladder for every kernel template ----------------------------------------------
+// Per tile: the LDS-DMA kernel and the merged one everywhere; the register-staged kernel, ROW3 and the stem body at 128 pixels
+// only, the stem body up to 64 columns; no register-staged instance of the modes that need the FAST path, no ROW3 head.
+template <int BM, int BN, int WM, int WN, int MODE, bool F32ACC, class Args>
+int launch_tile(const ConvPlan& p, const Args& args, hipStream_t stream) {
+  KOD_CHECK_ARG(p.bm == BM && p.bn == BN && p.waves_m == WM && p.waves_n == WN && p.block == 64 * WM * WN,
+                "conv: plan and kernel instance disagree");
+  auto go = [&](auto kernel, const char* name) -> int {
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), 0, stream, args);
+    KOD_LAUNCH_CHECK(name);
+    return KOD_OK;
+  };
+  constexpr bool one = std::is_same_v<Args, ConvArgs>, small = one && BM == 128, unit_fwd = MODE == MODE_RAW || mode_is_fused(MODE);
+  if constexpr (!one)
+    if (p.form == CONV_X4) return go(conv_igemm_x4_kernel<BM, BN, WM, WN, MODE, true, F32ACC>, "conv_igemm_x4");
+  if constexpr (one)
+    if (p.form == CONV_FAST) return go(conv_igemm_kernel<BM, BN, WM, WN, MODE, true, F32ACC>, "conv_igemm");
+  if constexpr (small && !F32ACC && MODE != MODE_PLAIN_BN)
+    if (p.form == CONV_REG) return go(conv_igemm_kernel<BM, BN, WM, WN, MODE, false>, "conv_igemm");
+  if constexpr (small && MODE != MODE_HEAD)
+    if (p.form == CONV_ROW3) return go(conv_igemm_row3_kernel<BN, WM, WN, MODE, F32ACC>, "conv_igemm_row3");
+  if constexpr (small && BN <= 64 && unit_fwd)
+    if (p.form == CONV_STEM_BODY) return go(conv_igemm_stem_kernel<BN, WM, WN, MODE>, "conv_igemm_stem");
+  KOD_CHECK_ARG(false, "conv: no kernel instance of form %d at %d x %d in mode %d", (int)p.form, BM, BN, MODE);
 }
 
+template <int MODE, bool F32ACC, class Args>
+int launch_plan(const ConvPlan& p, const Args& args, hipStream_t stream) {
+  if (p.bm == 256 && p.bn == 64) return launch_tile<256, 64, 4, 2, MODE, F32ACC>(p, args, stream);
+  if (p.bm == 256 && p.bn == 128) return launch_tile<256, 128, 4, 2, MODE, F32ACC>(p, args, stream);
+  if (p.bm == 128 && p.bn == 128) return launch_tile<128, 128, 2, 2, MODE, F32ACC>(p, args, stream);
+  if (p.bm == 128 && p.bn == 64) return launch_tile<128, 64, 2, 2, MODE, F32ACC>(p, args, stream);
+  if (p.bm == 128 && p.bn == 32) return launch_tile<128, 32, 4, 1, MODE, F32ACC>(p, args, stream);
+  KOD_CHECK_ARG(false, "conv: no kernel instance for a %d x %d tile", p.bm, p.bn);
+}
+
+// One launch: of one problem (n = 1), or of the four problems of a conv_plan_x4() plan (n = 4: data gradients only).
 template <int MODE, bool F32ACC = false>
-int launch(const ConvArgs& a, hipStream_t stream) {
-  if constexpr ((MODE == MODE_PLAIN || MODE == MODE_PLAIN_BN) && !F32ACC) {
-    if (a.f32_mode != 0) return launch<MODE, true>(a, stream);      // fp32 accumulation across producers: own kernels
+int launch(const ConvArgs* c, int n, hipStream_t stream) {
+  constexpr bool dgrad = MODE == MODE_PLAIN || MODE == MODE_PLAIN_BN;
+  if constexpr (dgrad && !F32ACC) {
+    if (c[0].f32_mode != 0) return launch<MODE, true>(c, n, stream);      // fp32 accumulation across producers: own kernels
   }
-  ConvArgs args = a;
-  const long xb = (long)a.B * a.Hs * a.Ws * a.ldx * 2, wb = (long)a.N * a.Kp * 2;
-  const bool fast = fast_eligible(a);
-  KOD_CHECK_ARG(fast || a.wide_px == 1, "conv: wide-pixel taps need the FAST path");
-  args.x_bytes = (uint32_t)xb; args.w_bytes = (uint32_t)wb;
-  args.pointwise = (fast && a.KH == 1 && a.KW == 1 && a.mul_h == 1 && a.mul_w == 1 && a.add_h == 0 && a.add_w == 0 &&
-                    a.Ho == a.Hs && a.Wo == a.Ws && a.wide_px == 1 && (a.sh_shift | a.sw_shift) == 0) ? 1 : 0;
-  bool row3;
-  const Plan p = plan_conv(a, fast, row3);
-  args.tiles_n = p.tiles_n; args.tiles_m = p.tiles_m; args.groups_m = p.groups_m;
-  if (MODE == MODE_RAW) {
-    KOD_CHECK_ARG(a.stats_slots >= p.groups_m, "conv: stats buffer has %d slots, launch needs %d", a.stats_slots, p.groups_m);
+  ConvPlan p;
+  if (n == 1) p = conv_plan(c[0], MODE);
+  else KOD_CHECK_ARG(dgrad && n == 4 && conv_plan_x4(c, p), "conv: these problems do not merge into one launch (query the slots first)");
+  KOD_CHECK_ARG(p.fast || c[0].wide_px == 1, "conv: wide-pixel taps need the FAST path");
+  KOD_CHECK_ARG(p.fast || !F32ACC, "conv: fp32 accumulation across producers needs the FAST path");
+  KOD_CHECK_ARG(p.fast || MODE != MODE_PLAIN_BN, "conv: the fused BatchNorm-backward reduction needs the FAST path (query the slots first)");
+  ConvArgs4 q;
+  for (int i = 0; i < n; ++i) {
+    ConvArgs& a = q.c[i];
+    a = c[i];
+    a.x_bytes = p.x_bytes; a.w_bytes = p.w_bytes[i]; a.pointwise = p.pointwise;
+    a.tiles_n = p.tiles_n; a.tiles_m = p.tiles_m; a.groups_m = p.groups_m;
+    if (MODE == MODE_RAW) KOD_CHECK_ARG(a.stats_slots >= p.groups_m, "conv: stats buffer has %d slots, launch needs %d", a.stats_slots, p.groups_m);
+    if (MODE == MODE_PLAIN_BN) {      // the classes of a merged launch reduce into disjoint slot ranges of the same buffers
+      KOD_CHECK_ARG(a.stats_slots >= p.bnred_slots, "conv: partial buffers have %d slots, launch needs %d", a.stats_slots, p.bnred_slots);
+      a.slot_base = i * p.groups_m; a.slot_used = p.bnred_slots;
+    }
   }
-  if (MODE == MODE_PLAIN_BN) {
-    const int need = (a.d2s_C ? 4 : 1) * p.groups_m;
-    KOD_CHECK_ARG(a.stats_slots >= need, "conv: partial buffers have %d slots, launch needs %d", a.stats_slots, need);
-    args.slot_base = 0; args.slot_used = need;
-  }
-  dim3 g(p.grid);
+  q.per_class = p.per_class;
+  if constexpr (dgrad)
+    if (p.form == CONV_X4) return launch_plan<MODE, F32ACC>(p, q, stream);
   if constexpr (MODE == MODE_RAW || mode_is_fused(MODE)) {
-    // the stem's wide-pixel form
-    if (fast && !row3 && a.wide_px == 4 && a.KW == 1 && a.mul_w == 1 && a.add_w == -1 && a.ldx == 8 && a.xcoff == 0 &&
-        p.bm == 128 && (p.bn == 32 || p.bn == 64) && (long)a.M + 256 < (1l << 31)) {
-      // the dedicated kernel for N <= 32, else row-shared staging inside the generic body
-      if (p.bn == 32 && a.N <= 32 && a.KH == 6 && a.ycoff % 8 == 0) {
-        int blocks = p.tiles_m < 768 ? p.tiles_m : 768;             // 3 resident blocks per CU (48 KB of LDS each)
-        if (blocks > a.stats_slots) blocks = a.stats_slots;           // (the fused modes keep the raw mode's grid: same slot count)
-        if constexpr (MODE == MODE_RAW) hipLaunchKernelGGL(conv_stem_fwd_kernel, dim3(blocks), dim3(256), 0, stream, args);
-        else hipLaunchKernelGGL(conv_stem_fwd_fused_kernel<MODE>, dim3(blocks), dim3(256), 0, stream, args);
-        KOD_LAUNCH_CHECK("conv_stem_fwd");
-        return KOD_OK;
-      }
-      if (p.bn == 32) hipLaunchKernelGGL((conv_igemm_stem_kernel<32, 4, 1, MODE>), g, dim3(256), 0, stream, args);
-      else hipLaunchKernelGGL((conv_igemm_stem_kernel<64, 2, 2, MODE>), g, dim3(256), 0, stream, args);
-      KOD_LAUNCH_CHECK("conv_igemm_stem");
+    if (p.form == CONV_STEM) {
+      if constexpr (MODE == MODE_RAW) hipLaunchKernelGGL(conv_stem_fwd_kernel, dim3(p.grid), dim3(p.block), 0, stream, q.c[0]);
+      else hipLaunchKernelGGL(conv_stem_fwd_fused_kernel<MODE>, dim3(p.grid), dim3(p.block), 0, stream, q.c[0]);
+      KOD_LAUNCH_CHECK("conv_stem_fwd");
       return KOD_OK;
     }
   }
-  if constexpr (MODE != MODE_HEAD) {
-    if (row3) {
-      if (p.bn == 128) hipLaunchKernelGGL((conv_igemm_row3_kernel<128, 2, 2, MODE, F32ACC>), g, dim3(256), 0, stream, args);
-      else if (p.bn == 64) hipLaunchKernelGGL((conv_igemm_row3_kernel<64, 2, 2, MODE, F32ACC>), g, dim3(256), 0, stream, args);
-      else hipLaunchKernelGGL((conv_igemm_row3_kernel<32, 4, 1, MODE, F32ACC>), g, dim3(256), 0, stream, args);
-      KOD_LAUNCH_CHECK("conv_igemm_row3");
-      return KOD_OK;
-    }
-  }
-  if (fast) {
-    if (p.bm == 256 && p.bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<256, 64, 4, 2, MODE, true, F32ACC>), g, dim3(512), 0, stream, args);
-    else if (p.bm == 256) hipLaunchKernelGGL((conv_igemm_kernel<256, 128, 4, 2, MODE, true, F32ACC>), g, dim3(512), 0, stream, args);
-    else if (p.bn == 128) hipLaunchKernelGGL((conv_igemm_kernel<128, 128, 2, 2, MODE, true, F32ACC>), g, dim3(256), 0, stream, args);
-    else if (p.bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<128, 64, 2, 2, MODE, true, F32ACC>), g, dim3(256), 0, stream, args);
-    else hipLaunchKernelGGL((conv_igemm_kernel<128, 32, 4, 1, MODE, true, F32ACC>), g, dim3(256), 0, stream, args);
-  } else if constexpr (F32ACC) {
-    KOD_CHECK_ARG(false, "conv: fp32 accumulation across producers needs the FAST path");
-  } else if constexpr (MODE == MODE_PLAIN_BN) {
-    KOD_CHECK_ARG(false, "conv: the fused BatchNorm-backward reduction needs the FAST path (query the slots first)");
-  } else {
-    if (p.bn == 128) hipLaunchKernelGGL((conv_igemm_kernel<128, 128, 2, 2, MODE, false>), g, dim3(256), 0, stream, args);
-    else if (p.bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<128, 64, 2, 2, MODE, false>), g, dim3(256), 0, stream, args);
-    else hipLaunchKernelGGL((conv_igemm_kernel<128, 32, 4, 1, MODE, false>), g, dim3(256), 0, stream, args);
-  }
-  KOD_LAUNCH_CHECK("conv_igemm");
-  return KOD_OK;
-}
-
-// the tile plan four FAST problems of one merged launch share: chosen for the longest reduction
-Plan plan_x4(const ConvArgs c[4]) {
-  int kmax = 0;
-  for (int i = 0; i < 4; ++i) kmax = c[i].K > kmax ? c[i].K : kmax;
-  return make_plan(c[0].M, c[0].N, kmax, true);
-}
-
-// one launch for four FAST problems that share M, N and the tile plan
-template <int MODE, bool F32ACC = false>
-int launch_x4(ConvArgs c[4], hipStream_t stream) {
-  if constexpr (!F32ACC) {
-    if (c[0].f32_mode != 0) return launch_x4<MODE, true>(c, stream);
-  }
-  ConvArgs4 p;
-  const Plan pl = plan_x4(c);
-  for (int i = 0; i < 4; ++i) {
-    p.c[i] = c[i];
-    p.c[i].x_bytes = (uint32_t)((long)c[i].B * c[i].Hs * c[i].Ws * c[i].ldx * 2);
-    p.c[i].w_bytes = (uint32_t)((long)c[i].N * c[i].Kp * 2);
-    p.c[i].tiles_n = pl.tiles_n; p.c[i].tiles_m = pl.tiles_m; p.c[i].groups_m = pl.groups_m;
-    if (MODE == MODE_PLAIN_BN) {      // the four classes reduce into disjoint slot ranges of the same buffers
-      KOD_CHECK_ARG(c[i].stats_slots >= 4 * pl.groups_m, "conv: partial buffers have %d slots, launch needs %d", c[i].stats_slots, 4 * pl.groups_m);
-      p.c[i].slot_base = i * pl.groups_m; p.c[i].slot_used = 4 * pl.groups_m;
-    }
-  }
-  p.per_class = pl.grid;
-  dim3 g(pl.grid * 4);
-  if (pl.bm == 256 && pl.bn == 64) hipLaunchKernelGGL((conv_igemm_x4_kernel<256, 64, 4, 2, MODE, true, F32ACC>), g, dim3(512), 0, stream, p);
-  else if (pl.bm == 256) hipLaunchKernelGGL((conv_igemm_x4_kernel<256, 128, 4, 2, MODE, true, F32ACC>), g, dim3(512), 0, stream, p);
-  else if (pl.bn == 128) hipLaunchKernelGGL((conv_igemm_x4_kernel<128, 128, 2, 2, MODE, true, F32ACC>), g, dim3(256), 0, stream, p);
-  else if (pl.bn == 64) hipLaunchKernelGGL((conv_igemm_x4_kernel<128, 64, 2, 2, MODE, true, F32ACC>), g, dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL((conv_igemm_x4_kernel<128, 32, 4, 1, MODE, true, F32ACC>), g, dim3(256), 0, stream, p);
-  KOD_LAUNCH_CHECK("conv_igemm_x4");
-  return KOD_OK;
-}
-
-bool fast_eligible(const ConvArgs& a) {
-  const long xb = (long)a.B * a.Hs * a.Ws * a.ldx * 2, wb = (long)a.N * a.Kp * 2;
-  return (a.cin_step % 32 == 0) && (a.sh_shift | a.sw_shift) == 0 && a.K == a.Kp && xb < (1l << 32) - 64 &&
-         wb < (1l << 32) - 64 && !getenv("KODHIP_NO_FAST");
+  return launch_plan<MODE, F32ACC>(p, q.c[0], stream);
 }
 
 int ilog2_exact(int v) { int s = 0; while ((1 << s) < v) ++s; return ((1 << s) == v) ? s : -1; }
 
-}  // namespace
-
-extern "C" {
-
-// Per-channel partial slots of the statistics buffer: it must hold 2 * N * kodhip_conv_stats_slots(M, N) floats;
-// the kernel fills the slots it uses and zeroes the rest.
-int kodhip_conv_stats_slots(long M, int N) {
-  long tiles_m = (M + 127) / 128;                  // upper bound over every tile shape the launcher may pick
-  (void)N;
-  return tiles_m < MAX_STATS_SLOTS ? (int)tiles_m : MAX_STATS_SLOTS;
-}
-
-static int fill_common(ConvArgs& a, const void* x, const void* w, int B, int Hs, int Ws, int ldx, int xcoff,
-                       int Cin, int Ho, int Wo, int N, int KH, int KW, int Kp) {
-  KOD_CHECK_ARG(x && w, "conv: null pointer");
-  KOD_CHECK_ARG(B > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0 && N > 0, "conv: bad dims");
-  KOD_CHECK_ARG(Cin % 8 == 0 && ldx % 8 == 0 && xcoff % 8 == 0, "conv: channels must be multiples of 8 (Cin=%d ldx=%d off=%d)", Cin, ldx, xcoff);
+// ---- geometry: integers in, checks, the geometric fields of ConvArgs out (`who`: the entry point, for the error text).  The entry
+// points then bind and check the pointers; the queries stop here.
+int geo_common(ConvArgs& a, const char* who, int B, int Hs, int Ws, int ldx, int xcoff, int Cin, int Ho, int Wo, int N, int KH,
+               int KW, int Kp) {
+  a = ConvArgs{};
+  KOD_CHECK_ARG(B > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0 && N > 0, "%s: bad dims", who);
+  KOD_CHECK_ARG(Cin % 8 == 0 && ldx % 8 == 0 && xcoff % 8 == 0, "%s: channels must be multiples of 8 (Cin=%d ldx=%d off=%d)", who, Cin, ldx, xcoff);
   // a tap may span several consecutive pixels (Cin = wide * ldx, one column of taps): the stem's pixel-pair window
   const bool wide = Cin > ldx && xcoff == 0 && Cin % ldx == 0 && KW == 1 && Cin == 32;
-  KOD_CHECK_ARG(xcoff + Cin <= ldx || wide, "conv: channel slice out of range");
+  KOD_CHECK_ARG(xcoff + Cin <= ldx || wide, "%s: channel slice out of range", who);
   a.wide_px = wide ? Cin / ldx : 1;
   const int cin_step = (Cin + 31) / 32 * 32;
-  KOD_CHECK_ARG(Kp == KH * KW * cin_step, "conv: Kp=%d must be taps x round_up(Cin, 32) = %d (packed K axis: k = tap * round_up(Cin, 32) + ci)", Kp, KH * KW * cin_step);
-  KOD_CHECK_ARG(KH * KW <= 32, "conv: at most 32 taps");
-  KOD_CHECK_ARG((long)B * Hs * Ws < (1l << 31) / 1 && (long)B * Ho * Wo < (1l << 31), "conv: pixel count overflows int32");
-  a.x = (const bf16_t*)x; a.w = (const bf16_t*)w;
+  KOD_CHECK_ARG(Kp == KH * KW * cin_step, "%s: Kp=%d must be taps x round_up(Cin, 32) = %d (packed K axis: k = tap * round_up(Cin, 32) + ci)", who, Kp, KH * KW * cin_step);
+  KOD_CHECK_ARG(KH * KW <= 32, "%s: at most 32 taps", who);
+  KOD_CHECK_ARG((long)B * Hs * Ws < (1l << 31) && (long)B * Ho * Wo < (1l << 31), "%s: pixel count overflows int32", who);
   a.B = B; a.Hs = Hs; a.Ws = Ws; a.ldx = ldx; a.xcoff = xcoff; a.Cin = Cin; a.cin_step = cin_step;
   a.Ho = Ho; a.Wo = Wo; a.M = B * Ho * Wo; a.N = N; a.K = KH * KW * cin_step; a.Kp = Kp; a.KH = KH; a.KW = KW;
   a.magic_cin = magic_u32((uint32_t)cin_step); a.magic_kw = magic_u32((uint32_t)KW);
@@ -1502,87 +1537,110 @@ static int fill_common(ConvArgs& a, const void* x, const void* w, int B, int Hs,
   return KOD_OK;
 }
 
-// Forward conv of a conv+BN+SiLU unit: y_raw[M][ldy] (bf16) + BatchNorm partials stats[2][N][slots].
-static int prep_fwd_raw(ConvArgs& a, const void* x, const void* w_packed, void* y, float* stats,
-                        int B, int H, int W, int ldx, int xcoff, int Cin,
-                        int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
-                        int ldy, int ycoff) {
-  a = ConvArgs{};
+// a data gradient's output slice and its `accumulate` argument: bit 0 = add to the bf16 partial already in dx (read-
+// modify-write, rounds twice); bits 8.. = f32_mode (ConvArgs) with dx_f32 = the output buffer's fp32 shadow
+int geo_dx(ConvArgs& a, const char* who, int Cin, int ldx, int xcoff, int accumulate) {
+  KOD_CHECK_ARG(Cin % 8 == 0 && ldx % 8 == 0 && xcoff % 8 == 0 && xcoff + Cin <= ldx, "%s: bad output slice", who);
+  a.ldy = ldx; a.ycoff = xcoff;
+  a.accumulate = accumulate & 1;
+  a.f32_mode = accumulate >> 8;
+  KOD_CHECK_ARG(a.f32_mode >= 0 && a.f32_mode <= 4, "conv_dgrad: bad fp32 accumulation mode %d", a.f32_mode);
+  return KOD_OK;
+}
+
+int geo_fwd(ConvArgs& a, const char* who, int B, int H, int W, int ldx, int xcoff, int Cin, int N, int KH, int KW, int SH, int SW,
+            int PH, int PW, int Kp, int ldy, int ycoff) {
   // wide-pixel form (the stem: Cin = 32 = four 8-channel pixel pairs per tap, KW = 1): the window's last pixel is
   // K-alignment padding with zero weights, so the true kernel width for the output size is Cin/ldx - 1
   const int kw_out = (Cin > ldx && KW == 1) ? Cin / ldx - 1 : KW;
   int Ho = (H + 2 * PH - KH) / SH + 1, Wo = (W + 2 * PW - kw_out) / SW + 1;
-  int rc = fill_common(a, x, w_packed, B, H, W, ldx, xcoff, Cin, Ho, Wo, N, KH, KW, Kp);
-  if (rc) return rc;
-  KOD_CHECK_ARG(y && stats, "conv_fwd_raw: null output");
-  KOD_CHECK_ARG(N % 8 == 0 && ldy % 8 == 0 && ycoff % 8 == 0 && ycoff + N <= ldy, "conv_fwd_raw: bad output slice");
-  a.y = (bf16_t*)y; a.stats = stats; a.ldy = ldy; a.ycoff = ycoff;
-  a.stats_slots = kodhip_conv_stats_slots(a.M, N);
+  if (int rc = geo_common(a, who, B, H, W, ldx, xcoff, Cin, Ho, Wo, N, KH, KW, Kp)) return rc;
+  KOD_CHECK_ARG(N % 8 == 0 && ldy % 8 == 0 && ycoff % 8 == 0 && ycoff + N <= ldy, "%s: bad output slice", who);
+  a.ldy = ldy; a.ycoff = ycoff;
+  a.stats_slots = stats_slots(a.M);
   a.mul_h = SH; a.mul_w = SW; a.add_h = -PH; a.add_w = -PW; a.tap_sign = 1; a.sh_shift = 0; a.sw_shift = 0;
   return KOD_OK;
 }
 
-int kodhip_conv_fwd_raw(const void* x, const void* w_packed, void* y, float* stats,
-                        int B, int H, int W, int ldx, int xcoff, int Cin,
-                        int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
-                        int ldy, int ycoff, hipStream_t stream) {
-  ConvArgs a;
-  if (int rc = prep_fwd_raw(a, x, w_packed, y, stats, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff)) return rc;
-  return launch<MODE_RAW>(a, stream);
+int geo_dgrad(ConvArgs& a, int B, int H, int W, int ldx, int xcoff, int Cin, int N, int KH, int KW, int SH, int SW, int PH, int PW,
+              int Kp, int ldy, int ycoff, int accumulate) {
+  int Ho = (H + 2 * PH - KH) / SH + 1, Wo = (W + 2 * PW - KW) / SW + 1;
+  // gather source is dy (channels N per tap), output pixels are the input pixels of the forward conv
+  if (int rc = geo_common(a, "conv_dgrad", B, Ho, Wo, ldy, ycoff, N, H, W, Cin, KH, KW, Kp)) return rc;
+  if (int rc = geo_dx(a, "conv_dgrad", Cin, ldx, xcoff, accumulate)) return rc;
+  int ssh = ilog2_exact(SH), ssw = ilog2_exact(SW);
+  KOD_CHECK_ARG(ssh >= 0 && ssw >= 0, "conv_dgrad: stride must be a power of two");
+  a.mul_h = 1; a.mul_w = 1; a.add_h = PH; a.add_w = PW; a.tap_sign = -1; a.sh_shift = ssh; a.sw_shift = ssw;
+  return KOD_OK;
 }
 
-// Forward conv of an EVAL-mode conv+BN+act unit as one launch: out = act(conv(x, w) * scale + shift) (+ residual), the
-// BatchNorm constants applied to the fp32 accumulators (one bf16 rounding; with a residual a second one, of the sum of the
-// rounded activation and the residual - what the two-pass form rounds too).  No pre-BN tensor, no statistics.  Same
-// geometry, tiles and launch plan as kodhip_conv_fwd_raw (kodhip_conv_plan_query op 0 answers for both).  `out` must not
-// overlap `x` or `residual`: tiles are written while neighbouring tiles still read.
-int kodhip_conv_fwd_fused(const void* x, const void* w_packed, const float* scale, const float* shift,
-                          const void* residual, int ldr, int rcoff, void* out,
-                          int B, int H, int W, int ldx, int xcoff, int Cin,
-                          int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
-                          int ldo, int ocoff, int act, float slope, hipStream_t stream) {
-  ConvArgs a;
-  const void* fake = (const void*)64;        // prep_fwd_raw's output checks under its own name; replaced below
-  KOD_CHECK_ARG(scale && shift && out, "conv_fwd_fused: null scale / shift / output");
-  KOD_CHECK_ARG(act >= ACT_SILU && act <= ACT_IDENTITY, "conv_fwd_fused: bad activation %d", act);
-  KOD_CHECK_ARG(((uintptr_t)scale | (uintptr_t)shift) % 16 == 0, "conv_fwd_fused: scale / shift must be 16-byte aligned");
-  KOD_CHECK_ARG(N % 8 == 0 && ldo % 8 == 0 && ocoff % 8 == 0 && ocoff >= 0 && ocoff + N <= ldo, "conv_fwd_fused: bad output slice (N=%d ldo=%d off=%d)", N, ldo, ocoff);
-  KOD_CHECK_ARG(!residual || (ldr % 8 == 0 && rcoff % 8 == 0 && rcoff >= 0 && rcoff + N <= ldr),
-                "conv_fwd_fused: bad residual slice (N=%d ldr=%d off=%d)", N, ldr, rcoff);
-  if (int rc = prep_fwd_raw(a, x, w_packed, out, (float*)fake, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldo, ocoff)) {
-    char msg[448];                            // the shared geometry checks speak of "conv": name this entry point
-    snprintf(msg, sizeof(msg), "%s", kodhip_last_error());
-    kodhip_set_error("conv_fwd_fused: %s", msg);
-    return rc;
+// the four parity classes of a 3x3 / stride 2 / pad 1 data gradient (see kodhip_conv_dgrad_s2)
+int geo_dgrad_s2(ConvArgs cls[4], int B, int H, int W, int ldx, int xcoff, int Cin, int N, int ldy, int ycoff, int accumulate) {
+  KOD_CHECK_ARG(H % 2 == 0 && W % 2 == 0, "conv_dgrad_s2: input dims must be even");
+  const int Ho = H / 2, Wo = W / 2;
+  for (int c = 0; c < 4; ++c) {
+    const int py = c >> 1, px = c & 1;
+    const int KH = 1 + py, KW = 1 + px;
+    const int Kp = KH * KW * ((N + 31) / 32 * 32);
+    ConvArgs& a = cls[c];
+    // gather source dy [B,Ho,Wo,N]; class outputs form a Ho x Wo grid scattered into dx with stride 2
+    if (int rc = geo_common(a, "conv_dgrad_s2", B, Ho, Wo, ldy, ycoff, N, Ho, Wo, Cin, KH, KW, Kp)) return rc;
+    if (int rc = geo_dx(a, "conv_dgrad_s2", Cin, ldx, xcoff, accumulate)) return rc;
+    a.mul_h = 1; a.mul_w = 1; a.add_h = py; a.add_w = px; a.tap_sign = -1; a.sh_shift = 0; a.sw_shift = 0;
+    a.out_mul = 2; a.out_off_y = py; a.out_off_x = px; a.out_H = H; a.out_W = W;
   }
-  a.stats = nullptr;
-  a.scale = scale; a.shift = shift; a.residual = (const bf16_t*)residual; a.ldr = ldr; a.rcoff = rcoff;
-  a.act = act; a.slope = slope;
-  return act == ACT_SILU ? launch<MODE_FUSED>(a, stream) : launch<MODE_FUSED_ACT>(a, stream);
+  return KOD_OK;
 }
 
-// Fused detection head of one level: out[B][A][Ho*Wo][P] fp32 = 1x1 conv (N = A*(5+nc) packed as
-// box(4A) | obj(A) | cls(nc*A)) + bias.
-int kodhip_conv_fwd_head(const void* x, const void* w_packed, const float* bias, float* out,
-                         int B, int H, int W, int ldx, int xcoff, int Cin, int A, int nc, int Kp,
-                         hipStream_t stream) {
-  ConvArgs a = {};
-  int N = A * (5 + nc);
-  int rc = fill_common(a, x, w_packed, B, H, W, ldx, xcoff, Cin, H, W, N, 1, 1, Kp);
-  if (rc) return rc;
-  KOD_CHECK_ARG(bias && out && A > 0 && nc > 0, "conv_fwd_head: bad args");
-  a.bias = bias; a.head_out = out; a.head_A = A; a.head_P = 5 + nc; a.head_nc = nc; a.magic_hp = magic_u32((uint32_t)(5 + nc));
-  KOD_CHECK_ARG(5 + nc <= 128, "conv_fwd_head: at most 123 classes");
-  a.mul_h = 1; a.mul_w = 1; a.add_h = 0; a.add_w = 0; a.tap_sign = 1;
-  return launch<MODE_HEAD>(a, stream);
+// the same data gradient "folded": ONE stride-1 gather over the 2x2 dY neighbourhood {i, i+1} x {j, j+1} of the output
+// pixel block (2i..2i+1, 2j..2j+1) with N = 4 classes x Cin columns (class (py,px) uses tap (dy,dx) iff py >= dy and
+// px >= dx; the other weights are zero) and a depth-to-space epilogue.  16 tap-class products instead of 9, but dY is
+// staged once instead of 9/4 times, the K loop is 4x round_up(N,32) long for every tile, and the epilogue writes
+// both x parities of a pixel pair: the shallow layers (Cin <= 64), which are bound by staging / pipeline fill and
+// half-line stores and not by the MFMA, run 2x faster this way.
+int geo_dgrad_s2f(ConvArgs& a, int B, int H, int W, int ldx, int xcoff, int Cin, int N, int ldy, int ycoff, int accumulate) {
+  KOD_CHECK_ARG(H % 2 == 0 && W % 2 == 0, "conv_dgrad_s2f: input dims must be even");
+  const int Ho = H / 2, Wo = W / 2;
+  const int Kp = 4 * ((N + 31) / 32 * 32);
+  if (int rc = geo_common(a, "conv_dgrad_s2f", B, Ho, Wo, ldy, ycoff, N, Ho, Wo, 4 * Cin, 2, 2, Kp)) return rc;
+  if (int rc = geo_dx(a, "conv_dgrad_s2f", Cin, ldx, xcoff, accumulate)) return rc;
+  a.mul_h = 1; a.mul_w = 1; a.add_h = 0; a.add_w = 0; a.tap_sign = 1; a.sh_shift = 0; a.sw_shift = 0;
+  a.out_mul = 2; a.out_off_y = 0; a.out_off_x = 0; a.out_H = H; a.out_W = W; a.d2s_C = Cin;
+  a.d2s_skip = 1;
+  KOD_CHECK_ARG(fast_eligible(a), "conv_dgrad_s2f: needs the LDS-DMA path (operands within a 32-bit buffer range)");
+  return KOD_OK;
 }
 
-// ---- data gradient ---------------------------------------------------------------------------------------------
-}  // extern "C"
-
-namespace {
+int geo_dgrad_dual(ConvArgs& a, int B, int H, int W, int ldx, int xcoff, int Cin, int N, int Kp, int ldy, int ycoff, int accumulate) {
+  if (int rc = geo_dgrad(a, B, H, W, ldx, xcoff, Cin, N, 1, 1, 1, 1, 0, 0, Kp, ldy, ycoff, accumulate)) return rc;
+  KOD_CHECK_ARG(fast_eligible(a), "conv_dgrad_dual: needs the LDS-DMA path (operands within a 32-bit buffer range)");
+  a.nk1 = Kp / 32;
+  return KOD_OK;
+}
 
 struct BnRedSeg { int ch_begin, ch_count; const void* raw; int ldr; const float* aff; float* partials; };
+
+int bind_dgrad(ConvArgs& a, const void* dy, const void* w, void* dx, void* dx_f32) {
+  KOD_CHECK_ARG(dy && w && dx, "conv_dgrad: null pointer");
+  KOD_CHECK_ARG(a.f32_mode == 0 || a.f32_mode == 4 || dx_f32, "conv_dgrad: fp32 accumulation mode %d needs the fp32 shadow of dx", a.f32_mode);
+  a.x = (const bf16_t*)dy; a.w = (const bf16_t*)w; a.y = (bf16_t*)dx; a.y32 = (float*)dx_f32;
+  return KOD_OK;
+}
+
+int bind_dgrad_s2(ConvArgs cls[4], const void* dy, const void* w_dgrad_s2, void* dx, void* dx_f32) {
+  size_t woff = 0;                              // the four class packs lie back to back
+  for (int c = 0; c < 4; ++c) {
+    if (int rc = bind_dgrad(cls[c], dy, (const bf16_t*)w_dgrad_s2 + woff, dx, dx_f32)) return rc;
+    woff += (size_t)cls[c].N * cls[c].Kp;
+  }
+  return KOD_OK;
+}
+
+int bind_dgrad_dual(ConvArgs& a, const void* dy1, const void* w1, const void* dy2, const void* w2, void* dx, void* dx_f32) {
+  KOD_CHECK_ARG(dy2 && w2, "conv_dgrad_dual: null second source");
+  a.x2 = (const bf16_t*)dy2; a.w2 = (const bf16_t*)w2;
+  return bind_dgrad(a, dy1, w1, dx, dx_f32);
+}
 
 int set_segments(ConvArgs& a, const BnRedSeg* segs, int nseg, int slots, int out_channels) {
   KOD_CHECK_ARG(segs && nseg >= 1 && nseg <= MAX_SEG && slots > 0, "conv_dgrad_bnred: 1..%d segments and a slot count expected", MAX_SEG);
@@ -1597,113 +1655,91 @@ int set_segments(ConvArgs& a, const BnRedSeg* segs, int nseg, int slots, int out
   return KOD_OK;
 }
 
-// the `accumulate` argument of the data-gradient entry points: bit 0 = add to the bf16 partial already in dx (read-
-// modify-write, rounds twice); bits 8.. = f32_mode (ConvArgs) with dx_f32 = the output buffer's fp32 shadow
-int set_f32(ConvArgs& a, int accumulate, void* dx_f32) {
-  a.accumulate = accumulate & 1;
-  a.f32_mode = accumulate >> 8;
-  a.y32 = (float*)dx_f32;
-  KOD_CHECK_ARG(a.f32_mode >= 0 && a.f32_mode <= 4, "conv_dgrad: bad fp32 accumulation mode %d", a.f32_mode);
-  KOD_CHECK_ARG(a.f32_mode == 0 || a.f32_mode == 4 || dx_f32, "conv_dgrad: fp32 accumulation mode %d needs the fp32 shadow of dx", a.f32_mode);
-  return KOD_OK;
-}
-
-int prep_dgrad(ConvArgs& a, const void* dy, const void* w_dgrad, void* dx, int B, int H, int W, int ldx, int xcoff, int Cin,
-               int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp, int ldy, int ycoff, int accumulate,
-               void* dx_f32 = nullptr) {
-  a = ConvArgs{};
-  int Ho = (H + 2 * PH - KH) / SH + 1, Wo = (W + 2 * PW - KW) / SW + 1;
-  // gather source is dy (channels N per tap), output pixels are the input pixels of the forward conv
-  int rc = fill_common(a, dy, w_dgrad, B, Ho, Wo, ldy, ycoff, N, H, W, Cin, KH, KW, Kp);
-  if (rc) return rc;
-  KOD_CHECK_ARG(dx, "conv_dgrad: null output");
-  KOD_CHECK_ARG(Cin % 8 == 0 && ldx % 8 == 0 && xcoff % 8 == 0 && xcoff + Cin <= ldx, "conv_dgrad: bad output slice");
-  int ssh = ilog2_exact(SH), ssw = ilog2_exact(SW);
-  KOD_CHECK_ARG(ssh >= 0 && ssw >= 0, "conv_dgrad: stride must be a power of two");
-  a.y = (bf16_t*)dx; a.ldy = ldx; a.ycoff = xcoff;
-  if (int rc2 = set_f32(a, accumulate, dx_f32)) return rc2;
-  a.mul_h = 1; a.mul_w = 1; a.add_h = PH; a.add_w = PW; a.tap_sign = -1; a.sh_shift = ssh; a.sw_shift = ssw;
-  return KOD_OK;
-}
-
-// the four parity classes of a 3x3 / stride 2 / pad 1 data gradient (see kodhip_conv_dgrad_s2)
-int prep_dgrad_s2(ConvArgs cls[4], bool& all_fast, const void* dy, const void* w_dgrad_s2, void* dx, int B, int H, int W,
-                  int ldx, int xcoff, int Cin, int N, int ldy, int ycoff, int accumulate, void* dx_f32 = nullptr) {
-  KOD_CHECK_ARG(H % 2 == 0 && W % 2 == 0, "conv_dgrad_s2: input dims must be even");
-  const int Ho = H / 2, Wo = W / 2;
-  size_t woff = 0;
-  all_fast = !getenv("KODHIP_S2_SEPARATE");
-  for (int c = 0; c < 4; ++c) {
-    const int py = c >> 1, px = c & 1;
-    const int KH = 1 + py, KW = 1 + px;
-    const int Kp = KH * KW * ((N + 31) / 32 * 32);
-    ConvArgs& a = cls[c];
-    a = ConvArgs{};
-    // gather source dy [B,Ho,Wo,N]; class outputs form a Ho x Wo grid scattered into dx with stride 2
-    int rc = fill_common(a, dy, (const bf16_t*)w_dgrad_s2 + woff, B, Ho, Wo, ldy, ycoff, N, Ho, Wo, Cin, KH, KW, Kp);
-    if (rc) return rc;
-    KOD_CHECK_ARG(dx && Cin % 8 == 0 && ldx % 8 == 0 && xcoff % 8 == 0 && xcoff + Cin <= ldx, "conv_dgrad_s2: bad output slice");
-    a.y = (bf16_t*)dx; a.ldy = ldx; a.ycoff = xcoff;
-    if (int rc2 = set_f32(a, accumulate, dx_f32)) return rc2;
-    a.mul_h = 1; a.mul_w = 1; a.add_h = py; a.add_w = px; a.tap_sign = -1; a.sh_shift = 0; a.sw_shift = 0;
-    a.out_mul = 2; a.out_off_y = py; a.out_off_x = px; a.out_H = H; a.out_W = W;
-    all_fast = all_fast && fast_eligible(a);
-    woff += (size_t)Cin * Kp;
-  }
-  return KOD_OK;
-}
-
-// the same data gradient "folded": ONE stride-1 gather over the 2x2 dY neighbourhood {i, i+1} x {j, j+1} of the output
-// pixel block (2i..2i+1, 2j..2j+1) with N = 4 classes x Cin columns (class (py,px) uses tap (dy,dx) iff py >= dy and
-// px >= dx; the other weights are zero) and a depth-to-space epilogue.  16 tap-class products instead of 9, but dY is
-// staged once instead of 9/4 times, the K loop is 4x round_up(N,32) long for every tile, and the epilogue writes
-// both x parities of a pixel pair: the shallow layers (Cin <= 64), which are bound by staging / pipeline fill and
-// half-line stores and not by the MFMA, run 2x faster this way.
-int prep_dgrad_s2f(ConvArgs& a, const void* dy, const void* w_fold, void* dx, int B, int H, int W,
-                   int ldx, int xcoff, int Cin, int N, int ldy, int ycoff, int accumulate, void* dx_f32 = nullptr) {
-  KOD_CHECK_ARG(H % 2 == 0 && W % 2 == 0, "conv_dgrad_s2f: input dims must be even");
-  const int Ho = H / 2, Wo = W / 2;
-  const int Kp = 4 * ((N + 31) / 32 * 32);
-  a = ConvArgs{};
-  if (int rc = fill_common(a, dy, w_fold, B, Ho, Wo, ldy, ycoff, N, Ho, Wo, 4 * Cin, 2, 2, Kp)) return rc;
-  KOD_CHECK_ARG(dx && Cin % 8 == 0 && ldx % 8 == 0 && xcoff % 8 == 0 && xcoff + Cin <= ldx, "conv_dgrad_s2f: bad output slice");
-  a.y = (bf16_t*)dx; a.ldy = ldx; a.ycoff = xcoff;
-  if (int rc2 = set_f32(a, accumulate, dx_f32)) return rc2;
-  a.mul_h = 1; a.mul_w = 1; a.add_h = 0; a.add_w = 0; a.tap_sign = 1; a.sh_shift = 0; a.sw_shift = 0;
-  a.out_mul = 2; a.out_off_y = 0; a.out_off_x = 0; a.out_H = H; a.out_W = W; a.d2s_C = Cin;
-  a.d2s_skip = 1;
-  KOD_CHECK_ARG(fast_eligible(a), "conv_dgrad_s2f: needs the LDS-DMA path (operands within a 32-bit buffer range)");
-  return KOD_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
+// Per-channel partial slots of the statistics buffer: it must hold 2 * N * kodhip_conv_stats_slots(M, N) floats;
+// the kernel fills the slots it uses and zeroes the rest.
+int kodhip_conv_stats_slots(long M, int N) {
+  (void)N;
+  return stats_slots(M);
+}
+
+// Forward conv of a conv+BN+SiLU unit: y_raw[M][ldy] (bf16) + BatchNorm partials stats[2][N][slots].
+int kodhip_conv_fwd_raw(const void* x, const void* w_packed, void* y, float* stats, int B, int H, int W, int ldx, int xcoff,
+                        int Cin, int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp, int ldy, int ycoff,
+                        hipStream_t stream) {
+  ConvArgs a;
+  KOD_CHECK_ARG(x && w_packed && y && stats, "conv_fwd_raw: null pointer");
+  if (int rc = geo_fwd(a, "conv_fwd_raw", B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff)) return rc;
+  a.x = (const bf16_t*)x; a.w = (const bf16_t*)w_packed; a.y = (bf16_t*)y; a.stats = stats;
+  return launch<MODE_RAW>(&a, 1, stream);
+}
+
+// Forward conv of an EVAL-mode conv+BN+act unit as one launch: out = act(conv(x, w) * scale + shift) (+ residual), the
+// BatchNorm constants applied to the fp32 accumulators (one bf16 rounding; with a residual a second one, of the sum of the
+// rounded activation and the residual - what the two-pass form rounds too).  No pre-BN tensor, no statistics.  Same
+// geometry, tiles and launch plan as kodhip_conv_fwd_raw (kodhip_conv_plan_query op 0 answers for both).  `out` must not
+// overlap `x` or `residual`: tiles are written while neighbouring tiles still read.
+int kodhip_conv_fwd_fused(const void* x, const void* w_packed, const float* scale, const float* shift, const void* residual,
+                          int ldr, int rcoff, void* out, int B, int H, int W, int ldx, int xcoff, int Cin, int N, int KH, int KW,
+                          int SH, int SW, int PH, int PW, int Kp, int ldo, int ocoff, int act, float slope, hipStream_t stream) {
+  ConvArgs a;
+  KOD_CHECK_ARG(x && w_packed, "conv_fwd_fused: null pointer");
+  KOD_CHECK_ARG(scale && shift && out, "conv_fwd_fused: null scale / shift / output");
+  KOD_CHECK_ARG(act >= ACT_SILU && act <= ACT_IDENTITY, "conv_fwd_fused: bad activation %d", act);
+  KOD_CHECK_ARG(((uintptr_t)scale | (uintptr_t)shift) % 16 == 0, "conv_fwd_fused: scale / shift must be 16-byte aligned");
+  KOD_CHECK_ARG(N % 8 == 0 && ldo % 8 == 0 && ocoff % 8 == 0 && ocoff >= 0 && ocoff + N <= ldo, "conv_fwd_fused: bad output slice (N=%d ldo=%d off=%d)", N, ldo, ocoff);
+  KOD_CHECK_ARG(!residual || (ldr % 8 == 0 && rcoff % 8 == 0 && rcoff >= 0 && rcoff + N <= ldr),
+                "conv_fwd_fused: bad residual slice (N=%d ldr=%d off=%d)", N, ldr, rcoff);
+  if (int rc = geo_fwd(a, "conv_fwd_fused", B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldo, ocoff)) return rc;
+  a.x = (const bf16_t*)x; a.w = (const bf16_t*)w_packed; a.y = (bf16_t*)out;
+  a.scale = scale; a.shift = shift; a.residual = (const bf16_t*)residual; a.ldr = ldr; a.rcoff = rcoff;
+  a.act = act; a.slope = slope;
+  return act == ACT_SILU ? launch<MODE_FUSED>(&a, 1, stream) : launch<MODE_FUSED_ACT>(&a, 1, stream);
+}
+
+// Fused detection head of one level: out[B][A][Ho*Wo][P] fp32 = 1x1 conv (N = A*(5+nc) packed as
+// box(4A) | obj(A) | cls(nc*A)) + bias.
+int kodhip_conv_fwd_head(const void* x, const void* w_packed, const float* bias, float* out, int B, int H, int W, int ldx,
+                         int xcoff, int Cin, int A, int nc, int Kp, hipStream_t stream) {
+  ConvArgs a;
+  KOD_CHECK_ARG(x && w_packed, "conv_fwd_head: null pointer");
+  if (int rc = geo_common(a, "conv_fwd_head", B, H, W, ldx, xcoff, Cin, H, W, A * (5 + nc), 1, 1, Kp)) return rc;
+  KOD_CHECK_ARG(bias && out && A > 0 && nc > 0, "conv_fwd_head: bad args");
+  KOD_CHECK_ARG(5 + nc <= 128, "conv_fwd_head: at most 123 classes");
+  a.x = (const bf16_t*)x; a.w = (const bf16_t*)w_packed; a.bias = bias; a.head_out = out;
+  a.head_A = A; a.head_P = 5 + nc; a.head_nc = nc; a.magic_hp = magic_u32((uint32_t)(5 + nc));
+  a.mul_h = 1; a.mul_w = 1; a.add_h = 0; a.add_w = 0; a.tap_sign = 1;
+  return launch<MODE_HEAD>(&a, 1, stream);
+}
+
+// ---- data gradient ---------------------------------------------------------------------------------------------
 // Data gradient: dx[B][H][W][ldx](+xcoff, Cin channels) (+)= conv_transpose(dy[B][Ho][Wo][ldy](+ycoff, N), w).
 // w_dgrad is packed [Cin][Kp] with k = (kh, kw, n).
-int kodhip_conv_dgrad(const void* dy, const void* w_dgrad, void* dx,
-                      int B, int H, int W, int ldx, int xcoff, int Cin,
-                      int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
-                      int ldy, int ycoff, int accumulate, void* dx_f32, hipStream_t stream) {
+int kodhip_conv_dgrad(const void* dy, const void* w_dgrad, void* dx, int B, int H, int W, int ldx, int xcoff, int Cin, int N,
+                      int KH, int KW, int SH, int SW, int PH, int PW, int Kp, int ldy, int ycoff, int accumulate, void* dx_f32,
+                      hipStream_t stream) {
   ConvArgs a;
-  if (int rc = prep_dgrad(a, dy, w_dgrad, dx, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff, accumulate, dx_f32)) return rc;
-  return launch<MODE_PLAIN>(a, stream);
+  if (int rc = geo_dgrad(a, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff, accumulate)) return rc;
+  if (int rc = bind_dgrad(a, dy, w_dgrad, dx, dx_f32)) return rc;
+  return launch<MODE_PLAIN>(&a, 1, stream);
 }
 
 // Data gradient of a 3x3 / stride 2 / pad 1 convolution, decomposed by output-pixel parity: class (py,px)
 // only meets taps kh = 1 (py=0) or kh in {0,2} (py=1) (same for kw), so the four classes are stride-1 gathers
 // with 1, 2, 2 and 4 taps - 9 taps of MFMA work instead of 36.  w_dgrad_s2 holds the four class packs
 // back to back: class c = 2*py+px is [Cin][Kdp_c], Kdp_c = ntaps_c * round_up(N, 32), k = (kh', kw', n) tap-major.
-int kodhip_conv_dgrad_s2(const void* dy, const void* w_dgrad_s2, void* dx,
-                         int B, int H, int W, int ldx, int xcoff, int Cin, int N,
+int kodhip_conv_dgrad_s2(const void* dy, const void* w_dgrad_s2, void* dx, int B, int H, int W, int ldx, int xcoff, int Cin, int N,
                          int ldy, int ycoff, int accumulate, void* dx_f32, hipStream_t stream) {
   ConvArgs cls[4];
-  bool all_fast;
-  if (int rc = prep_dgrad_s2(cls, all_fast, dy, w_dgrad_s2, dx, B, H, W, ldx, xcoff, Cin, N, ldy, ycoff, accumulate, dx_f32)) return rc;
-  if (all_fast) return launch_x4<MODE_PLAIN>(cls, stream);
+  ConvPlan p;
+  if (int rc = geo_dgrad_s2(cls, B, H, W, ldx, xcoff, Cin, N, ldy, ycoff, accumulate)) return rc;
+  if (int rc = bind_dgrad_s2(cls, dy, w_dgrad_s2, dx, dx_f32)) return rc;
+  if (conv_plan_x4(cls, p)) return launch<MODE_PLAIN>(cls, 4, stream);
   for (int c = 0; c < 4; ++c)
-    if (int rc = launch<MODE_PLAIN>(cls[c], stream)) return rc;
+    if (int rc = launch<MODE_PLAIN>(cls + c, 1, stream)) return rc;
   return KOD_OK;
 }
 
@@ -1711,72 +1747,42 @@ int kodhip_conv_dgrad_s2(const void* dy, const void* w_dgrad_s2, void* dx,
 // 1 = folded (kodhip_conv_dgrad_s2f, pack mode 3), 0 = parity classes (kodhip_conv_dgrad_s2, pack mode 2).
 // KODHIP_S2_FOLD_MAXC overrides the channel threshold (0 = never fold).
 int kodhip_conv_dgrad_s2_folded(int Cin, int N) {
-  static int maxc = -1;
-  if (maxc < 0) { const char* e = getenv("KODHIP_S2_FOLD_MAXC"); maxc = e ? atoi(e) : 64; }
   (void)N;
-  return Cin <= maxc ? 1 : 0;
+  return Cin <= conv_knobs().s2_fold_maxc ? 1 : 0;
 }
 
-// Folded form of kodhip_conv_dgrad_s2 (see prep_dgrad_s2f).  w_fold: [4 * Cin][4 * round_up(N, 32)], row = class * Cin
+// Folded form of kodhip_conv_dgrad_s2 (see geo_dgrad_s2f).  w_fold: [4 * Cin][4 * round_up(N, 32)], row = class * Cin
 // + ci (class = 2 * py + px), k = (dy * 2 + dx) * round_up(N, 32) + n.
-int kodhip_conv_dgrad_s2f(const void* dy, const void* w_fold, void* dx,
-                          int B, int H, int W, int ldx, int xcoff, int Cin, int N,
+int kodhip_conv_dgrad_s2f(const void* dy, const void* w_fold, void* dx, int B, int H, int W, int ldx, int xcoff, int Cin, int N,
                           int ldy, int ycoff, int accumulate, void* dx_f32, hipStream_t stream) {
   ConvArgs a;
-  if (int rc = prep_dgrad_s2f(a, dy, w_fold, dx, B, H, W, ldx, xcoff, Cin, N, ldy, ycoff, accumulate, dx_f32)) return rc;
-  return launch<MODE_PLAIN>(a, stream);
+  if (int rc = geo_dgrad_s2f(a, B, H, W, ldx, xcoff, Cin, N, ldy, ycoff, accumulate)) return rc;
+  if (int rc = bind_dgrad(a, dy, w_fold, dx, dx_f32)) return rc;
+  return launch<MODE_PLAIN>(&a, 1, stream);
 }
 
-int kodhip_conv_dgrad_s2f_bnred_slots(int B, int H, int W, int Cin, int N, int ldy) {
-  const void* fake = (const void*)64;
-  if (getenv("KODHIP_NO_BNRED")) return 0;
-  ConvArgs a;
-  if (prep_dgrad_s2f(a, fake, fake, (void*)fake, B, H, W, Cin, 0, Cin, N, ldy, 0, 0)) return 0;
-  return 4 * make_plan(a.M, a.N, a.K, true).groups_m;
-}
-
-int kodhip_conv_dgrad_s2f_bnred(const void* dy, const void* w_fold, void* dx,
-                                int B, int H, int W, int ldx, int xcoff, int Cin, int N,
-                                int ldy, int ycoff, int accumulate, void* dx_f32, const void* segments, int nseg, int slots,
+int kodhip_conv_dgrad_s2f_bnred(const void* dy, const void* w_fold, void* dx, int B, int H, int W, int ldx, int xcoff, int Cin,
+                                int N, int ldy, int ycoff, int accumulate, void* dx_f32, const void* segments, int nseg, int slots,
                                 hipStream_t stream) {
   ConvArgs a;
-  if (int rc = prep_dgrad_s2f(a, dy, w_fold, dx, B, H, W, ldx, xcoff, Cin, N, ldy, ycoff, accumulate, dx_f32)) return rc;
+  if (int rc = geo_dgrad_s2f(a, B, H, W, ldx, xcoff, Cin, N, ldy, ycoff, accumulate)) return rc;
+  if (int rc = bind_dgrad(a, dy, w_fold, dx, dx_f32)) return rc;
   if (int rc = set_segments(a, (const BnRedSeg*)segments, nseg, slots, Cin)) return rc;
-  return launch<MODE_PLAIN_BN>(a, stream);
+  return launch<MODE_PLAIN_BN>(&a, 1, stream);
 }
 
 // ---- data gradient + BatchNorm-backward reduction of the units whose output gradient this launch completes.
 // The launch must be the LAST writer of dx's channel ranges named by the segments; per segment it leaves
 // partials[2][ch_count][slots] = per-block sums of dz and dz*y (dz = dx * silu'(y*scale + shift)), which
 // kodhip_bn_bwd_coeffs_partials(..., raw_moment = 1) turns into the BatchNorm-backward coefficients.
-// *_slots: slots a launch of this geometry writes (allocate partials with exactly that many); 0 = this geometry
-// cannot carry the fused reduction (run kodhip_bn_silu_bwd_reduce instead).  stride2 = the 3x3/s2/p1 form.
-int kodhip_conv_dgrad_bnred_slots(int B, int H, int W, int Cin, int N, int KH, int KW, int SH, int SW, int PH, int PW,
-                                  int ldy, int stride2) {
-  const void* fake = (const void*)64;      // never dereferenced: only the launch plan is computed
-  if (getenv("KODHIP_NO_BNRED")) return 0;
-  if (stride2) {
-    ConvArgs cls[4];
-    bool all_fast;
-    if (prep_dgrad_s2(cls, all_fast, fake, fake, (void*)fake, B, H, W, Cin, 0, Cin, N, ldy, 0, 0) || !all_fast) return 0;
-    return 4 * plan_x4(cls).groups_m;
-  }
+int kodhip_conv_dgrad_bnred(const void* dy, const void* w_dgrad, void* dx, int B, int H, int W, int ldx, int xcoff, int Cin, int N,
+                            int KH, int KW, int SH, int SW, int PH, int PW, int Kp, int ldy, int ycoff, int accumulate,
+                            void* dx_f32, const void* segments, int nseg, int slots, hipStream_t stream) {
   ConvArgs a;
-  const int Kp = KH * KW * ((N + 31) / 32 * 32);
-  if (prep_dgrad(a, fake, fake, (void*)fake, B, H, W, Cin, 0, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, 0, 0) || !fast_eligible(a)) return 0;
-  bool row3;
-  return plan_conv(a, true, row3).groups_m;
-}
-
-int kodhip_conv_dgrad_bnred(const void* dy, const void* w_dgrad, void* dx,
-                            int B, int H, int W, int ldx, int xcoff, int Cin,
-                            int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
-                            int ldy, int ycoff, int accumulate, void* dx_f32, const void* segments, int nseg, int slots,
-                            hipStream_t stream) {
-  ConvArgs a;
-  if (int rc = prep_dgrad(a, dy, w_dgrad, dx, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff, accumulate, dx_f32)) return rc;
+  if (int rc = geo_dgrad(a, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff, accumulate)) return rc;
+  if (int rc = bind_dgrad(a, dy, w_dgrad, dx, dx_f32)) return rc;
   if (int rc = set_segments(a, (const BnRedSeg*)segments, nseg, slots, Cin)) return rc;
-  return launch<MODE_PLAIN_BN>(a, stream);
+  return launch<MODE_PLAIN_BN>(&a, 1, stream);
 }
 
 // ---- data gradient of TWO pointwise convs that read the same tensor (a CSP layer's main_conv and short_conv,
@@ -1785,94 +1791,84 @@ int kodhip_conv_dgrad_bnred(const void* dy, const void* w_dgrad, void* dx,
 // read-modified-written by a second launch.  1x1 / stride 1 / no padding; dy1, dy2: [B*H*W][ldy] (+ycoff, N channels
 // each); w1, w2: [Cin][Kp] dgrad packs (Kp = round_up(N, 32)).  *_bnred: also the BatchNorm-backward reduction of the
 // units whose output gradient dx completes (see kodhip_conv_dgrad_bnred).
-static int prep_dgrad_dual(ConvArgs& a, const void* dy1, const void* w1, const void* dy2, const void* w2, void* dx,
-                           int B, int H, int W, int ldx, int xcoff, int Cin, int N, int Kp, int ldy, int ycoff, int accumulate,
-                           void* dx_f32 = nullptr) {
-  if (int rc = prep_dgrad(a, dy1, w1, dx, B, H, W, ldx, xcoff, Cin, N, 1, 1, 1, 1, 0, 0, Kp, ldy, ycoff, accumulate, dx_f32)) return rc;
-  KOD_CHECK_ARG(dy2 && w2, "conv_dgrad_dual: null second source");
-  KOD_CHECK_ARG(fast_eligible(a), "conv_dgrad_dual: needs the LDS-DMA path (operands within a 32-bit buffer range)");
-  a.x2 = (const bf16_t*)dy2; a.w2 = (const bf16_t*)w2; a.nk1 = Kp / 32;
-  return KOD_OK;
+int kodhip_conv_dgrad_dual(const void* dy1, const void* w1, const void* dy2, const void* w2, void* dx, int B, int H, int W, int ldx,
+                           int xcoff, int Cin, int N, int Kp, int ldy, int ycoff, int accumulate, void* dx_f32,
+                           hipStream_t stream) {
+  ConvArgs a;
+  if (int rc = geo_dgrad_dual(a, B, H, W, ldx, xcoff, Cin, N, Kp, ldy, ycoff, accumulate)) return rc;
+  if (int rc = bind_dgrad_dual(a, dy1, w1, dy2, w2, dx, dx_f32)) return rc;
+  return launch<MODE_PLAIN>(&a, 1, stream);
 }
 
-int kodhip_conv_dgrad_dual(const void* dy1, const void* w1, const void* dy2, const void* w2, void* dx,
-                           int B, int H, int W, int ldx, int xcoff, int Cin, int N, int Kp, int ldy, int ycoff,
-                           int accumulate, void* dx_f32, hipStream_t stream) {
+int kodhip_conv_dgrad_dual_bnred(const void* dy1, const void* w1, const void* dy2, const void* w2, void* dx, int B, int H, int W,
+                                 int ldx, int xcoff, int Cin, int N, int Kp, int ldy, int ycoff, int accumulate, void* dx_f32,
+                                 const void* segments, int nseg, int slots, hipStream_t stream) {
   ConvArgs a;
-  if (int rc = prep_dgrad_dual(a, dy1, w1, dy2, w2, dx, B, H, W, ldx, xcoff, Cin, N, Kp, ldy, ycoff, accumulate, dx_f32)) return rc;
-  return launch<MODE_PLAIN>(a, stream);
-}
-
-int kodhip_conv_dgrad_dual_bnred_slots(int B, int H, int W, int Cin, int N, int ldy) {
-  const void* fake = (const void*)64;
-  if (getenv("KODHIP_NO_BNRED")) return 0;
-  ConvArgs a;
-  const int Kp = (N + 31) / 32 * 32;
-  if (prep_dgrad_dual(a, fake, fake, fake, fake, (void*)fake, B, H, W, Cin, 0, Cin, N, Kp, ldy, 0, 0)) return 0;
-  return make_plan(a.M, a.N, 2 * a.K, true).groups_m;
-}
-
-int kodhip_conv_dgrad_dual_bnred(const void* dy1, const void* w1, const void* dy2, const void* w2, void* dx,
-                                 int B, int H, int W, int ldx, int xcoff, int Cin, int N, int Kp, int ldy, int ycoff,
-                                 int accumulate, void* dx_f32, const void* segments, int nseg, int slots, hipStream_t stream) {
-  ConvArgs a;
-  if (int rc = prep_dgrad_dual(a, dy1, w1, dy2, w2, dx, B, H, W, ldx, xcoff, Cin, N, Kp, ldy, ycoff, accumulate, dx_f32)) return rc;
+  if (int rc = geo_dgrad_dual(a, B, H, W, ldx, xcoff, Cin, N, Kp, ldy, ycoff, accumulate)) return rc;
+  if (int rc = bind_dgrad_dual(a, dy1, w1, dy2, w2, dx, dx_f32)) return rc;
   if (int rc = set_segments(a, (const BnRedSeg*)segments, nseg, slots, Cin)) return rc;
-  return launch<MODE_PLAIN_BN>(a, stream);
+  return launch<MODE_PLAIN_BN>(&a, 1, stream);
 }
 
-int kodhip_conv_dgrad_s2_bnred(const void* dy, const void* w_dgrad_s2, void* dx,
-                               int B, int H, int W, int ldx, int xcoff, int Cin, int N,
-                               int ldy, int ycoff, int accumulate, void* dx_f32, const void* segments, int nseg, int slots,
+int kodhip_conv_dgrad_s2_bnred(const void* dy, const void* w_dgrad_s2, void* dx, int B, int H, int W, int ldx, int xcoff, int Cin,
+                               int N, int ldy, int ycoff, int accumulate, void* dx_f32, const void* segments, int nseg, int slots,
                                hipStream_t stream) {
   ConvArgs cls[4];
-  bool all_fast;
-  if (int rc = prep_dgrad_s2(cls, all_fast, dy, w_dgrad_s2, dx, B, H, W, ldx, xcoff, Cin, N, ldy, ycoff, accumulate, dx_f32)) return rc;
-  KOD_CHECK_ARG(all_fast, "conv_dgrad_s2_bnred: this geometry cannot carry the fused reduction (query the slots first)");
+  if (int rc = geo_dgrad_s2(cls, B, H, W, ldx, xcoff, Cin, N, ldy, ycoff, accumulate)) return rc;
+  if (int rc = bind_dgrad_s2(cls, dy, w_dgrad_s2, dx, dx_f32)) return rc;
   for (int c = 0; c < 4; ++c)
     if (int rc = set_segments(cls[c], (const BnRedSeg*)segments, nseg, slots, Cin)) return rc;
-  return launch_x4<MODE_PLAIN_BN>(cls, stream);
+  return launch<MODE_PLAIN_BN>(cls, 4, stream);      // the fused reduction of the classes exists in the merged launch only
 }
 
-// Read-only view of the launch plan (tests assert which kernel a case reaches; nothing is launched, no pointer is read).
-// The geometry is taken as the entry point named by `op` takes it: 0 kodhip_conv_fwd_raw, 1 kodhip_conv_dgrad,
-// 2 kodhip_conv_dgrad_s2, 3 kodhip_conv_dgrad_s2f, 4 kodhip_conv_dgrad_dual (ops 2..4 ignore KH .. PW; op 2 and 3 ignore Kp).
-// out = {bm, bn, row3, fast, tiles_m, tiles_n, groups_m, bm of the merged four-class launch or 0 when the launch is not
-// merged}; op 2 without the merged launch (KODHIP_S2_SEPARATE, a class off the FAST path) reports the four-tap class.
-int kodhip_conv_plan_query(int op, int B, int H, int W, int ldx, int xcoff, int Cin,
-                           int N, int KH, int KW, int SH, int SW, int PH, int PW, int Kp,
-                           int ldy, int ycoff, int* out) {
-  KOD_CHECK_ARG(out, "conv_plan_query: null output");
-  void* fake = (void*)64;                   // never dereferenced
-  ConvArgs a;
-  Plan p;
-  bool fast = true, row3 = false;
-  int merged = 0;
-  if (op == 2) {
-    ConvArgs cls[4];
-    bool all_fast;
-    if (int rc = prep_dgrad_s2(cls, all_fast, fake, fake, fake, B, H, W, ldx, xcoff, Cin, N, ldy, ycoff, 0)) return rc;
-    if (all_fast) {
-      p = plan_x4(cls);
-      merged = p.bm;
-    } else {
-      fast = fast_eligible(cls[3]);
-      p = plan_conv(cls[3], fast, row3);
-    }
-  } else {
-    int rc = KOD_OK;
-    KOD_CHECK_ARG(op >= 0 && op <= 4, "conv_plan_query: bad op %d", op);
-    if (op == 0) rc = prep_fwd_raw(a, fake, fake, fake, (float*)fake, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff);
-    else if (op == 1) rc = prep_dgrad(a, fake, fake, fake, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff, 0);
-    else if (op == 3) rc = prep_dgrad_s2f(a, fake, fake, fake, B, H, W, ldx, xcoff, Cin, N, ldy, ycoff, 0);
-    else rc = prep_dgrad_dual(a, fake, fake, fake, fake, fake, B, H, W, ldx, xcoff, Cin, N, Kp, ldy, ycoff, 0);
-    if (rc) return rc;
-    fast = fast_eligible(a);
-    p = plan_conv(a, fast, row3);
-  }
-  out[0] = p.bm; out[1] = p.bn; out[2] = row3 ? 1 : 0; out[3] = fast ? 1 : 0;
-  out[4] = p.tiles_m; out[5] = p.tiles_n; out[6] = p.groups_m; out[7] = merged;
+// The plan of the entry point named by `op`, from the geometry as that entry point takes it: 0 kodhip_conv_fwd_raw, 1 kodhip_conv_dgrad,
+// 2 kodhip_conv_dgrad_s2, 3 kodhip_conv_dgrad_s2f, 4 kodhip_conv_dgrad_dual (ops 2..4 ignore KH .. PW; op 2 and 3 ignore Kp).  Op 2
+// without the merged launch (KODHIP_S2_SEPARATE, a class off the FAST path) gives the four-tap class.
+static int op_plan(ConvPlan& p, int op, int B, int H, int W, int ldx, int xcoff, int Cin, int N, int KH, int KW, int SH, int SW, int PH,
+                   int PW, int Kp, int ldy, int ycoff) {
+  KOD_CHECK_ARG(op >= 0 && op <= 4, "conv_plan_query: bad op %d", op);
+  ConvArgs a, cls[4];
+  int rc;
+  if (op == 0) rc = geo_fwd(a, "conv_fwd_raw", B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff);
+  else if (op == 1) rc = geo_dgrad(a, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff, 0);
+  else if (op == 2) rc = geo_dgrad_s2(cls, B, H, W, ldx, xcoff, Cin, N, ldy, ycoff, 0);
+  else if (op == 3) rc = geo_dgrad_s2f(a, B, H, W, ldx, xcoff, Cin, N, ldy, ycoff, 0);
+  else rc = geo_dgrad_dual(a, B, H, W, ldx, xcoff, Cin, N, Kp, ldy, ycoff, 0);
+  if (rc) return rc;
+  if (op != 2 || !conv_plan_x4(cls, p)) p = conv_plan(op == 2 ? cls[3] : a, op == 0 ? MODE_RAW : MODE_PLAIN);
   return KOD_OK;
+}
+
+// Read-only view of the launch plan (tests assert which kernel a case reaches; nothing is launched, no pointer is read): op and
+// geometry as op_plan takes them.  out = {bm, bn, row3, fast, tiles_m, tiles_n, groups_m, bm of the merged four-class launch or 0
+// when the launch is not merged}.
+int kodhip_conv_plan_query(int op, int B, int H, int W, int ldx, int xcoff, int Cin, int N, int KH, int KW, int SH, int SW, int PH,
+                           int PW, int Kp, int ldy, int ycoff, int* out) {
+  KOD_CHECK_ARG(out, "conv_plan_query: null output");
+  ConvPlan p;
+  if (int rc = op_plan(p, op, B, H, W, ldx, xcoff, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, ycoff)) return rc;
+  out[0] = p.bm; out[1] = p.bn; out[2] = p.form == CONV_ROW3 ? 1 : 0; out[3] = p.fast ? 1 : 0;
+  out[4] = p.tiles_m; out[5] = p.tiles_n; out[6] = p.groups_m; out[7] = p.form == CONV_X4 ? p.bm : 0;
+  return KOD_OK;
+}
+
+// *_slots: slots a *_bnred launch of this geometry writes (allocate partials with exactly that many); 0 = this geometry cannot carry
+// the fused reduction (run kodhip_bn_silu_bwd_reduce instead).  stride2 = the 3x3/s2/p1 form, whose reduction exists in the merged
+// launch only.  The geometry is that of a contiguous dx: no plan depends on dx's row stride or channel offset.
+static int bnred_slots(int op, int B, int H, int W, int Cin, int N, int KH, int KW, int SH, int SW, int PH, int PW, int ldy) {
+  ConvPlan p;
+  const int Kp = (op == 4 ? 1 : KH * KW) * ((N + 31) / 32 * 32);
+  if (conv_knobs().no_bnred || op_plan(p, op, B, H, W, Cin, 0, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, 0)) return 0;
+  return op == 2 && p.form != CONV_X4 ? 0 : p.bnred_slots;
+}
+int kodhip_conv_dgrad_bnred_slots(int B, int H, int W, int Cin, int N, int KH, int KW, int SH, int SW, int PH, int PW, int ldy, int stride2) {
+  return bnred_slots(stride2 ? 2 : 1, B, H, W, Cin, N, KH, KW, SH, SW, PH, PW, ldy);
+}
+int kodhip_conv_dgrad_s2f_bnred_slots(int B, int H, int W, int Cin, int N, int ldy) {
+  return bnred_slots(3, B, H, W, Cin, N, 3, 3, 2, 2, 1, 1, ldy);
+}
+int kodhip_conv_dgrad_dual_bnred_slots(int B, int H, int W, int Cin, int N, int ldy) {
+  return bnred_slots(4, B, H, W, Cin, N, 1, 1, 1, 1, 0, 0, ldy);
 }
 
 }  // extern "C"

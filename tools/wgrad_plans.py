@@ -8,11 +8,20 @@ A conv row is [B, H, W, ldx, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, dual] -> t
 {tn, tk, row3, wn, rn, wc, splits, dma} + splits_geo (dual = 0) or dual_splits (dual = 1); a stem row is [B, H, Wp, N] -> blocks.
 The file keeps the default table in full and, per knob setting, only the rows whose answer differs from the default one.
 
+The same machinery records csrc/conv_igemm.hip's plans (forward, data gradients): tests/golden/conv_plans.json.gz, asserted by
+tests/test_conv_plans.py.  There a conv row is [B, H, W, ldx, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, op] (op as
+kodhip_conv_plan_query takes it, channel offsets 0) -> [0, the eight plan_query outputs {bm, bn, row3, fast, tiles_m, tiles_n,
+groups_m, merged}, the op's slot query], or [return code] alone where the query refuses; the second list ("fold" in place of
+"stem") is [Cin, N] -> kodhip_conv_dgrad_s2_folded.  The file says which table it holds ("table": "conv"; none = this one).
+A file whose name ends in .gz is the same JSON text gzip-compressed (the conv table is 290 KB of integers as text, 60 KB so).
+
 usage:  python tools/wgrad_plans.py --record tests/golden/wgrad_plans.json      (every knob setting in a child process: a knob
                                                                                 is read once per process)
+        python tools/wgrad_plans.py --record-conv tests/golden/conv_plans.json.gz
         python tools/wgrad_plans.py --eval FILE                                 this process' answers for FILE's rows, as JSON
 """
 import ctypes as C
+import gzip
 import json
 import os
 import subprocess
@@ -30,6 +39,24 @@ SETTINGS = {
     "row3_slots_1536": {"KODHIP_WGRAD_ROW3_SLOTS": "1536"},
     "stem_tw_160": {"KODHIP_STEM_BWD_TW": "160"},
 }
+CONV_KNOBS = ("KODHIP_FORCE_BN", "KODHIP_FORCE_BM", "KODHIP_ROW3", "KODHIP_NO_FAST", "KODHIP_S2_SEPARATE", "KODHIP_S2_FOLD_MAXC",
+              "KODHIP_NO_BNRED")
+CONV_SETTINGS = {
+    "default": {},
+    "row3_off": {"KODHIP_ROW3": "0"},
+    "row3_128": {"KODHIP_ROW3": "1"},
+    "no_fast": {"KODHIP_NO_FAST": "1"},
+    "force_bn_32": {"KODHIP_FORCE_BN": "32"},
+    "force_bn_64": {"KODHIP_FORCE_BN": "64"},
+    "force_bn_128": {"KODHIP_FORCE_BN": "128"},
+    "force_bm_128": {"KODHIP_FORCE_BM": "128"},
+    "force_bm_256": {"KODHIP_FORCE_BM": "256"},
+    "s2_separate": {"KODHIP_S2_SEPARATE": "1"},
+    "no_bnred": {"KODHIP_NO_BNRED": "1"},
+    "s2_fold_never": {"KODHIP_S2_FOLD_MAXC": "0"},
+}
+# per table: (knob settings, key of the file's second row list)
+TABLES = {"wgrad": (SETTINGS, "stem"), "conv": (CONV_SETTINGS, "fold")}
 pad = lambda v, m: (v + m - 1) // m * m
 
 
@@ -116,11 +143,115 @@ def all_rows():
     return uniq(conv), uniq(stem)
 
 
+# ------------------------------------------------------------------ the rows, read for csrc/conv_igemm.hip's entry points
+def igemm_rows(conv):
+    """the rows above as kodhip_conv_plan_query takes them.  A row above names the forward layer; each entry point has its own Kp
+    = taps x round_up(channels per tap, 32): the forward's per Cin, the data gradient's per N.  -> (conv rows, fold rows)"""
+    rows, fold = [], []
+    for B, H, W, ldx, Cin, N, KH, KW, SH, SW, PH, PW, _, ldy, dual in conv:
+        if (ldx, Cin, KH, KW) == (8, 8, 6, 3):                     # the stem: op 0 in its wide-pixel form
+            rows.append([B, H, W, 8, 32, N, 6, 1, 2, 1, 2, 1, 192, ldy, 0])
+        elif dual:
+            rows.append([B, H, W, ldx, Cin, N, 1, 1, 1, 1, 0, 0, pad(N, 32), ldy, 4])
+        else:
+            geo = [KH, KW, SH, SW, PH, PW]
+            rows.append([B, H, W, ldx, Cin, N] + geo + [KH * KW * pad(Cin, 32), ldy, 0])
+            rows.append([B, H, W, ldx, Cin, N] + geo + [KH * KW * pad(N, 32), ldy, 1])
+            if geo == [3, 3, 2, 2, 1, 1] and H % 2 == 0 and W % 2 == 0:
+                rows += [[B, H, W, ldx, Cin, N] + geo + [0, ldy, 2], [B, H, W, ldx, Cin, N] + geo + [0, ldy, 3]]
+                fold.append([Cin, N])
+    return rows, fold
+
+
+def igemm_hand_rows():
+    """the hand cases of tests/test_hip_conv_exact.py (with the ops each names), the geometries of tests/test_hip_conv_fused.py
+    and the conv half of tests/test_abi.py::test_plan_queries_launch_nothing"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, ROOT)
+    import fused_reference as fr
+    import test_hip_conv_exact as t
+
+    def q(op, B, Cin, H, W, N, k, s, p):
+        Kp = {0: k * k * pad(Cin, 32), 1: k * k * pad(N, 32), 2: 0, 3: 0, 4: pad(N, 32)}[op]
+        return [B, H, W, Cin, Cin, N, k, k, s, s, p, p, Kp, N, op]
+    rows = []
+    for c in list(t.CASES.values()) + list(t.CASES_ROW3_OFF.values()):
+        rows += [q("fdco".index(o), *c[:8]) for o in c[8] if o in "fdco"]
+    rows += [q(0, *c[0]) for c in fr.CASES.values()]
+    for N, B, H, W, _ in list(t.STEM_CASES) + list(fr.STEM_CASES):
+        rows.append([B, H, W // 2, 8, 32, N, 6, 1, 2, 1, 2, 1, 192, N, 0])
+    rows += [q(0, 1, 512, 128, 128, 64, 1, 1, 0), q(0, 1, 512, 127, 128, 64, 1, 1, 0), q(0, 1, 480, 128, 128, 64, 1, 1, 0),
+             q(0, 1, 512, 128, 128, 32, 1, 1, 0), q(0, 5, 64, 60, 56, 160, 3, 1, 1), q(2, 4, 64, 128, 128, 128, 3, 2, 1),
+             q(1, 4, 64, 128, 128, 128, 3, 2, 1), q(3, 2, 32, 16, 16, 64, 3, 2, 1), q(0, 1, 32, 130, 128, 512, 3, 1, 1)]
+    conv, fold = igemm_rows(hand_rows()[0])
+    return rows + conv, fold
+
+
+def igemm_boundary_rows():
+    """M on both sides of 256 * 64, K on both sides of 512 and N at every boundary of the tile rule, as pointwise and 3x3 layers in
+    ops 0 and 1 and as stride-2 layers in ops 2 and 3; the dual form over the same N; the rows above (beyond the 32-bit buffer
+    range among them)"""
+    rows, fold = igemm_rows(boundary_rows()[0])
+    widths = (32, 33, 40, 64, 65, 72, 96, 128, 129, 136, 192, 256)
+    for H in (127, 128):                                        # M = 16256 | 16384
+        for K in (480, 512):
+            for N in widths:
+                rows += [[1, H, 128, K, K, N, 1, 1, 1, 1, 0, 0, K, pad(N, 8), 0],
+                         [1, H, 128, pad(N, 8), N, K, 1, 1, 1, 1, 0, 0, K, K, 1],
+                         [1, H, 128, pad(N, 8), N, K // 2, 1, 1, 1, 1, 0, 0, pad(K // 2, 32), K // 2, 4]]
+    for H in (126, 128):
+        for C in (32, 64):                                      # K = 288 | 576
+            for N in widths:
+                rows += [[1, H, 128, C, C, N, 3, 3, 1, 1, 1, 1, 9 * C, pad(N, 8), 0],
+                         [1, H, 128, pad(N, 8), N, C, 3, 3, 1, 1, 1, 1, 9 * C, C, 1]]
+                s2 = [2 * H, 256, pad(N, 8), N, C, 3, 3, 2, 2, 1, 1]
+                rows += [[1] + s2 + [0, C, 2], [1] + s2 + [0, C, 3]]
+                fold.append([N, C])
+    return rows, fold
+
+
+def all_igemm_rows():
+    conv, fold = [], []
+    for fn in (lambda: igemm_rows(network_rows()[0]), igemm_hand_rows, igemm_boundary_rows):
+        c, f = fn()
+        conv += c
+        fold += f
+    fold += [[c, 64] for c in (8, 56, 64, 72, 128)]            # the fold threshold
+    uniq = lambda rows: [list(r) for r in sorted(set(map(tuple, rows)))]
+    return uniq(conv), uniq(fold)
+
+
 # ---------------------------------------------------------------------------------------------- the answers
+def load(lib_path=None):
+    return C.CDLL(lib_path or os.environ.get("KODHIP_LIB") or os.path.join(ROOT, "object_detection_cib_amd", "libkodhip.so"))
+
+
+def evaluate_igemm(conv, fold, lib_path=None):
+    """-> (conv answers: [0, the eight outputs, slots] or [rc], fold answers) of the library in THIS process' environment"""
+    h = load(lib_path)
+    h.kodhip_conv_stats_slots.argtypes = [C.c_long, C.c_int]
+    out = (C.c_int * 8)()
+    ca = []
+    for B, H, W, ldx, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, op in conv:
+        rc = h.kodhip_conv_plan_query(op, B, H, W, ldx, 0, Cin, N, KH, KW, SH, SW, PH, PW, Kp, ldy, 0, out)
+        if rc != 0:
+            ca.append([rc])
+            continue
+        if op == 0:
+            kw = Cin // ldx - 1 if Cin > ldx and KW == 1 else KW          # the stem's window ends in a padding pixel
+            slots = h.kodhip_conv_stats_slots(B * ((H + 2 * PH - KH) // SH + 1) * ((W + 2 * PW - kw) // SW + 1), N)
+        elif op <= 2:
+            slots = h.kodhip_conv_dgrad_bnred_slots(B, H, W, Cin, N, KH, KW, SH, SW, PH, PW, ldy, op - 1)
+        else:
+            slots = (h.kodhip_conv_dgrad_s2f_bnred_slots if op == 3 else h.kodhip_conv_dgrad_dual_bnred_slots)(B, H, W, Cin, N, ldy)
+        ca.append([0] + list(out) + [slots])
+    return ca, [h.kodhip_conv_dgrad_s2_folded(*r) for r in fold]
+
+
 def evaluate(conv, stem, lib_path=None):
     """-> (conv answers [9 ints per row], stem answers) of the library in THIS process' environment (plain ctypes: the
     queries need no runtime and no torch)"""
-    h = C.CDLL(lib_path or os.environ.get("KODHIP_LIB") or os.path.join(ROOT, "object_detection_cib_amd", "libkodhip.so"))
+    h = load(lib_path)
     out = (C.c_int * 8)()
     ca = []
     for r in conv:
@@ -132,15 +263,33 @@ def evaluate(conv, stem, lib_path=None):
     return ca, [h.kodhip_stem_bwd_fused_blocks(*r) for r in stem]
 
 
+def load_table(path):
+    with (gzip.open(path, "rt") if path.endswith(".gz") else open(path)) as f:
+        return json.load(f)
+
+
+def write_table(path, text):
+    if path.endswith(".gz"):
+        with open(path, "wb") as f, gzip.GzipFile(filename="", mode="wb", fileobj=f, mtime=0) as z:       # (no name, no time: same bytes each run)
+            z.write(text.encode())
+    else:
+        with open(path, "w") as f:
+            f.write(text)
+
+
+def kind(table):
+    return table.get("table", "wgrad")
+
+
 def run_setting(name, path):
-    """the answers for the rows of `path` under knob setting `name`, from a child process"""
-    env = {k: v for k, v in os.environ.items() if k not in KNOBS}
-    env.update(SETTINGS[name])
+    """the answers for the rows of `path` under knob setting `name` of the file's table, from a child process"""
+    env = {k: v for k, v in os.environ.items() if k not in KNOBS + CONV_KNOBS}
+    env.update(TABLES[kind(load_table(path))][0][name])
     r = subprocess.run([sys.executable, os.path.abspath(__file__), "--eval", path], capture_output=True, text=True, env=env, timeout=120)
     if r.returncode != 0:
         raise RuntimeError("wgrad_plans --eval under %s failed (rc %s):\n%s" % (name, r.returncode, r.stderr[-2000:]))
     got = json.loads(r.stdout)
-    return got["conv"], got["stem"]
+    return got["conv"], got["aux"]
 
 
 def conv_rows(table):
@@ -150,57 +299,61 @@ def conv_rows(table):
 
 def expected(table, name):
     """the file's answers under setting `name`: the default table with the setting's differing rows put in"""
-    d, s = table["settings"]["default"], table["settings"][name]
-    conv, stem = list(d["conv"]), list(d["stem"])
+    d, s, aux = table["settings"]["default"], table["settings"][name], TABLES[kind(table)][1]
+    conv, stem = list(d["conv"]), list(d[aux])
     if name != "default":
         for i, a in s["conv"]:
             conv[i] = a
-        for i, a in s["stem"]:
+        for i, a in s[aux]:
             stem[i] = a
     return [table["answers"][a] for a in conv], stem
 
 
-def record(path):
+def record(path, which="wgrad"):
     """File layout (integer arrays throughout): geo = the distinct geometries without B, conv = [B, index into geo] per row,
     stem = [B, H, Wp, N] per row, answers = the distinct nine-integer answers; settings[name] = {env, conv, stem}: under
-    "default" one entry per row (conv: index into answers, stem: blocks), under a knob [row, value] for the rows that differ."""
-    conv, stem = all_rows()
+    "default" one entry per row (conv: index into answers, stem: blocks), under a knob [row, value] for the rows that differ.
+    (The conv table: "table": "conv", "fold" = [Cin, N] per row in place of "stem".)"""
+    SETTINGS, aux = TABLES[which]
+    conv, stem = all_rows() if which == "wgrad" else all_igemm_rows()
     geo = sorted(set(tuple(r[1:]) for r in conv))
     gi = {g: i for i, g in enumerate(geo)}
-    table = dict(geo=[list(g) for g in geo], conv=[[r[0], gi[tuple(r[1:])]] for r in conv], stem=stem, answers=[], settings={})
-    with open(path, "w") as f:
-        json.dump(table, f)
+    table = dict(geo=[list(g) for g in geo], conv=[[r[0], gi[tuple(r[1:])]] for r in conv], answers=[], settings={})
+    table[aux] = stem
+    if which != "wgrad":
+        table["table"] = which
+    write_table(path, json.dumps(table))
     ai, dc, ds = {}, None, None
     for name in SETTINGS:
         ca, sa = run_setting(name, path)
         ca = [ai.setdefault(tuple(a), len(ai)) for a in ca]
         if name == "default":
             dc, ds = ca, sa
-            table["settings"][name] = dict(env={}, conv=ca, stem=sa)
+            table["settings"][name] = {"env": {}, "conv": ca, aux: sa}
             continue
-        table["settings"][name] = dict(env=SETTINGS[name], conv=[[i, a] for i, a in enumerate(ca) if a != dc[i]],
-                                       stem=[[i, a] for i, a in enumerate(sa) if a != ds[i]])
-        print(name, len(table["settings"][name]["conv"]), "conv rows and", len(table["settings"][name]["stem"]),
-              "stem rows differ from the default table", flush=True)
+        table["settings"][name] = {"env": SETTINGS[name], "conv": [[i, a] for i, a in enumerate(ca) if a != dc[i]],
+                                   aux: [[i, a] for i, a in enumerate(sa) if a != ds[i]]}
+        print(name, len(table["settings"][name]["conv"]), "conv rows and", len(table["settings"][name][aux]),
+              aux, "rows differ from the default table", flush=True)
     table["answers"] = [list(a) for a in ai]
-    with open(path, "w") as f:
-        f.write("{\n")
-        for k in ("geo", "conv", "stem", "answers"):
-            f.write(' "%s": %s,\n' % (k, json.dumps(table[k], separators=(",", ":"))))
-        f.write(' "settings": {\n')
-        for j, (k, v) in enumerate(table["settings"].items()):
-            f.write('  "%s": %s%s\n' % (k, json.dumps(v, separators=(",", ":")), "," if j + 1 < len(SETTINGS) else ""))
-        f.write(" }\n}\n")
-    print(len(conv), "conv rows,", len(stem), "stem rows ->", path, os.path.getsize(path), "bytes")
+    text = "{\n"
+    for k in ("table", "geo", "conv", aux, "answers"):
+        if k in table:
+            text += ' "%s": %s,\n' % (k, json.dumps(table[k], separators=(",", ":")))
+    text += ' "settings": {\n'
+    for j, (k, v) in enumerate(table["settings"].items()):
+        text += '  "%s": %s%s\n' % (k, json.dumps(v, separators=(",", ":")), "," if j + 1 < len(SETTINGS) else "")
+    write_table(path, text + " }\n}\n")
+    print(len(conv), "conv rows,", len(stem), aux, "rows ->", path, os.path.getsize(path), "bytes")
 
 
 def main(argv):
-    if len(argv) == 2 and argv[0] == "--record":
-        record(argv[1])
+    if len(argv) == 2 and argv[0] in ("--record", "--record-conv"):
+        record(argv[1], "wgrad" if argv[0] == "--record" else "conv")
     elif len(argv) == 2 and argv[0] == "--eval":
-        table = json.load(open(argv[1]))
-        ca, sa = evaluate(conv_rows(table), table["stem"])
-        json.dump(dict(conv=ca, stem=sa), sys.stdout)
+        table = load_table(argv[1])
+        ca, sa = (evaluate if kind(table) == "wgrad" else evaluate_igemm)(conv_rows(table), table[TABLES[kind(table)][1]])
+        json.dump(dict(conv=ca, aux=sa), sys.stdout)
     else:
         print(__doc__)
     return 0
