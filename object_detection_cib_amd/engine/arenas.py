@@ -53,11 +53,15 @@ def arena_layout(g: Graph, numel: Dict[str, int]):
     return layout, gid, off, unit_starts
 
 
-class _UnitState:
-    """Per conv unit: arena offsets (set once) and the current shape set's buffers / launch state."""
-    __slots__ = ("u", "w_off", "g_off", "b_off", "f_off", "d_off", "Kp", "Kdp", "rs_off", "stats", "T",
-                 "sums", "aff", "bsums", "bsums_g", "bpart", "T2", "coef", "raw", "M", "H", "W", "Ho", "Wo",
-                 "fused_red", "segs", "seg_slots", "Kp_f", "raw_ld", "s2_fold", "stem_fused", "wg_dual")
+class UnitLayout:
+    """Per conv unit, per engine: the unit, its arena / pack offsets (elements), the packs' K paddings, the stride-2 data-
+    gradient form.  Written once in _build_arenas; what depends on the input shape is in engine/buffers.py UnitBuffers."""
+    __slots__ = ("u", "w_off", "g_off", "b_off", "rs_off", "f_off", "d_off", "Kp", "Kp_f", "Kdp", "s2_fold")
+
+
+class HeadLayout:
+    """Per head, per engine: the head unit, its arena and pack offsets and K paddings (shape side: buffers.HeadBuffers)."""
+    __slots__ = ("h", "w_off", "b_off", "f_off", "d_off", "Kp", "Kdp")
 
 
 class _StagingRing:
@@ -87,7 +91,7 @@ class ArenaMixin:
     # ------------------------------------------------------------------ arenas
     def _build_arenas(self, device):
         g = self.g
-        self.ustate: Dict[str, _UnitState] = {}
+        self.ulayout: Dict[str, UnitLayout] = {}
         layout, gid, off, self.unit_starts = arena_layout(g, {n: p.numel() for n, p in self.params.items()})
         exec_units = [op.unit for op in g.ops if op.kind == "conv"]
         self.n_arena = off
@@ -134,7 +138,7 @@ class ArenaMixin:
             blk += (N * Cin * KH * KW + 255) // 256
 
         for u in exec_units:
-            st = _UnitState()
+            st = UnitLayout()
             st.u = u
             K = u.k * u.k * u.cin if not u.stem else 144
             st.Kp = _pad(K, 32)                       # K of the weight-gradient slabs (stem: 6x3 taps x 8 = 144 -> 160)
@@ -160,15 +164,16 @@ class ArenaMixin:
             else:
                 add_desc(u.name + ".0.weight", st.f_off, st.d_off, u.cout, u.cin, u.k, u.k, st.Kp_f, st.Kdp,
                          u.cout, 0, (3 if st.s2_fold else 2) if s2 else 0)
-            self.ustate[u.name] = st
-        self.hstate = {}
+            self.ulayout[u.name] = st
+        self.hlayout: Dict[str, HeadLayout] = {}
         self.head_npad = _pad(A * (5 + nc), 8)
         for h in g.heads:
             Kp = _pad(h.cin, 32)
             Kdp = _pad(self.head_npad, 32)
-            hs = dict(f_off=foff, d_off=doff, Kp=Kp, Kdp=Kdp,
-                      w_off=layout[head_param(h, "box", "weight")][0],
-                      b_off=layout[head_param(h, "box", "bias")][0])
+            hs = HeadLayout()
+            hs.h, hs.f_off, hs.d_off, hs.Kp, hs.Kdp = h, foff, doff, Kp, Kdp
+            hs.w_off = layout[head_param(h, "box", "weight")][0]
+            hs.b_off = layout[head_param(h, "box", "bias")][0]
             n_off = 0
             for k, n in (("box", 4 * A), ("obj", A), ("cls", nc * A)):
                 add_desc(head_param(h, k, "weight"), foff + n_off * Kp, doff, n, h.cin, 1, 1, Kp, Kdp,
@@ -176,7 +181,7 @@ class ArenaMixin:
                 n_off += n
             foff += self.head_npad * Kp
             doff += h.cin * Kdp
-            self.hstate[h.name] = hs
+            self.hlayout[h.name] = hs
         self.fpack = torch.zeros(foff, dtype=torch.bfloat16, device=device)
         self.dpack = torch.zeros(max(doff, 8), dtype=torch.bfloat16, device=device)
         self.pack_descs = torch.tensor(descs, dtype=torch.int64, device=device)
@@ -184,6 +189,7 @@ class ArenaMixin:
         self.pack_blocks = blk
         self.exec_units = exec_units
         self.device = device
+        self._plan_static()               # engine/buffers.py: the plans that depend on the graph and the options alone
         self.hyper = torch.zeros(12, dtype=torch.float32, device=device)      # lr[3] | momentum[3] | wd[3] | grad scale | flags | dampening
         self.sgd_nesterov = True          # FusedSGD(nesterov=...): smart_sgd.yaml's default, kod/configs/nn/optimizers/smart_sgd.yaml
         self.sgd_dampening, self.sgd_maximize = 0.0, False      # torch.optim.SGD(dampening=, maximize=) through FusedSGD

@@ -28,13 +28,14 @@ class _BackwardPass:
 
     def __init__(self, eng, head_grads: List[torch.Tensor]):
         self.eng, self.lib, self.head_grads = eng, eng.lib, head_grads
-        self.B, self.H, self.W = eng.shape
+        self.bs = bs = eng.cur
+        self.B, self.H, self.W = bs.shape
         self.s = eng._stream()
         self.ga = eng.g_arena[eng.g_cur]
         self.gp = self.ga.data_ptr()
         self.dp = eng.dpack.data_ptr()
         self.pa = eng.p_arena.data_ptr()
-        self.wgp = eng.wg_part.data_ptr()
+        self.wgp = bs.wg_part.data_ptr()
         self.touched = set()            # grad buffers already holding a (partial) sum
         # freeze plan (engine/freeze.py), None when everything is trainable: then this is the program without any freeze
         # logic.  With one: nothing for units in the no-grad region, no data gradient that no trainable tensor needs,
@@ -70,7 +71,7 @@ class _BackwardPass:
         self.buckets = {}
         self.due = []                   # gradient buckets whose last unit has been processed: launched at the next flush point
         self.unit_i = len(eng.unit_starts)
-        self.pool_i = len(eng.pool_idx)
+        self.pool_i = len(bs.pool_idx)
         self.head_i = len(eng.g.heads)
         self.sync = eng.sync_bn and eng.collectives
         self.rccl_sync = self.sync and eng.peer is None
@@ -164,9 +165,9 @@ class _BackwardPass:
             return 1
         self.touched.add(name)
         if v.C != v.buf.C:
-            eng.gact[name].zero_()
-            if name in eng.gact32:
-                eng.gact32[name].zero_()
+            self.bs.gact[name].zero_()
+            if name in self.bs.gact32:
+                self.bs.gact32[name].zero_()
             return 1
         return 0
 
@@ -175,17 +176,17 @@ class _BackwardPass:
         if self.f32plan is None:
             return 0, None
         mode = self.f32plan.modes.get((kind, self.op_index[id(ident)] if kind in ("up", "pool") else ident), 0)
-        sh = self.eng.gact32.get(v.buf.name)
+        sh = self.bs.gact32.get(v.buf.name)
         return mode << 8, (sh.data_ptr() if (sh is not None and mode in (1, 2, 3)) else None)
 
     # ------------------------------------------------------------------ BatchNorm-backward coefficients
     def coef_job(self, u, ranks: int = 1):
         """one unit's coefficient job: (partials, slots, M, gamma, mean, rstd, dgamma, dbeta, coef, C, raw_moment)"""
-        st, C_ = self.eng.ustate[u.name], u.cout
-        aff, pa, gp = st.aff.data_ptr(), self.pa, self.gp
+        st, C_ = self.bs.units[u.name], u.cout
+        lay, aff, pa, gp = st.lay, st.aff.data_ptr(), self.pa, self.gp
         # raw_moment: the partials came from the last dgrad into this tensor
-        return (st.bpart.data_ptr(), st.T2, float(st.M) * ranks, pa + 4 * st.g_off, aff + 8 * C_, aff + 12 * C_,
-                gp + 4 * st.g_off, gp + 4 * st.b_off, st.coef.data_ptr(), C_, 1 if st.fused_red else 0)
+        return (st.bpart.data_ptr(), st.T2, float(st.M) * ranks, pa + 4 * lay.g_off, aff + 8 * C_, aff + 12 * C_,
+                gp + 4 * lay.g_off, gp + 4 * lay.b_off, st.coef.data_ptr(), C_, 1 if st.fused_red else 0)
 
     def bn_bwd_stats(self, group):
         """BatchNorm-backward sums -> coefficients.  Under SyncBN the [sum dz, sum dz*xhat] vectors of the group's
@@ -201,7 +202,7 @@ class _BackwardPass:
         for kind, names, flags in coef_launches(eng.bn_mode, self.fz, [u.name for u in group], self.sync):
             units = [by_name[n] for n in names]
             for u in units:
-                st, C_ = eng.ustate[u.name], u.cout
+                st, C_ = self.bs.units[u.name], u.cout
                 if not st.fused_red:
                     aff, dA = st.aff.data_ptr(), u.dst
                     e0 = eng._t0()
@@ -219,7 +220,7 @@ class _BackwardPass:
             else:
                 job = self.coef_job(units[0])
                 chk(lib.kodhip_bn_bwd_coeffs_eval_partials(job[0], job[1], *job[3:], s), names[0])
-            eng._t1(e0, "bn_bwd_coeffs", sum(8.0 * u.cout * eng.ustate[u.name].T2 for u in units), name="+".join(names))
+            eng._t1(e0, "bn_bwd_coeffs", sum(8.0 * u.cout * self.bs.units[u.name].T2 for u in units), name="+".join(names))
 
     def coef_train(self, group):
         """the train-mode coefficient launch(es) of a group: peer exchange, RCCL exchange, paired launch or single launch"""
@@ -230,12 +231,12 @@ class _BackwardPass:
                                                            eng.peer_slots[(u.name, "b")], s), u.name)
         elif self.sync:
             for u in group:
-                st = eng.ustate[u.name]
+                st = self.bs.units[u.name]
                 chk(lib.kodhip_bn_reduce_partials(st.bpart.data_ptr(), st.bsums.data_ptr(), u.cout, st.T2, s), u.name)
             # out of place: the local sums stay for dgamma / dbeta
-            eng._allreduce_group([eng.ustate[u.name].bsums for u in group], [eng.ustate[u.name].bsums_g for u in group])
+            eng._allreduce_group([self.bs.units[u.name].bsums for u in group], [self.bs.units[u.name].bsums_g for u in group])
             for u in group:
-                st = eng.ustate[u.name]
+                st = self.bs.units[u.name]
                 chk(lib.kodhip_bn_bwd_coeffs(st.bsums.data_ptr(), st.bsums_g.data_ptr(),
                                              *self.coef_job(u, eng.world_size)[2:], s), u.name)
         elif len(group) == 2:           # short_conv + main_conv: one launch for both coefficient sets
@@ -258,9 +259,9 @@ class _BackwardPass:
                 if name not in touched:
                     touched.add(name)
                     if v.C != v.buf.C or t is None:
-                        eng.gact[name].zero_()
+                        self.bs.gact[name].zero_()
                 if t is not None:
-                    eng.gact[name][..., v.coff:v.coff + v.C].copy_(t.permute(0, 2, 3, 1))
+                    self.bs.gact[name][..., v.coff:v.coff + v.C].copy_(t.permute(0, 2, 3, 1))
         eng._pending = []
         if eng.collectives:
             first = 0 if fz is None else trainable_span(eng.unit_starts, fz, eng.layout)
@@ -295,7 +296,7 @@ class _BackwardPass:
                 h, w = H // op.src.stride, W // op.src.stride
                 # src and dst are slices of the same (already initialised) concat gradient buffer
                 chk(lib.kodhip_maxpool_bwd(eng._ptr(op.dst, True), op.dst.buf.C, op.dst.coff,
-                                           eng.pool_idx[self.pool_i].data_ptr(), eng._ptr(op.src, True),
+                                           self.bs.pool_idx[self.pool_i].data_ptr(), eng._ptr(op.src, True),
                                            op.src.buf.C, op.src.coff, B, h, w, op.src.C, op.k, self.f32("pool", op, op.src)[1], s), "maxpool_bwd")
             else:
                 group = [op.unit]
@@ -306,7 +307,7 @@ class _BackwardPass:
                     group.append(rops[ri].unit)
                     ri += 1
                 # what each unit of the group launches (engine/freeze.py group_launches; None: outside the grad region)
-                launches = group_launches(group, fz, eng._dual, len(group) == 2 and eng.ustate[group[1].name].wg_dual > 0)
+                launches = group_launches(group, fz, eng._dual, len(group) == 2 and self.bs.units[group[1].name].wg_dual > 0)
                 runs = [u for u, ln in zip(group, launches) if ln is not None]
                 if runs:
                     self.bn_bwd_stats(runs)
@@ -333,9 +334,10 @@ class _BackwardPass:
         hf = fz.heads[hu.name] if fz is not None else None
         if hf is not None and not hf.needs_out_grad:
             return
-        hs = eng.hstate[hu.name]
+        hs = self.bs.heads[hu.name]
+        geo = hs.geo_bwd(eng.head_npad)
         gten = self.head_grads[self.head_i].contiguous()
-        assert gten.shape == (B, A, hs["H"], hs["W"], 5 + nc) and gten.dtype == torch.float32
+        assert gten.shape == (B, A, hs.H, hs.W, 5 + nc) and gten.dtype == torch.float32
         names = [head_param(hu, k, "bias") for k in ("box", "obj", "cls")]
         offs = [eng.layout[n][0] for n in names]
         src = hu.src
@@ -350,19 +352,17 @@ class _BackwardPass:
                 eng.head_stream = torch.cuda.Stream(device=eng.device)
             hstream, hs_ = eng.head_stream, eng.head_stream.cuda_stream
             hstream.wait_event(self.bwd_start)
-        chk(lib.kodhip_head_bwd_prep(gten.data_ptr(), hs["dy"].data_ptr(), hs["ws"].data_ptr(),
+        chk(lib.kodhip_head_bwd_prep(gten.data_ptr(), hs.dy.data_ptr(), hs.ws.data_ptr(),
                                      gp + 4 * offs[0], gp + 4 * offs[1], gp + 4 * offs[2],
-                                     B, hs["H"] * hs["W"], A, nc, eng.head_npad, hs_), hu.name)
+                                     B, hs.H * hs.W, A, nc, eng.head_npad, hs_), hu.name)
         self.fork_point(hstream)
         if hf is None or hf.needs_in_grad:
             acc = self.acc_flag(src)
             fm, fptr = self.f32("head", hu.name, src)
             e0 = eng._t0()
-            chk(lib.kodhip_conv_dgrad(hs["dy"].data_ptr(), self.dp + 2 * hs["d_off"], eng._ptr(src, True),
-                                      B, hs["H"], hs["W"], src.buf.C, src.coff, hu.cin,
-                                      eng.head_npad, 1, 1, 1, 1, 0, 0, hs["Kdp"], eng.head_npad, 0,
-                                      acc | fm, fptr, hs_), hu.name + ".dgrad")
-            eng._t1(e0, "dgrad", 2.0 * hs["M"] * (eng.head_npad + hu.cin), name=hu.name)
+            chk(lib.kodhip_conv_dgrad(hs.dy.data_ptr(), self.dp + 2 * hs.lay.d_off, eng._ptr(src, True),
+                                      *geo, hs.lay.Kdp, eng.head_npad, 0, acc | fm, fptr, hs_), hu.name + ".dgrad")
+            eng._t1(e0, "dgrad", 2.0 * hs.M * (eng.head_npad + hu.cin), name=hu.name)
             if side:
                 ev = torch.cuda.Event()
                 ev.record(hstream)
@@ -372,10 +372,9 @@ class _BackwardPass:
             ev.record(hstream)
             self.grad_events["head:" + hu.name] = ev
         if hf is None or any(hf.w_trainable):
-            self.timed_wgrad(hu.name, 2.0 * hs["M"] * (hu.cin + eng.head_npad),
-                             eng._ptr(src), hs["dy"].data_ptr(), self.wgp, gp + 4 * hs["w_off"],
-                             B, hs["H"], hs["W"], src.buf.C, src.coff, hu.cin,
-                             eng.head_npad, 1, 1, 1, 1, 0, 0, hs["Kp"], eng.head_npad, 0, A * (5 + nc), 0, 1.0)
+            self.timed_wgrad(hu.name, 2.0 * hs.M * (hu.cin + eng.head_npad),
+                             eng._ptr(src), hs.dy.data_ptr(), self.wgp, gp + 4 * hs.lay.w_off,
+                             *geo, hs.lay.Kp, eng.head_npad, 0, A * (5 + nc), 0, 1.0)
         else:
             self.fork_ev = None
         self.flush_wgrads()
@@ -389,11 +388,9 @@ class _BackwardPass:
         eng, lib = self.eng, self.lib
         B, H, W, s, gp, dp, wgp = self.B, self.H, self.W, self.s, self.gp, self.dp, self.wgp
         dgrad, partner, dual_w, w_grad = ln.dgrad, ln.partner, ln.dual_w, ln.w_grad
-        st = eng.ustate[u.name]
-        C_ = u.cout
-        aff = st.aff.data_ptr()
-        dA = u.dst
-        res = u.residual
+        st = self.bs.units[u.name]
+        lay, C_, aff = st.lay, u.cout, st.aff.data_ptr()
+        dA, res = u.dst, u.residual
         eng._stamp("m:" + u.name)
         if not ln.res_grad:
             res = None
@@ -412,14 +409,14 @@ class _BackwardPass:
                 # otherwise left to the tail of the weight-gradient stream (small launches, one at a time) - this HBM-bound
                 # kernel runs beside them instead of behind them
                 e0 = eng._t0()
-                chk(lib.kodhip_stem_bwd_fused(*fargs, eng.stem_part.data_ptr(), gp + 4 * st.w_off,
+                chk(lib.kodhip_stem_bwd_fused(*fargs, self.bs.stem_part.data_ptr(), gp + 4 * lay.w_off,
                                               B, st.H, st.W, C_, 1.0, s), u.name + ".bwd_fused")
                 eng._t1(e0, "wgrad", nb, name=u.name)
                 self.flush_wgrads()
                 self.join_main()          # a gradient bucket on the weight-gradient stream must see this gradient
                 return
             self.fork_point()
-            self.timed_wgrad(u.name, nb, "stem", *fargs, wgp, gp + 4 * st.w_off, B, st.H, st.W, C_, 1.0)
+            self.timed_wgrad(u.name, nb, "stem", *fargs, wgp, gp + 4 * lay.w_off, B, st.H, st.W, C_, 1.0)
             self.flush_wgrads()
             return
         racc = self.acc_flag(res) if res else 0
@@ -432,19 +429,17 @@ class _BackwardPass:
         eng._t1(e0, "bn_silu_bwd_apply", (6.0 + ((4.0 if racc else 2.0) if res else 0.0)) * st.M * C_, name=u.name)
         self.fork_point()
         # st.raw now holds dY
-        if u.stem:
-            geo = (B, st.H, st.W, 8, 0, 8, C_, 6, 3, 2, 1, 2, 1)
-        else:
-            geo = (B, st.H, st.W, u.src.buf.C, u.src.coff, u.cin, C_, u.k, u.k, u.s, u.s, u.p, u.p)
+        geo = st.geo_bwd()
+        if not u.stem:
             segs = () if st.segs is None else (C.cast(st.segs, C.c_void_p), len(st.segs), st.seg_slots)
             if dgrad == "skip" and dual_w:          # its weight gradient rides in the main_conv's dual launch
                 self.hold = True
                 return
             if dgrad == "skip":
                 if w_grad:
-                    self.timed_wgrad(u.name, 2.0 * (B * st.H * st.W * u.cin + st.M * C_),
-                                     eng._ptr(u.src), st.raw.data_ptr(), wgp, gp + 4 * st.w_off,
-                                     *geo, st.Kp, st.raw_ld, 0, C_, 0, 1.0)
+                    self.timed_wgrad(u.name, float(st.conv_bytes()),
+                                     eng._ptr(u.src), st.raw.data_ptr(), wgp, gp + 4 * lay.w_off,
+                                     *geo, lay.Kp, st.raw_ld, 0, C_, 0, 1.0)
                 return
             if dgrad != "none":
                 fm, fptr = self.f32("dgrad", u.name, u.src)
@@ -457,39 +452,35 @@ class _BackwardPass:
                     nb += 2.0 * in_px * sum(sg.ch_count for sg in st.segs)
                 e0 = eng._t0()
                 if dgrad == "dual":
-                    ps = eng.ustate[partner.name]
+                    ps = self.bs.units[partner.name]
                     nb += 2.0 * ps.M * partner.cout
                     fn = lib.kodhip_conv_dgrad_dual if st.segs is None else lib.kodhip_conv_dgrad_dual_bnred
-                    chk(fn(st.raw.data_ptr(), dp + 2 * st.d_off, ps.raw.data_ptr(), dp + 2 * ps.d_off, eng._ptr(u.src, True),
-                           B, st.H, st.W, u.src.buf.C, u.src.coff, u.cin, C_, st.Kdp, st.raw_ld, 0, acc_src, fptr, *segs, s), u.name + ".dgrad2")
+                    chk(fn(st.raw.data_ptr(), dp + 2 * lay.d_off, ps.raw.data_ptr(), dp + 2 * ps.lay.d_off, eng._ptr(u.src, True),
+                           *geo[:7], lay.Kdp, st.raw_ld, 0, acc_src, fptr, *segs, s), u.name + ".dgrad2")
                 elif u.k == 3 and u.s == 2 and u.p == 1:
-                    if st.s2_fold:
+                    if lay.s2_fold:
                         fn = lib.kodhip_conv_dgrad_s2f if st.segs is None else lib.kodhip_conv_dgrad_s2f_bnred
                     else:
                         fn = lib.kodhip_conv_dgrad_s2 if st.segs is None else lib.kodhip_conv_dgrad_s2_bnred
-                    chk(fn(st.raw.data_ptr(), dp + 2 * st.d_off, eng._ptr(u.src, True),
-                           B, st.H, st.W, u.src.buf.C, u.src.coff, u.cin, C_, st.raw_ld, 0,
-                           acc_src, fptr, *segs, s), u.name + ".dgrad")
+                    chk(fn(st.raw.data_ptr(), dp + 2 * lay.d_off, eng._ptr(u.src, True),
+                           *geo[:7], st.raw_ld, 0, acc_src, fptr, *segs, s), u.name + ".dgrad")
                 else:
                     fn = lib.kodhip_conv_dgrad if st.segs is None else lib.kodhip_conv_dgrad_bnred
-                    chk(fn(st.raw.data_ptr(), dp + 2 * st.d_off, eng._ptr(u.src, True),
-                           *geo, st.Kdp, st.raw_ld, 0, acc_src, fptr, *segs, s), u.name + ".dgrad")
+                    chk(fn(st.raw.data_ptr(), dp + 2 * lay.d_off, eng._ptr(u.src, True),
+                           *geo, lay.Kdp, st.raw_ld, 0, acc_src, fptr, *segs, s), u.name + ".dgrad")
                 eng._t1(e0, "dgrad" if st.segs is None else "dgrad+bn_reduce", nb, name=u.name + ("+" + partner.name if dgrad == "dual" else ""))
         if dgrad == "dual" and dual_w:
-            ps = eng.ustate[partner.name]
+            ps = self.bs.units[partner.name]
             self.hold = False
             self.timed_wgrad(u.name + "+" + partner.name, 2.0 * (B * st.H * st.W * u.cin + 2 * st.M * C_),
                              "dual", eng._ptr(u.src), st.raw.data_ptr(), ps.raw.data_ptr(), wgp,
-                             gp + 4 * st.w_off, gp + 4 * ps.w_off, B, st.H, st.W, u.src.buf.C, u.src.coff, u.cin, C_, st.Kp,
-                             st.raw_ld, 0, 1.0)
+                             gp + 4 * lay.w_off, gp + 4 * ps.lay.w_off, *geo[:7], lay.Kp, st.raw_ld, 0, 1.0)
             self.flush_wgrads()
             return
-        cin_true = 3 if u.stem else u.cin
-        in_px_w = B * H * W if u.stem else B * st.H * st.W
         if w_grad:
-            self.timed_wgrad(u.name, 2.0 * (in_px_w * cin_true + st.M * C_),
-                             eng._ptr(u.src), st.raw.data_ptr(), wgp, gp + 4 * st.w_off,
-                             *geo, st.Kp, st.raw_ld, 0, C_, 1 if u.stem else 0, 1.0)
+            self.timed_wgrad(u.name, float(st.conv_bytes()),
+                             eng._ptr(u.src), st.raw.data_ptr(), wgp, gp + 4 * lay.w_off,
+                             *geo, lay.Kp, st.raw_ld, 0, C_, 1 if u.stem else 0, 1.0)
         self.flush_wgrads()           # this unit's - and a fused short_conv partner's - weight gradients: after the dgrad
 
 
@@ -504,8 +495,8 @@ class BackwardMixin:
         bp.run(out_grads)
         self._publish_grads()
         if self.g.inputs:
-            B, H, W = self.shape
-            return [self.gact[v.buf.name][..., v.coff:v.coff + v.C].permute(0, 3, 1, 2).float() if v.buf.name in bp.touched
+            B, H, W = self.cur.shape
+            return [self.cur.gact[v.buf.name][..., v.coff:v.coff + v.C].permute(0, 3, 1, 2).float() if v.buf.name in bp.touched
                     else torch.zeros((B, v.C, H // v.stride, W // v.stride), device=self.device) for v in self.g.inputs]
 
     def _frozen_f32plan(self, fz):
@@ -531,8 +522,8 @@ class BackwardMixin:
             cached = plan_f32_accumulation(kept, {b.name: b.C for b in self.g.bufs})
             self._f32_frozen[fz.key] = cached
         for name in cached.shadow_bufs:           # (a buffer that needs a shadow only with fewer writers)
-            if name not in self.gact32:
-                self.gact32[name] = torch.empty(self.gact[name].shape, dtype=torch.float32, device=self.device)
+            if name not in self.cur.gact32:
+                self.cur.gact32[name] = torch.empty(self.cur.gact[name].shape, dtype=torch.float32, device=self.device)
         return cached
 
     def _comm_stream(self):

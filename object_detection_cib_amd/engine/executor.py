@@ -11,17 +11,15 @@ PyTorch is used for device memory, streams and torch.distributed only.
 from __future__ import annotations
 
 import os
-
 from typing import Dict, Optional
-
 
 import torch
 
 from .. import _lib
 from .graph import Graph, check_head_limits
 from .options import EngineOptions
-from .arenas import ArenaMixin, _UnitState, _pad          # noqa: F401
-from .buffers import BufferMixin
+from .arenas import ArenaMixin, UnitLayout, HeadLayout, _pad          # noqa: F401
+from .buffers import BufferMixin, BufferSet
 from .forward import ForwardMixin, BN_EPS, BN_MOMENTUM   # noqa: F401
 from .backward import BackwardMixin
 
@@ -29,10 +27,12 @@ from .backward import BackwardMixin
 class Engine(ArenaMixin, BufferMixin, ForwardMixin, BackwardMixin):
     """Owns arenas + buffers for one network instance (one process, one GPU).  The work is split by concern:
     engine/options.py (every switch), engine/plan.py + engine/ddp.py + engine/freeze.py + engine/bn_mode.py (pure
-    planning, CPU-testable), engine/arenas.py (parameters, packs, optimizer), engine/buffers.py (per-shape buffer sets),
-    engine/forward.py / engine/backward.py (the launch programs; the state of one backward pass lives in
-    backward._BackwardPass, the engine keeps none between calls), engine/comm.py (RCCL communicator, SyncBN peer
-    exchange)."""
+    planning, CPU-testable), engine/arenas.py (parameters, packs, optimizer; per unit and head one layout record -
+    `ulayout`, `hlayout` - with the arena / pack offsets, written once), engine/buffers.py (per input shape one BufferSet:
+    activations, gradients, slabs and per unit / head one record of buffers and launch-plan integers; `cur` is the
+    current one, made current by one assignment in allocate()), engine/forward.py / engine/backward.py (the launch
+    programs; the state of one pass lives in forward._ForwardPass / backward._BackwardPass, each built over `cur`, the
+    engine keeps none between calls), engine/comm.py (RCCL communicator, SyncBN peer exchange)."""
 
     def __init__(self, graph: Graph, params: Dict[str, torch.nn.Parameter], buffers: Dict[str, torch.Tensor],
                  options: Optional[EngineOptions] = None):
@@ -45,10 +45,10 @@ class Engine(ArenaMixin, BufferMixin, ForwardMixin, BackwardMixin):
         self.params = params          # full state_dict-style names -> Parameter (shared with the nn.Module)
         self.buffers = buffers        # running_mean / running_var / num_batches_tracked
         self.device = None
-        self.shape = None             # (B, H, W) of the current allocation
+        self.cur: Optional[BufferSet] = None      # the current shape's buffer set (allocate())
         # one complete buffer set per (B, H, W): a captured hipGraph bakes buffer addresses in, so a forward at another
         # shape (validation batch, partial last batch) must never free what a graph replays into
-        self._sets: Dict[tuple, dict] = {}
+        self._sets: Dict[tuple, BufferSet] = {}   # shape -> set, least recently used first (the current one is last)
         self._pinned = set()          # shapes a captured graph depends on: never evicted
         self.max_shape_sets = self.opt.max_shape_sets
         self.training_ready = False

@@ -288,7 +288,7 @@ def test_every_batchnorm_eval_under_train_mode_equals_the_eval_forward():
         torch.cuda.synchronize()
         assert eng.bn_mode is not None and len(eng.bn_mode.eval_units) == len(eng.exec_units)
         for u in eng.exec_units:
-            st, C = eng.ustate[u.name], u.cout
+            st, C = eng.cur.units[u.name], u.cout
             bn = net.get_submodule(u.name + ".1")
             rstd = torch.rsqrt(bn.running_var.double() + bn.eps)
             sc = bn.weight.double() * rstd

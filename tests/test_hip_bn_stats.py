@@ -782,17 +782,17 @@ def test_in_situ_statistics_every_unit(B):
     for it, x in enumerate(xs):
         if it == 0:
             for u in eng.exec_units:
-                eng.ustate[u.name].stats.fill_(NAN)
+                eng.cur.units[u.name].stats.fill_(NAN)
         rm0, rv0 = eng.rm_arena.clone(), eng.rv_arena.clone()
         with torch.no_grad():
             net.forward_raw(x)
         torch.cuda.synchronize()
         for u in eng.exec_units:
-            st, C_ = eng.ustate[u.name], u.cout
+            st, C_ = eng.cur.units[u.name], u.cout
             chain = fwd_chain(st.M, C_, u.cin, u.k, u.s, stem=u.stem)
-            o = st.rs_off
-            ref = _fwd_reference(st.raw.view(-1, C_), chain, st.T, eng.p_arena[st.g_off:st.g_off + C_],
-                                 eng.p_arena[st.b_off:st.b_off + C_], rm0[o:o + C_], rv0[o:o + C_])
+            o = st.lay.rs_off
+            ref = _fwd_reference(st.raw.view(-1, C_), chain, st.T, eng.p_arena[st.lay.g_off:st.lay.g_off + C_],
+                                 eng.p_arena[st.lay.b_off:st.lay.b_off + C_], rm0[o:o + C_], rv0[o:o + C_])
             w = {}
             _check_fwd_constants(ref, st.aff, eng.rm_arena[o:o + C_], eng.rv_arena[o:o + C_], f"B={B} batch {it} {u.name}", w)
             for key, v in w.items():

@@ -133,7 +133,7 @@ def test_launch_program():
     # algorithmic bytes: 2 (in + out), + 2 out with a residual
     by_name = {p[4]: p[3] for p in prof}
     for u in eng.exec_units:
-        st = eng.ustate[u.name]
+        st = eng.cur.units[u.name]
         in_elems = 2 * 96 * 96 * 3 if u.stem else 2 * st.H * st.W * u.cin
         assert by_name[u.name] == 2 * (in_elems + st.M * u.cout) + (2 * st.M * u.cout if u.residual else 0), u.name
     assert dict(profile_counts(net.fuse_eval(False), x)[0]) == dict(off)

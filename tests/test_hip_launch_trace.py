@@ -8,6 +8,11 @@ is.  A pull request that changes the program on purpose re-records the file on i
 traces (`--keep` writes them next to the JSON):
 
     python tools/launch_trace.py --record tests/golden/launch_trace.json [--keep DIR]
+
+The eval_forward* rows pin one eval forward (two-pass and fused) the same way.  tests/golden/profile_families.json pins what
+the launch text does not show: the (family, algorithmic bytes, name) sequence of eng.profile for one eager training step and
+the two eval forwards - the byte formulas bench.py --full builds its roofline table from, and the one-stream schedule of a
+profiled step.  The byte counts are integer arithmetic carried in floats: compared for equality.
 """
 import importlib.util
 import json
@@ -23,6 +28,7 @@ launch_trace = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(launch_trace)
 
 GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "launch_trace.json")))
+PROFILES = json.load(open(os.path.join(ROOT, "tests", "golden", "profile_families.json")))
 # a child that ended by a signal, an abort or its time limit: no further GPU child is started in this run
 _stopped = []
 
@@ -48,3 +54,23 @@ def test_launch_trace_equals_golden(config, tmp_path):
     assert got["lines"] == want["lines"], hint
     assert got["launches"] == want["launches"], hint
     assert got["sha256"] == want["sha256"], hint
+
+
+def test_profile_golden_covers_the_cases():
+    assert sorted(PROFILES) == sorted(launch_trace.PROFILE_CASES)
+
+
+@pytest.mark.parametrize("case", list(launch_trace.PROFILE_CASES))
+def test_profile_families_equal_golden(case, tmp_path):
+    if _stopped:
+        pytest.fail(f"not started: the trace child of {_stopped[0]} ended by a signal or its time limit")
+    out = str(tmp_path / (case + ".json"))
+    rc, err = launch_trace.run_child(case, out, profile=True)
+    if rc is None or rc < 0 or rc in (124, 134, 137, 139):
+        _stopped.append(case)
+        pytest.fail(f"profile child of {case} ended by a signal or its time limit (rc {rc}):\n{err}")
+    assert rc == 0, err
+    got, want = json.load(open(out)), PROFILES[case]
+    assert len(got) == len(want)
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g == w, f"launch {i}: {g} != {w}"

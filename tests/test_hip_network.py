@@ -304,11 +304,11 @@ def _dY(eng, u):
     fused backward (kodhip_stem_bwd_fused never writes dY; st.raw still holds y): there the stand-alone pass forms it from
     the same dA / y / coefficients."""
     from object_detection_cib_amd import _lib
-    st = eng.ustate[u.name]
+    st = eng.cur.units[u.name]
     if not st.stem_fused:
         return st.raw
     dy = st.raw.clone()
-    C_, aff, dA = u.cout, st.aff.data_ptr(), eng.gact[u.dst.buf.name]
+    C_, aff, dA = u.cout, st.aff.data_ptr(), eng.cur.gact[u.dst.buf.name]
     _lib.check(_lib.lib().kodhip_bn_silu_bwd_apply(dA.data_ptr(), u.dst.buf.C, u.dst.coff, dy.data_ptr(), st.raw_ld,
                                                    aff, aff + 4 * C_, st.coef.data_ptr(), None, 0, 0, 0, st.M, C_,
                                                    torch.cuda.current_stream().cuda_stream), "bwd_apply")
@@ -339,13 +339,13 @@ def test_bench_geometry_b64_640_deterministic_and_teacher_forced():
     grads = {k: p.grad.detach().cpu() for k, p in net.named_parameters()}
     params = {k: p.detach().cpu() for k, p in net.named_parameters()}
     bf = lambda t: t.to(torch.bfloat16).float()
-    units = sorted(eng.exec_units, key=lambda u: -eng.ustate[u.name].M)[:6]
+    units = sorted(eng.exec_units, key=lambda u: -eng.cur.units[u.name].M)[:6]
     units += [u for u in eng.exec_units if u.name == "backbone.stages.stage2.blocks.0"]
     worst, ref_y = {}, {}
     for u in units:
-        st = eng.ustate[u.name]
+        st = eng.cur.units[u.name]
         # NOTE st.raw holds dY after backward; the forward's pre-BN tensor is recomputed by one more forward below
-        X = bf(x) if u.stem else eng.act[u.src.buf.name][..., u.src.coff:u.src.coff + u.src.C].float().permute(0, 3, 1, 2).cpu()
+        X = bf(x) if u.stem else eng.cur.act[u.src.buf.name][..., u.src.coff:u.src.coff + u.src.C].float().permute(0, 3, 1, 2).cpu()
         W = bf(params[u.name + ".0.weight"]).requires_grad_(True)
         y = F.conv2d(X, W, None, u.s, u.p)
         dY = _dY(eng, u).float().permute(0, 3, 1, 2).cpu()
@@ -358,7 +358,7 @@ def test_bench_geometry_b64_640_deterministic_and_teacher_forced():
     with torch.no_grad():
         net.forward_raw(xg)             # train-mode forward again: st.raw = pre-BN output, st.aff = batch statistics
     for u in units:
-        st = eng.ustate[u.name]
+        st = eng.cur.units[u.name]
         raw = st.raw.float().permute(0, 3, 1, 2).cpu()
         e = _rel(raw, ref_y.pop(u.name))
         worst["conv_raw"] = max(worst.get("conv_raw", 0.0), e)
@@ -438,7 +438,7 @@ def test_layers_teacher_forced(case):
     raws = net.forward_raw(x.cuda())
     for r in raws:
         r.retain_grad()
-    fwd_raw = {u.name: eng.ustate[u.name].raw.float().cpu() for u in eng.exec_units}
+    fwd_raw = {u.name: eng.cur.units[u.name].raw.float().cpu() for u in eng.exec_units}
     lr = _loss()(FeatureShape(width=img_w, height=img_h),
                  tuple((r[..., :4], r[..., 4:5], r[..., 5:]) for r in raws), tuple(DetectionTarget(b, l) for b, l in tg))
     (B * (lr.localization + lr.classification + lr.objectness)).backward()
@@ -446,7 +446,7 @@ def test_layers_teacher_forced(case):
     params = {k: p.detach().cpu() for k, p in net.named_parameters()}
 
     def view(v, grad=False):
-        t = (eng.gact if grad else eng.act)[v.buf.name]
+        t = (eng.cur.gact if grad else eng.cur.act)[v.buf.name]
         return t[..., v.coff:v.coff + v.C].float().permute(0, 3, 1, 2).cpu()
 
     bf = lambda t: t.to(torch.bfloat16).float()
@@ -454,7 +454,7 @@ def test_layers_teacher_forced(case):
 
     def add_expect(v, g):
         if v.buf.name not in expect:
-            t = eng.gact[v.buf.name]
+            t = eng.cur.gact[v.buf.name]
             expect[v.buf.name] = torch.zeros((t.shape[0], t.shape[3], t.shape[1], t.shape[2]), dtype=torch.float64)
         expect[v.buf.name][:, v.coff:v.coff + v.C] += g.double()
 
@@ -471,7 +471,7 @@ def test_layers_teacher_forced(case):
         if op.kind != "conv":
             continue
         u = op.unit
-        st = eng.ustate[u.name]
+        st = eng.cur.units[u.name]
         X = bf(x) if u.stem else view(u.src)
         W = bf(params[u.name + ".0.weight"]).requires_grad_(True)
         Xr = X.clone().requires_grad_(not u.stem)
@@ -519,7 +519,7 @@ def test_layers_teacher_forced(case):
     for name, g in expect.items():
         if ".2.cat" in name:
             continue
-        got = eng.gact[name].float().permute(0, 3, 1, 2).cpu()
+        got = eng.cur.gact[name].float().permute(0, 3, 1, 2).cpu()
         note("dX_accum", name, _rel(got, g), 2e-2)
         checked += 1
     assert checked >= 20
@@ -702,13 +702,13 @@ def test_multi_producer_dx_b64_640_vs_fp32_torch():
         assert len(multi) == 13
 
         def gview(v):                 # gradient of a view, NCHW fp32 on the host
-            return eng.gact[v.buf.name][..., v.coff:v.coff + v.C].float().permute(0, 3, 1, 2).cpu()
+            return eng.cur.gact[v.buf.name][..., v.coff:v.coff + v.C].float().permute(0, 3, 1, 2).cpu()
 
         def aview(v):
-            return eng.act[v.buf.name][..., v.coff:v.coff + v.C].float().permute(0, 3, 1, 2).cpu()
+            return eng.cur.act[v.buf.name][..., v.coff:v.coff + v.C].float().permute(0, 3, 1, 2).cpu()
 
         def conv_dx(u):               # fp32 torch data gradient of one conv unit from the HIP path's bf16 dY and weights
-            st = eng.ustate[u.name]
+            st = eng.cur.units[u.name]
             dY = _dY(eng, u).float().permute(0, 3, 1, 2).cpu()
             W = bf(params[u.name + ".0.weight"])
             shape = (B, u.cin, st.H, st.W)
@@ -717,7 +717,7 @@ def test_multi_producer_dx_b64_640_vs_fp32_torch():
         expect = {}
 
         def add(buf, lo, g):
-            t = eng.gact[buf]
+            t = eng.cur.gact[buf]
             e = expect.setdefault(buf, torch.zeros((t.shape[0], t.shape[3], t.shape[1], t.shape[2]), dtype=torch.float32))
             e[:, lo:lo + g.shape[1]] += g
 
@@ -753,7 +753,7 @@ def test_multi_producer_dx_b64_640_vs_fp32_torch():
                 F.max_pool2d(xs, 5, 1, 2).backward(gview(op.dst))
                 add(w.buf, w.lo, xs.grad)
         for buf, e in sorted(expect.items()):
-            got = eng.gact[buf].float().permute(0, 3, 1, 2).cpu()
+            got = eng.cur.gact[buf].float().permute(0, 3, 1, 2).cpu()
             # compare only channel ranges with several producers (single-producer slices are covered elsewhere)
             C = got.shape[1]
             cover = torch.zeros(C, dtype=torch.int32)
@@ -798,8 +798,8 @@ def test_schedule_switches_keep_the_gradients():
         net = net.cuda().train()
         _step(net, x.cuda(), tg, size, B)
         eng = net.engine()
-        assert eng.ustate["backbone.stem"].stem_fused == (tag != "unfused")
-        n_dual = sum(1 for st in eng.ustate.values() if st.wg_dual > 0)
+        assert eng.cur.units["backbone.stem"].stem_fused == (tag != "unfused")
+        n_dual = sum(1 for st in eng.cur.units.values() if st.wg_dual > 0)
         assert n_dual == (0 if tag == "single_wgrads" else 8), n_dual
         got[tag] = {k: p.grad.detach().clone() for k, p in net.named_parameters()}
     for k, g in got["default"].items():
@@ -844,7 +844,7 @@ def test_yv5m_bench_geometry_b64_640_deterministic_and_teacher_forced():
     grads = {k: p.grad.detach().cpu() for k, p in net.named_parameters()}
     params = {k: p.detach().cpu() for k, p in net.named_parameters()}
     bf = lambda t: t.to(torch.bfloat16).float()
-    by_m = sorted(eng.exec_units, key=lambda u: -eng.ustate[u.name].M)
+    by_m = sorted(eng.exec_units, key=lambda u: -eng.cur.units[u.name].M)
     units, seen = [], set()
     for u in by_m:                                    # the largest-M unit of every (cin, cout, k, s) class, first five classes
         key = (u.cin, u.cout, u.k, u.s)
@@ -857,8 +857,8 @@ def test_yv5m_bench_geometry_b64_640_deterministic_and_teacher_forced():
     assert {u.cin for u in units} & {48, 96, 192}
     worst, ref_y = {}, {}
     for u in units:
-        st = eng.ustate[u.name]
-        X = eng.act[u.src.buf.name][..., u.src.coff:u.src.coff + u.src.C].float().permute(0, 3, 1, 2).cpu()
+        st = eng.cur.units[u.name]
+        X = eng.cur.act[u.src.buf.name][..., u.src.coff:u.src.coff + u.src.C].float().permute(0, 3, 1, 2).cpu()
         W = bf(params[u.name + ".0.weight"]).requires_grad_(True)
         y = F.conv2d(X, W, None, u.s, u.p)
         y.backward(_dY(eng, u).float().permute(0, 3, 1, 2).cpu())     # (st.raw holds dY after backward; fused stem: _dY)
@@ -869,7 +869,7 @@ def test_yv5m_bench_geometry_b64_640_deterministic_and_teacher_forced():
     with torch.no_grad():
         net.forward_raw(xg)             # train-mode forward again: st.raw = pre-BN output, st.aff = batch statistics
     for u in units:
-        st = eng.ustate[u.name]
+        st = eng.cur.units[u.name]
         raw = st.raw.float().permute(0, 3, 1, 2).cpu()
         e = _rel(raw, ref_y.pop(u.name))
         worst["conv_raw"] = max(worst.get("conv_raw", 0.0), e)

@@ -30,9 +30,9 @@ torch.manual_seed(seed); net = Yolov5Network(3, nc, widen_factor=widen, deepen_f
 outs = net.forward_raw(x.cuda())
 eng = net.engine()
 for u in eng.exec_units:
-    st = eng.ustate[u.name]
+    st = eng.cur.units[u.name]
     raw = st.raw.float().permute(0, 3, 1, 2).cpu()
-    a = eng.act[u.dst.buf.name][..., u.dst.coff:u.dst.coff + u.dst.C].float().permute(0, 3, 1, 2).cpu()
+    a = eng.cur.act[u.dst.buf.name][..., u.dst.coff:u.dst.coff + u.dst.C].float().permute(0, 3, 1, 2).cpu()
     line = f"{u.name:52s}"
     for which in ("ref", "emu"):
         acts = allacts[which]

@@ -9,10 +9,18 @@ s<n> by first appearance), events as e<n> by first record, pointers as <engine o
 allocates: t<n> by allocation order).  A non-null pointer that resolves to nothing is an error.  Nothing is synchronised or
 timed inside the step: the recording does not change what it records.
 
+The eval_forward* configurations record one eval forward (net.eval(), net(x) under torch.no_grad()) the same way.
+
+A second mode keeps what the launch text does not show: the (family, algorithmic bytes, name) sequence of eng.profile - the
+numbers bench.py --full builds its roofline table from, and the one-stream schedule of a profiled step - for the cases of
+PROFILE_CASES (tests/golden/profile_families.json).
+
 usage (GPU box):  python tools/launch_trace.py CONFIG [--out FILE]      one configuration's trace (a fresh process each:
                                                                        the engine reads its switches once)
                   python tools/launch_trace.py --list
                   python tools/launch_trace.py --record FILE [--keep DIR]   every configuration in a child process -> golden JSON
+                  python tools/launch_trace.py --profile CASE [--out FILE]  one case's eng.profile sequence as JSON
+                  python tools/launch_trace.py --record-profile FILE        every case in a child process -> golden JSON
 """
 import bisect
 import ctypes as C
@@ -38,10 +46,11 @@ _FREEZE = {
 }
 
 
-def _cfg(env=None, model="net", freeze=None, bn_eval=None, dist=None, clip=None):
+def _cfg(env=None, model="net", freeze=None, bn_eval=None, dist=None, clip=None, eval_forward=False):
     """env: engine switches; model: net | csp | csp_relu; freeze: key of _FREEZE; bn_eval: backbone | short | all;
-    dist: None or (sync_batchnorm,) on a 1-rank group; clip: (algorithm, value, skip_nonfinite, track_grad_norm)"""
-    return dict(env=env or {}, model=model, freeze=freeze, bn_eval=bn_eval, dist=dist, clip=clip)
+    dist: None or (sync_batchnorm,) on a 1-rank group; clip: (algorithm, value, skip_nonfinite, track_grad_norm);
+    eval_forward: the step is one eval forward of the whole network instead of a training step"""
+    return dict(env=env or {}, model=model, freeze=freeze, bn_eval=bn_eval, dist=dist, clip=clip, eval_forward=eval_forward)
 
 
 _COLL = {"KODHIP_FORCE_COLLECTIVES": "1"}
@@ -79,7 +88,11 @@ CONFIGS = {
     "clip_value": _cfg(clip=("value", 0.01, False, False)),
     "clip_skip_nonfinite": _cfg(clip=(None, None, True, False)),
     "clip_track_grad_norm": _cfg(clip=(None, None, False, True)),
+    "eval_forward": _cfg(eval_forward=True),
+    "eval_forward_fused": _cfg({"KODHIP_EVAL_FUSED": "1"}, eval_forward=True),
 }
+# eng.profile cases (tests/golden/profile_families.json): case -> the configuration whose step is profiled
+PROFILE_CASES = {"train_step": "default", "eval_forward": "eval_forward", "eval_forward_fused": "eval_forward_fused"}
 SWITCHES = sorted({k for c in CONFIGS.values() for k in c["env"]})
 
 
@@ -282,10 +295,15 @@ def _walk(tr, obj, name, depth=0, seen=None):
 
 def _register(tr, eng, extra):
     # the engine's own tensors first, so that views (parameters, gradients, per-unit slices) resolve to the arenas
+    # (the current buffer set under the names the golden file was recorded with: the engine once kept these on itself,
+    # the per-unit records as `ustate`, the per-head ones as dicts `hstate`)
+    bs = eng.cur
+    named = dict(wg_part=bs.wg_part, stem_part=bs.stem_part, act=bs.act, gact=bs.gact, gact32=bs.gact32, ustate=bs.units,
+                 hstate={n: dict(dy=hs.dy, ws=hs.ws) for n, hs in bs.heads.items()}, pool_idx=bs.pool_idx)
     for k in ("p_arena", "g_arena", "m_arena", "rm_arena", "rv_arena", "nbt_arena", "gid", "fpack", "dpack", "wg_part",
               "stem_part", "act", "gact", "gact32", "ustate", "hstate", "pool_idx", "clip", "norm_ws", "hyper", "keep_mask"):
-        if hasattr(eng, k):
-            _walk(tr, getattr(eng, k), k)
+        if k in named or hasattr(eng, k):
+            _walk(tr, named[k] if k in named else getattr(eng, k), k)
     _walk(tr, eng, "eng")
     for name, obj in extra.items():
         _walk(tr, obj() if callable(obj) else obj, name)
@@ -356,14 +374,37 @@ def _set_modes(cfg, net):
             p.requires_grad_(not pick(n))
 
 
-def trace_config(name):
-    """-> Trace of configuration `name` (this process: environment switches are set here, before the engine is built)"""
+def _enter_config(name):
+    """this process takes the environment switches of configuration `name` (before the engine is built)"""
     cfg = CONFIGS[name]
     for k in SWITCHES:
         os.environ.pop(k, None)
     os.environ.pop("KODHIP_DEBUG_STAMPS", None)
     os.environ.update(cfg["env"])
     sys.path.insert(0, ROOT)
+    return cfg
+
+
+def profile_case(case):
+    """-> [[family, algorithmic bytes, name], ...] of eng.profile over the third step of PROFILE_CASES[case]: the step runs
+    eagerly with eng.profile = [] (every launch event-timed on one stream, no side branches)"""
+    cfg = _enter_config(PROFILE_CASES[case])
+    import torch
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    step, eng, _ = _build_step(cfg, dev)
+    for _ in range(2):
+        step()
+    eng.profile = []
+    step()
+    torch.cuda.synchronize()
+    prof, eng.profile = eng.profile, None
+    return [[fam, float(nb), name] for fam, _, _, nb, name in prof]
+
+
+def trace_config(name):
+    """-> Trace of configuration `name` (this process: environment switches are set here, before the engine is built)"""
+    cfg = _enter_config(name)
     import torch
     from object_detection_cib_amd import _lib
     tr = Trace(_lib.lib(), _lib.SIGNATURES)
@@ -459,6 +500,13 @@ def _build_step(cfg, dev):
     if cfg["dist"] is not None:
         net.configure_distributed(None, sync_batchnorm=cfg["dist"][0], bucket_mb=0.5, native_rccl=True)
         assert eng.collectives and eng.comm is not None
+    if cfg["eval_forward"]:
+        net.eval()
+
+        def step():
+            with torch.no_grad():
+                net(x)
+        return step, eng, dict(x=x)
     eng.set_hyper(*hyper)
     if cfg["clip"] is not None:
         algo, val, skip, track = cfg["clip"]
@@ -490,12 +538,14 @@ def summary(text, launches=None):
     return dict(lines=len(lines), launches=dict(sorted(launches.items())), sha256=hashlib.sha256(text.encode()).hexdigest())
 
 
-def run_child(name, out_path, timeout=CHILD_TIMEOUT):
-    """One configuration in a fresh process under its own time limit -> (return code, stderr tail).  A negative return
-    code is a signal (an abort, a fault); None the time limit: start nothing more on the GPU after either."""
+def run_child(name, out_path, timeout=CHILD_TIMEOUT, profile=False):
+    """One configuration (profile: one case of PROFILE_CASES) in a fresh process under its own time limit -> (return code,
+    stderr tail).  A negative return code is a signal (an abort, a fault); None the time limit: start nothing more on the
+    GPU after either."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), name, "--out", out_path], capture_output=True,
+        r = subprocess.run([sys.executable, os.path.abspath(__file__)] + (["--profile"] if profile else []) +
+                           [name, "--out", out_path], capture_output=True,
                            text=True, timeout=timeout, env=env, cwd=ROOT)
     except subprocess.TimeoutExpired as e:
         return None, str(e)
@@ -525,6 +575,21 @@ def record(path, keep=None):
         sys.exit("no trace of: " + " ".join(failed))
 
 
+def record_profile(path):
+    golden = {}
+    for case in PROFILE_CASES:
+        tmp = path + "." + case + ".tmp"
+        rc, err = run_child(case, tmp, profile=True)
+        if rc != 0:
+            sys.exit("profile of %s: rc %s; nothing further was started\n%s" % (case, rc, err))
+        golden[case] = json.load(open(tmp))
+        os.remove(tmp)
+        print(case, len(golden[case]), "launches", flush=True)
+    with open(path, "w") as f:
+        f.write("{\n" + ",\n".join(' "%s": [\n%s\n ]' % (case, ",\n".join("  " + json.dumps(r) for r in rows))
+                                   for case, rows in sorted(golden.items())) + "\n}\n")
+
+
 def main(argv):
     if not argv or argv[0] in ("-h", "--help"):
         print(__doc__)
@@ -534,6 +599,17 @@ def main(argv):
         return 0
     if argv[0] == "--record":
         record(argv[1], argv[3] if len(argv) > 3 and argv[2] == "--keep" else None)
+        return 0
+    if argv[0] == "--record-profile":
+        record_profile(argv[1])
+        return 0
+    if argv[0] == "--profile":
+        text = json.dumps(profile_case(argv[1]))
+        if len(argv) > 3 and argv[2] == "--out":
+            with open(argv[3], "w") as f:
+                f.write(text)
+        else:
+            print(text)
         return 0
     tr = trace_config(argv[0])
     if len(argv) > 2 and argv[1] == "--out":

@@ -46,7 +46,7 @@ print("%-46s %4s %4s %2s %8s | %6s %5s %4s | %5s %6s | %6s %6s | %6s %5s %4s | %
     "unit", "cin", "cout", "ks", "M", "fwd", "GB/s", "TF", "fin", "apply", "coeff", "bapply", "dgrad", "GB/s", "TF", "wgrad", "GB/s", "TF"))
 by_stride, tot = {}, 0.0
 for u in units:
-    st = eng.ustate[u.name]
+    st = eng.cur.units[u.name]
     cin = 3 if u.stem else u.cin
     k = 6 if u.stem else u.k
     Min = B * (S // (1 if u.stem else u.src.stride)) ** 2
