@@ -106,6 +106,59 @@ __global__ void bn_reduce_partials_kernel(const float* part, double* sums, int C
   if (lane == 0) sums[idx] = s;
 }
 
+// ---------------------------------------------------------------- the channel arithmetic, stated once
+// rstd / scale / shift of one channel from its variance and mean (the apply pass sees the mean in fp32)
+__device__ __forceinline__ float bn_affine(double var, float eps, float g, float b, double mean, float* scale, float* shift) {
+  float rstd = (float)(1.0 / sqrt(var + (double)eps));
+  float sc = g * rstd;
+  *scale = sc;
+  *shift = b - (float)mean * sc;
+  return rstd;
+}
+
+// forward finalize of channel c: the two fp64 sums over `count` pixels -> affine constants, saved statistics and (with
+// update_running) the running statistics from their old values rm0 / rv0
+__device__ __forceinline__ void bn_finalize_channel(double s0, double s1, double count, float g, float b, float rm0, float rv0,
+                                                    float momentum, float eps, int update_running, int c, float* scale,
+                                                    float* shift, float* mean_out, float* rstd_out, float* running_mean,
+                                                    float* running_var) {
+  double mean = s0 / count;
+  double var = s1 / count - mean * mean;
+  if (var < 0.0) var = 0.0;
+  float rstd = bn_affine(var, eps, g, b, mean, &scale[c], &shift[c]);
+  mean_out[c] = (float)mean;
+  rstd_out[c] = rstd;
+  if (update_running) {
+    double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
+    running_mean[c] = (1.f - momentum) * rm0 + momentum * (float)mean;
+    running_var[c] = (1.f - momentum) * rv0 + momentum * (float)unbiased;
+  }
+}
+
+// raw_moment: the second backward sum is sum dz*y (produced by the data-gradient epilogue, conv_igemm.hip MODE_PLAIN_BN)
+// instead of sum dz*xhat; xhat = (y - mean)*rstd  =>  sum dz*xhat = rstd * (sum dz*y - mean * sum dz), in fp64
+// (linear in the sums: ranks may add converted values)
+__device__ __forceinline__ double bn_central_moment(double rs, double mu, double s0, double s1) { return rs * (s1 - mu * s0); }
+
+// backward coefficients of a channel: dY = k1*dz + k2*y + k3
+struct BnCoef { float k1, k2, k3; };
+__device__ __forceinline__ void bn_coef_store(float* coef, int C, int c, BnCoef k) {
+  coef[c] = k.k1;
+  coef[C + c] = k.k2;
+  coef[2 * C + c] = k.k3;
+}
+
+// train mode, from the sums over ALL ranks' `count` pixels:
+//   k1 = g*rstd, k2 = -g*rstd^2*S1/n, k3 = -g*rstd*S0/n + g*rstd^2*mean*S1/n
+__device__ __forceinline__ BnCoef bn_coef_train(double g, double rs, double mu, double s0, double s1, double count) {
+  double S0 = s0 / count, S1 = s1 / count;
+  return {(float)(g * rs), (float)(-g * rs * rs * S1), (float)(-g * rs * S0 + g * rs * rs * mu * S1)};
+}
+
+// an eval-mode BatchNorm inside a training network (normalised with its running statistics): the data gradient is the plain
+// dX = gamma*rstd*dZ - no terms through the batch moments
+__device__ __forceinline__ BnCoef bn_coef_eval(float g, float rstd) { return {(float)((double)g * (double)rstd), 0.f, 0.f}; }
+
 // forward finalize: sums (already all-reduced over ranks when SyncBN) -> affine constants + running stats
 __global__ void bn_finalize_kernel(const double* sums, double count, const float* gamma, const float* beta,
                                    float* running_mean, float* running_var, float momentum, float eps,
@@ -113,21 +166,9 @@ __global__ void bn_finalize_kernel(const double* sums, double count, const float
                                    int update_running) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  double mean = sums[c] / count;
-  double var = sums[C + c] / count - mean * mean;
-  if (var < 0.0) var = 0.0;
-  float rstd = (float)(1.0 / sqrt(var + (double)eps));
-  float g = gamma[c], b = beta[c];
-  float sc = g * rstd;
-  scale[c] = sc;
-  shift[c] = b - (float)mean * sc;
-  mean_out[c] = (float)mean;
-  rstd_out[c] = rstd;
-  if (update_running) {
-    double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-  }
+  bn_finalize_channel(sums[c], sums[C + c], count, gamma[c], beta[c], update_running ? running_mean[c] : 0.f,
+                      update_running ? running_var[c] : 0.f, momentum, eps, update_running, c, scale, shift, mean_out,
+                      rstd_out, running_mean, running_var);
 }
 
 // single-GPU fast path: partial slabs -> constants in ONE launch (one wave per channel).  PEER: SyncBN - the rank's
@@ -150,114 +191,54 @@ __global__ void bn_finalize_fused_kernel(const float* part, int T, double count,
   wave_sum_partials2(p0, p1, T, lane, s0, s1);
   if constexpr (PEER) peer_allreduce2(pv, slot, c, C + c, lane, s0, s1);
   if (lane != 0) return;
-  double mean = s0 / count;
-  double var = s1 / count - mean * mean;
-  if (var < 0.0) var = 0.0;
-  float rstd = (float)(1.0 / sqrt(var + (double)eps));
-  float sc = g * rstd;
-  scale[c] = sc;
-  shift[c] = b - (float)mean * sc;
-  mean_out[c] = (float)mean;
-  rstd_out[c] = rstd;
-  if (update_running) {
-    double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    running_mean[c] = (1.f - momentum) * rm0 + momentum * (float)mean;
-    running_var[c] = (1.f - momentum) * rv0 + momentum * (float)unbiased;
-  }
+  bn_finalize_channel(s0, s1, count, g, b, rm0, rv0, momentum, eps, update_running, c, scale, shift, mean_out, rstd_out,
+                      running_mean, running_var);
 }
 
-// raw_moment: the second partial is sum dz*y (produced by the data-gradient epilogue, conv_igemm.hip MODE_PLAIN_BN)
-// instead of sum dz*xhat; xhat = (y - mean)*rstd  =>  sum dz*xhat = rstd * (sum dz*y - mean * sum dz), in fp64.
-// EVAL: an eval-mode BatchNorm inside a training network (normalised with its running statistics, which `mean` / `rstd`
-// then hold): the parameter gradients are reduced as above, the data gradient is the plain dX = gamma*rstd*dZ - no terms
-// through the batch moments, no cross-rank exchange.
-template <bool PEER = false, bool EVAL = false>
+// backward coefficients from partial slabs, one wave per channel, ONE or TWO units per launch (blockIdx.y = unit,
+// gridDim.y = number of jobs): a CSP layer's short_conv and main_conv reach this point of the backward pass together, and on
+// the critical chain a launch costs more than the arithmetic.  eval: the unit is an eval-mode BatchNorm (bn_coef_eval;
+// `mean` / `rstd` hold its running statistics, `count` has no effect) - a sibling pair may be one eval-mode and one train-mode
+// unit.  The parameter gradients are reduced the same way in both modes.
+struct CoefJob { const float* part; int T; double count; const float* gamma; const float* mean; const float* rstd;
+                 float* dgamma; float* dbeta; float* coef; int C; int raw_moment; int eval; };
+
+// one channel of one job (a wave).  PEER: SyncBN - the sums behind dX are exchanged through the peer buffers (one job; an
+// eval-mode unit exchanges nothing).  The job's fields arrive by value: read before the reduction, like the parameters
+template <bool PEER>
 __device__ __forceinline__ void bn_bwd_coeffs_channel(const float* part, int T, double count, const float* gamma,
                                                       const float* mean, const float* rstd, float* dgamma, float* dbeta,
-                                                      float* coef, int C, int raw_moment, int c, int lane,
-                                                      const KodPeerView* pv = nullptr, unsigned int slot = 0) {
+                                                      float* coef, int C, int raw_moment, int eval, int c, int lane,
+                                                      const KodPeerView& pv, unsigned int slot) {
   const float* p0 = part + (size_t)c * T;
   const float* p1 = part + (size_t)(C + c) * T;
   const float g_ = gamma[c], rs_ = rstd[c], mu_ = mean[c];      // up front: not a second round trip behind the reduction
   double s0, s1;
   wave_sum_partials2(p0, p1, T, lane, s0, s1);
-  if (raw_moment) s1 = (double)rs_ * (s1 - (double)mu_ * s0);      // (linear in the sums: ranks may add converted values)
+  if (raw_moment) s1 = bn_central_moment((double)rs_, (double)mu_, s0, s1);
   if (lane == 0) {          // parameter gradients keep the rank's own sums (the gradient all-reduce adds the ranks later)
     dbeta[c] = (float)s0;
     dgamma[c] = (float)s1;
   }
-  if constexpr (EVAL) {
-    static_assert(!PEER, "an eval-mode unit exchanges nothing");
-    if (lane == 0) {
-      coef[c] = (float)((double)g_ * (double)rs_);
-      coef[C + c] = 0.f;
-      coef[2 * C + c] = 0.f;
-    }
-    return;
-  }
-  if constexpr (PEER) peer_allreduce2(*pv, slot, c, C + c, lane, s0, s1);   // dX uses the sums over ALL ranks' pixels
+  if constexpr (PEER) peer_allreduce2(pv, slot, c, C + c, lane, s0, s1);   // dX uses the sums over ALL ranks' pixels
   if (lane != 0) return;
-  double g = g_, rs = rs_, mu = mu_;
-  double S0 = s0 / count, S1 = s1 / count;
-  coef[c] = (float)(g * rs);
-  coef[C + c] = (float)(-g * rs * rs * S1);
-  coef[2 * C + c] = (float)(-g * rs * S0 + g * rs * rs * mu * S1);
+  BnCoef k = bn_coef_train(g_, rs_, mu_, s0, s1, count);
+  if (!PEER && eval) k = bn_coef_eval(g_, rs_);       // (a select behind the train triple, whatever `count` made of it)
+  bn_coef_store(coef, C, c, k);
 }
 
-__global__ void bn_bwd_coeffs_fused_kernel(const float* part, int T, double count, const float* gamma,
-                                           const float* mean, const float* rstd, float* dgamma, float* dbeta,
-                                           float* coef, int C, int raw_moment) {
-  int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (c >= C) return;
-  bn_bwd_coeffs_channel(part, T, count, gamma, mean, rstd, dgamma, dbeta, coef, C, raw_moment, c, threadIdx.x & 63);
-}
-
-__global__ void bn_bwd_coeffs_peer_kernel(const float* part, int T, double count, const float* gamma,
-                                          const float* mean, const float* rstd, float* dgamma, float* dbeta,
-                                          float* coef, int C, int raw_moment, KodPeerView pv, unsigned int slot) {
-  int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (c >= C) return;
-  bn_bwd_coeffs_channel<true>(part, T, count, gamma, mean, rstd, dgamma, dbeta, coef, C, raw_moment, c, threadIdx.x & 63, &pv, slot);
-}
-
-// the same for TWO units in one launch (blockIdx.y = unit): a CSP layer's short_conv and main_conv reach this point of
-// the backward pass together, and on the critical chain a launch costs more than the arithmetic
-struct CoefJob { const float* part; int T; double count; const float* gamma; const float* mean; const float* rstd;
-                 float* dgamma; float* dbeta; float* coef; int C; int raw_moment; };
-__global__ void bn_bwd_coeffs_fused2_kernel(CoefJob j0, CoefJob j1) {
+template <bool PEER>
+__global__ void bn_bwd_coeffs_fused_kernel(CoefJob j0, CoefJob j1, KodPeerView pv, unsigned int slot) {
   const CoefJob& j = blockIdx.y == 0 ? j0 : j1;
   int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (c >= j.C) return;
-  bn_bwd_coeffs_channel(j.part, j.T, j.count, j.gamma, j.mean, j.rstd, j.dgamma, j.dbeta, j.coef, j.C, j.raw_moment, c,
-                        threadIdx.x & 63);
-}
-
-// eval-mode units (see bn_bwd_coeffs_channel's EVAL); the two-unit form takes a mode per job - a CSP layer's sibling
-// pair may be one eval-mode and one train-mode unit
-__global__ void bn_bwd_coeffs_eval_kernel(const float* part, int T, const float* gamma, const float* mean,
-                                          const float* rstd, float* dgamma, float* dbeta, float* coef, int C,
-                                          int raw_moment) {
-  int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (c >= C) return;
-  bn_bwd_coeffs_channel<false, true>(part, T, 1.0, gamma, mean, rstd, dgamma, dbeta, coef, C, raw_moment, c,
-                                     threadIdx.x & 63);
-}
-
-__global__ void bn_bwd_coeffs_mode2_kernel(CoefJob j0, CoefJob j1, int eval0, int eval1) {
-  const CoefJob& j = blockIdx.y == 0 ? j0 : j1;
-  int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (c >= j.C) return;
-  if (blockIdx.y == 0 ? eval0 : eval1)
-    bn_bwd_coeffs_channel<false, true>(j.part, j.T, j.count, j.gamma, j.mean, j.rstd, j.dgamma, j.dbeta, j.coef, j.C,
-                                       j.raw_moment, c, threadIdx.x & 63);
-  else
-    bn_bwd_coeffs_channel(j.part, j.T, j.count, j.gamma, j.mean, j.rstd, j.dgamma, j.dbeta, j.coef, j.C, j.raw_moment,
-                          c, threadIdx.x & 63);
+  bn_bwd_coeffs_channel<PEER>(j.part, j.T, j.count, j.gamma, j.mean, j.rstd, j.dgamma, j.dbeta, j.coef, j.C, j.raw_moment,
+                              j.eval, c, threadIdx.x & 63, pv, slot);
 }
 
 // ---------------------------------------------------------------- eval-mode constants of many units, one launch
 // One descriptor per unit (block); one thread per channel.  Writes the four vectors the training path keeps in `aff`
-// (scale | shift | mean | rstd) from the running statistics, rstd in fp64 as bn_finalize_kernel forms it; never writes a
+// (scale | shift | mean | rstd) from the running statistics, rstd in fp64 as bn_finalize_channel forms it; never writes a
 // running statistic.  coef != null (gamma and beta both frozen: no coefficient kernel runs in backward): also the
 // eval-mode backward coefficients (gamma*rstd, 0, 0).
 struct BnEvalDesc {
@@ -270,17 +251,10 @@ __global__ __launch_bounds__(256) void bn_eval_constants_kernel(const BnEvalDesc
   const int C = (int)d.C;
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     const float g = d.gamma[c], b = d.beta[c], rm = d.running_mean[c];
-    const float rstd = (float)(1.0 / sqrt((double)d.running_var[c] + (double)eps));
-    const float sc = g * rstd;
-    d.aff[c] = sc;
-    d.aff[C + c] = b - rm * sc;
+    const float rstd = bn_affine((double)d.running_var[c], eps, g, b, (double)rm, &d.aff[c], &d.aff[C + c]);
     d.aff[2 * C + c] = rm;
     d.aff[3 * C + c] = rstd;
-    if (d.coef != nullptr) {
-      d.coef[c] = (float)((double)g * (double)rstd);
-      d.coef[C + c] = 0.f;
-      d.coef[2 * C + c] = 0.f;
-    }
+    if (d.coef != nullptr) bn_coef_store(d.coef, C, c, bn_coef_eval(g, rstd));
   }
 }
 
@@ -422,8 +396,7 @@ __global__ __launch_bounds__(256) void bn_silu_bwd_reduce_kernel(const bf16_t* d
   }
 }
 
-// grads from the LOCAL sums; coefficients from the (all-reduced) sums:
-//   dY = k1*dz + k2*y + k3,  k1 = g*rstd, k2 = -g*rstd^2*S1/n, k3 = -g*rstd*S0/n + g*rstd^2*mean*S1/n
+// sums form (the RCCL SyncBN route): grads from the LOCAL sums; coefficients from the (all-reduced) sums
 __global__ void bn_bwd_coeffs_kernel(const double* sums_local, const double* sums_global, double count,
                                      const float* gamma, const float* mean, const float* rstd,
                                      float* dgamma, float* dbeta, float* coef, int C, int raw_moment) {
@@ -431,13 +404,10 @@ __global__ void bn_bwd_coeffs_kernel(const double* sums_local, const double* sum
   if (c >= C) return;
   double g = gamma[c], rs = rstd[c], mu = mean[c];
   double l1 = sums_local[C + c], g1 = sums_global[C + c];
-  if (raw_moment) { l1 = rs * (l1 - mu * sums_local[c]); g1 = rs * (g1 - mu * sums_global[c]); }
+  if (raw_moment) { l1 = bn_central_moment(rs, mu, sums_local[c], l1); g1 = bn_central_moment(rs, mu, sums_global[c], g1); }
   dbeta[c] = (float)sums_local[c];
   dgamma[c] = (float)l1;
-  double S0 = sums_global[c] / count, S1 = g1 / count;
-  coef[c] = (float)(g * rs);
-  coef[C + c] = (float)(-g * rs * rs * S1);
-  coef[2 * C + c] = (float)(-g * rs * S0 + g * rs * rs * mu * S1);
+  bn_coef_store(coef, C, c, bn_coef_train(g, rs, mu, sums_global[c], g1, count));
 }
 
 // dY (bf16, written in place over y) ; optional identity gradient: dI[m][c] (+)= dA[m][c]
@@ -596,59 +566,83 @@ int kodhip_bn_finalize(const double* sums, double count, const float* gamma, con
   return KOD_OK;
 }
 
+// One launcher per fused family; `fn` names the entry point that was called in the messages.  view == NULL: the rank's own
+// sums; else SyncBN (kod/configs/trainer/ddp.yaml:9 sync_batchnorm): the same single launch, with the rank's two sums per
+// channel exchanged through the peer buffers of kodhip_peer_* inside the kernel.  count = pixels of ALL ranks; slot = first
+// granule of this exchange in the buffers (4 * C granules); view = kodhip_peer_view's struct.
+static int bn_finalize_partials(const char* fn, const float* partials, int T, double count, const float* gamma,
+                                const float* beta, float* running_mean, float* running_var, float momentum, float eps,
+                                float* scale, float* shift, float* mean, float* rstd, int C, int update_running,
+                                const void* view, unsigned int slot, hipStream_t stream) {
+  KOD_CHECK_ARG(partials && gamma && beta && scale && shift && mean && rstd && C > 0 && T > 0 && count > 0, "%s: bad args", fn);
+  KOD_CHECK_ARG(!update_running || (running_mean && running_var), "%s: running stats missing", fn);
+  const dim3 grid(cdiv(C, 4)), blk(256);
+  if (view) {
+    const KodPeerView pv = *(const KodPeerView*)view;
+    KOD_CHECK_ARG(pv.world >= 1 && pv.world <= KOD_PEER_MAX && pv.world * 4 <= 64, "%s: bad peer view", fn);
+    hipLaunchKernelGGL(bn_finalize_fused_kernel<true>, grid, blk, 0, stream, partials, T, count, gamma, beta, running_mean,
+                       running_var, momentum, eps, scale, shift, mean, rstd, C, update_running, pv, slot);
+  } else {
+    hipLaunchKernelGGL(bn_finalize_fused_kernel<false>, grid, blk, 0, stream, partials, T, count, gamma, beta, running_mean,
+                       running_var, momentum, eps, scale, shift, mean, rstd, C, update_running, KodPeerView{}, 0u);
+  }
+  KOD_LAUNCH_CHECK(fn);
+  return KOD_OK;
+}
+
+// one or two jobs (the grid covers the wider one; the narrower job's surplus blocks exit); the peer form takes one
+static int bn_bwd_coeffs_partials(const char* fn, const CoefJob* jobs, int n_jobs, const void* view, unsigned int slot,
+                                  hipStream_t stream) {
+  int Cmax = 0;
+  for (int i = 0; i < n_jobs; ++i) {
+    const CoefJob& j = jobs[i];
+    KOD_CHECK_ARG(j.part && j.gamma && j.mean && j.rstd && j.dgamma && j.dbeta && j.coef && j.C > 0 && j.T > 0 &&
+                  (j.eval || j.count > 0), "%s: bad args", fn);
+    if (j.C > Cmax) Cmax = j.C;
+  }
+  const dim3 grid(cdiv(Cmax, 4), n_jobs), blk(256);
+  const CoefJob& j1 = jobs[n_jobs - 1];
+  if (view) {
+    const KodPeerView pv = *(const KodPeerView*)view;
+    KOD_CHECK_ARG(pv.world >= 1 && pv.world <= KOD_PEER_MAX, "%s: bad peer view", fn);
+    hipLaunchKernelGGL(bn_bwd_coeffs_fused_kernel<true>, grid, blk, 0, stream, jobs[0], j1, pv, slot);
+  } else {
+    hipLaunchKernelGGL(bn_bwd_coeffs_fused_kernel<false>, grid, blk, 0, stream, jobs[0], j1, KodPeerView{}, 0u);
+  }
+  KOD_LAUNCH_CHECK(fn);
+  return KOD_OK;
+}
+
 int kodhip_bn_finalize_partials(const float* partials, int T, double count, const float* gamma, const float* beta,
                                 float* running_mean, float* running_var, float momentum, float eps,
                                 float* scale, float* shift, float* mean, float* rstd, int C, int update_running,
                                 hipStream_t stream) {
-  KOD_CHECK_ARG(partials && gamma && beta && scale && shift && mean && rstd && C > 0 && T > 0 && count > 0,
-                "bn_finalize_partials: bad args");
-  KOD_CHECK_ARG(!update_running || (running_mean && running_var), "bn_finalize_partials: running stats missing");
-  hipLaunchKernelGGL(bn_finalize_fused_kernel<false>, dim3(cdiv(C, 4)), dim3(256), 0, stream, partials, T, count, gamma, beta,
-                     running_mean, running_var, momentum, eps, scale, shift, mean, rstd, C, update_running, KodPeerView{}, 0u);
-  KOD_LAUNCH_CHECK("bn_finalize_partials");
-  return KOD_OK;
+  return bn_finalize_partials("bn_finalize_partials", partials, T, count, gamma, beta, running_mean, running_var, momentum, eps,
+                              scale, shift, mean, rstd, C, update_running, nullptr, 0u, stream);
 }
 
-// SyncBN forms (kod/configs/trainer/ddp.yaml:9 sync_batchnorm): the same single launches, with the rank's two sums
-// per channel exchanged through the peer buffers of kodhip_peer_* inside the kernel.  count = pixels of ALL ranks;
-// slot = first granule of this exchange in the buffers (4 * C granules); view = kodhip_peer_view's struct.
 int kodhip_bn_finalize_partials_peer(const float* partials, int T, double count, const float* gamma, const float* beta,
                                      float* running_mean, float* running_var, float momentum, float eps,
                                      float* scale, float* shift, float* mean, float* rstd, int C, int update_running,
                                      const void* view, unsigned int slot, hipStream_t stream) {
-  KOD_CHECK_ARG(partials && gamma && beta && scale && shift && mean && rstd && C > 0 && T > 0 && count > 0 && view,
-                "bn_finalize_partials_peer: bad args");
-  KOD_CHECK_ARG(!update_running || (running_mean && running_var), "bn_finalize_partials_peer: running stats missing");
-  const KodPeerView pv = *(const KodPeerView*)view;
-  KOD_CHECK_ARG(pv.world >= 1 && pv.world <= KOD_PEER_MAX && pv.world * 4 <= 64, "bn_finalize_partials_peer: bad peer view");
-  hipLaunchKernelGGL(bn_finalize_fused_kernel<true>, dim3(cdiv(C, 4)), dim3(256), 0, stream, partials, T, count, gamma, beta,
-                     running_mean, running_var, momentum, eps, scale, shift, mean, rstd, C, update_running, pv, slot);
-  KOD_LAUNCH_CHECK("bn_finalize_partials_peer");
-  return KOD_OK;
+  KOD_CHECK_ARG(view, "bn_finalize_partials_peer: bad args");
+  return bn_finalize_partials("bn_finalize_partials_peer", partials, T, count, gamma, beta, running_mean, running_var, momentum,
+                              eps, scale, shift, mean, rstd, C, update_running, view, slot, stream);
 }
 
 int kodhip_bn_bwd_coeffs_partials_peer(const float* partials, int T, double count, const float* gamma, const float* mean,
                                        const float* rstd, float* dgamma, float* dbeta, float* coef, int C,
                                        int raw_moment, const void* view, unsigned int slot, hipStream_t stream) {
-  KOD_CHECK_ARG(partials && gamma && mean && rstd && dgamma && dbeta && coef && C > 0 && T > 0 && count > 0 && view,
-                "bn_bwd_coeffs_partials_peer: bad args");
-  const KodPeerView pv = *(const KodPeerView*)view;
-  KOD_CHECK_ARG(pv.world >= 1 && pv.world <= KOD_PEER_MAX, "bn_bwd_coeffs_partials_peer: bad peer view");
-  hipLaunchKernelGGL(bn_bwd_coeffs_peer_kernel, dim3(cdiv(C, 4)), dim3(256), 0, stream, partials, T, count, gamma,
-                     mean, rstd, dgamma, dbeta, coef, C, raw_moment, pv, slot);
-  KOD_LAUNCH_CHECK("bn_bwd_coeffs_partials_peer");
-  return KOD_OK;
+  KOD_CHECK_ARG(view, "bn_bwd_coeffs_partials_peer: bad args");
+  const CoefJob j = {partials, T, count, gamma, mean, rstd, dgamma, dbeta, coef, C, raw_moment, 0};
+  return bn_bwd_coeffs_partials("bn_bwd_coeffs_partials_peer", &j, 1, view, slot, stream);
 }
 
 int kodhip_bn_bwd_coeffs_partials(const float* partials, int T, double count, const float* gamma, const float* mean,
                                   const float* rstd, float* dgamma, float* dbeta, float* coef, int C,
                                   int raw_moment, hipStream_t stream) {
-  KOD_CHECK_ARG(partials && gamma && mean && rstd && dgamma && dbeta && coef && C > 0 && T > 0 && count > 0,
-                "bn_bwd_coeffs_partials: bad args");
-  hipLaunchKernelGGL(bn_bwd_coeffs_fused_kernel, dim3(cdiv(C, 4)), dim3(256), 0, stream, partials, T, count, gamma,
-                     mean, rstd, dgamma, dbeta, coef, C, raw_moment);
-  KOD_LAUNCH_CHECK("bn_bwd_coeffs_partials");
-  return KOD_OK;
+  const CoefJob j = {partials, T, count, gamma, mean, rstd, dgamma, dbeta, coef, C, raw_moment, 0};
+  return bn_bwd_coeffs_partials("bn_bwd_coeffs_partials", &j, 1, nullptr, 0u, stream);
 }
 
 int kodhip_bn_bwd_coeffs_partials2(const float* partials0, int T0, double count0, const float* gamma0, const float* mean0,
@@ -656,25 +650,17 @@ int kodhip_bn_bwd_coeffs_partials2(const float* partials0, int T0, double count0
                                    const float* partials1, int T1, double count1, const float* gamma1, const float* mean1,
                                    const float* rstd1, float* dgamma1, float* dbeta1, float* coef1, int C1, int raw_moment1,
                                    hipStream_t stream) {
-  KOD_CHECK_ARG(partials0 && gamma0 && mean0 && rstd0 && dgamma0 && dbeta0 && coef0 && C0 > 0 && T0 > 0 && count0 > 0 &&
-                partials1 && gamma1 && mean1 && rstd1 && dgamma1 && dbeta1 && coef1 && C1 > 0 && T1 > 0 && count1 > 0,
-                "bn_bwd_coeffs_partials2: bad args");
-  CoefJob j0 = {partials0, T0, count0, gamma0, mean0, rstd0, dgamma0, dbeta0, coef0, C0, raw_moment0};
-  CoefJob j1 = {partials1, T1, count1, gamma1, mean1, rstd1, dgamma1, dbeta1, coef1, C1, raw_moment1};
-  hipLaunchKernelGGL(bn_bwd_coeffs_fused2_kernel, dim3(cdiv(C0 > C1 ? C0 : C1, 4), 2), dim3(256), 0, stream, j0, j1);
-  KOD_LAUNCH_CHECK("bn_bwd_coeffs_partials2");
-  return KOD_OK;
+  const CoefJob j[2] = {{partials0, T0, count0, gamma0, mean0, rstd0, dgamma0, dbeta0, coef0, C0, raw_moment0, 0},
+                        {partials1, T1, count1, gamma1, mean1, rstd1, dgamma1, dbeta1, coef1, C1, raw_moment1, 0}};
+  return bn_bwd_coeffs_partials("bn_bwd_coeffs_partials2", j, 2, nullptr, 0u, stream);
 }
 
+// eval-mode units (CoefJob's eval); the one-job form needs no count, the two-job form takes a mode per job
 int kodhip_bn_bwd_coeffs_eval_partials(const float* partials, int T, const float* gamma, const float* mean,
                                        const float* rstd, float* dgamma, float* dbeta, float* coef, int C,
                                        int raw_moment, hipStream_t stream) {
-  KOD_CHECK_ARG(partials && gamma && mean && rstd && dgamma && dbeta && coef && C > 0 && T > 0,
-                "bn_bwd_coeffs_eval_partials: bad args");
-  hipLaunchKernelGGL(bn_bwd_coeffs_eval_kernel, dim3(cdiv(C, 4)), dim3(256), 0, stream, partials, T, gamma, mean, rstd,
-                     dgamma, dbeta, coef, C, raw_moment);
-  KOD_LAUNCH_CHECK("bn_bwd_coeffs_eval_partials");
-  return KOD_OK;
+  const CoefJob j = {partials, T, 1.0, gamma, mean, rstd, dgamma, dbeta, coef, C, raw_moment, 1};
+  return bn_bwd_coeffs_partials("bn_bwd_coeffs_eval_partials", &j, 1, nullptr, 0u, stream);
 }
 
 int kodhip_bn_bwd_coeffs_eval_partials2(const float* partials0, int T0, double count0, const float* gamma0,
@@ -683,16 +669,9 @@ int kodhip_bn_bwd_coeffs_eval_partials2(const float* partials0, int T0, double c
                                         const float* partials1, int T1, double count1, const float* gamma1,
                                         const float* mean1, const float* rstd1, float* dgamma1, float* dbeta1,
                                         float* coef1, int C1, int raw_moment1, int eval1, hipStream_t stream) {
-  KOD_CHECK_ARG(partials0 && gamma0 && mean0 && rstd0 && dgamma0 && dbeta0 && coef0 && C0 > 0 && T0 > 0 &&
-                (eval0 || count0 > 0) &&
-                partials1 && gamma1 && mean1 && rstd1 && dgamma1 && dbeta1 && coef1 && C1 > 0 && T1 > 0 &&
-                (eval1 || count1 > 0), "bn_bwd_coeffs_eval_partials2: bad args");
-  CoefJob j0 = {partials0, T0, count0, gamma0, mean0, rstd0, dgamma0, dbeta0, coef0, C0, raw_moment0};
-  CoefJob j1 = {partials1, T1, count1, gamma1, mean1, rstd1, dgamma1, dbeta1, coef1, C1, raw_moment1};
-  hipLaunchKernelGGL(bn_bwd_coeffs_mode2_kernel, dim3(cdiv(C0 > C1 ? C0 : C1, 4), 2), dim3(256), 0, stream, j0, j1,
-                     eval0 ? 1 : 0, eval1 ? 1 : 0);
-  KOD_LAUNCH_CHECK("bn_bwd_coeffs_eval_partials2");
-  return KOD_OK;
+  const CoefJob j[2] = {{partials0, T0, count0, gamma0, mean0, rstd0, dgamma0, dbeta0, coef0, C0, raw_moment0, eval0 ? 1 : 0},
+                        {partials1, T1, count1, gamma1, mean1, rstd1, dgamma1, dbeta1, coef1, C1, raw_moment1, eval1 ? 1 : 0}};
+  return bn_bwd_coeffs_partials("bn_bwd_coeffs_eval_partials2", j, 2, nullptr, 0u, stream);
 }
 
 int kodhip_bn_eval_constants(const void* desc, int n_units, float eps, hipStream_t stream) {

@@ -263,7 +263,6 @@ __global__ __launch_bounds__(256) void maxpool5_fwd_kernel(const bf16_t* x, int 
 constexpr int POOL_BWD_THREADS = 128;       // 35 KB of private words per block: four blocks per CU
 // one thread's 4 x 4 inputs x 4 channels: pixel group (gy, gx) of image b, channel quad c4; words0..3: this thread's column
 // of the block's private-word arrays (stride POOL_BWD_THREADS floats between a thread's words)
-template <int POOL_BWD_THREADS>
 __device__ __forceinline__ void maxpool5_bwd_body(float* w0, float* w1, float* w2, float* w3,
                                                   const bf16_t* dy, int ldy, int ycoff, const unsigned char* idx,
                                                   bf16_t* dx, int ldx, int xcoff, int H, int W, int C, const float* dx32,
@@ -366,8 +365,8 @@ __global__ __launch_bounds__(POOL_BWD_THREADS) void maxpool5_bwd_kernel(const bf
   p /= WG;
   const int gy = (int)(p % HG);
   const int b = (int)(p / HG);
-  maxpool5_bwd_body<POOL_BWD_THREADS>(words0 + threadIdx.x, words1 + threadIdx.x, words2 + threadIdx.x, words3 + threadIdx.x,
-                                      dy, ldy, ycoff, idx, dx, ldx, xcoff, H, W, C, dx32, b, gy, gx, c4);
+  maxpool5_bwd_body(words0 + threadIdx.x, words1 + threadIdx.x, words2 + threadIdx.x, words3 + threadIdx.x,
+                    dy, ldy, ycoff, idx, dx, ldx, xcoff, H, W, C, dx32, b, gy, gx, c4);
 }
 
 // ------------------------------------------------------------------ max-pool of any odd window (SPPF kernel_sizes != 5)
@@ -589,72 +588,6 @@ __global__ void head_bias_reduce_kernel(const float* bpart, int nblk, int Npad, 
   else db_cls[n - 5 * A] = (float)s;
 }
 
-// ------------------------------------------------------------------ SGD
-// group id per 64-element granule: 0 bias, 1 decay, 2 norm, 255 padding
-// hyper (device memory, so a captured hipGraph sees per-step schedules): lr[3] | momentum[3] | wd[3] | grad_scale | flags |
-// dampening (12 floats; flags = nesterov + 2 maximize + 4 first step, small integers held in a float).  torch.optim.SGD
-// (torch/optim/sgd.py _single_tensor_sgd): g = maximize ? -g : g; g += wd * p; momentum != 0: buf = first step ? g :
-// mu * buf + (1 - dampening) * g; g = nesterov ? g + mu * buf : buf; p -= lr * g.  With dampening = 0 the first step needs no
-// flag (buf starts at zero: mu * 0 + g = g), which is the reference's configuration (smart_sgd.yaml).
-__global__ void sgd_nesterov_kernel(float* p, const float* g, float* buf, const unsigned char* gid, long n,
-                                    const float* hyper) {
-  long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i >= n) return;
-  unsigned char grp = gid[i >> 6];
-  if (grp > 2) return;
-  const float lr = hyper[grp], mu = hyper[3 + grp], wd = hyper[6 + grp], gscale = hyper[9];
-  const int flags = (int)hyper[10];
-  const bool nesterov = (flags & 1) != 0, maximize = (flags & 2) != 0, first = (flags & 4) != 0;
-  const float undamped = 1.0f - hyper[11];
-  f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);
-  f32x4 gv = kod_load_once<f32x4>(g + i);
-  f32x4 bv = *reinterpret_cast<const f32x4*>(buf + i);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float gg = gv[e] * gscale;
-    if (maximize) gg = -gg;
-    if (wd != 0.f) gg = gg + wd * pv[e];
-    float b = (first || mu == 0.f) ? gg : mu * bv[e] + undamped * gg;      // (undamped = 1: mu * buf + g, bit for bit)
-    bv[e] = b;
-    pv[e] = pv[e] - lr * (nesterov ? gg + mu * b : b);
-  }
-  *reinterpret_cast<f32x4*>(p + i) = pv;
-  *reinterpret_cast<f32x4*>(buf + i) = bv;
-}
-
-// sgd_nesterov_kernel for a freeze plan (engine/freeze.py): keep[i] == 0 marks an element of a frozen tensor, which no
-// weight decay, momentum or update touches (torch.optim.SGD skips a parameter whose .grad is None).  Per element: the
-// three head weights / biases share 64-element chunks.  Trainable elements compute exactly what the unmasked kernel does.
-__global__ void sgd_nesterov_masked_kernel(float* p, const float* g, float* buf, const unsigned char* gid,
-                                           const unsigned char* keep, long n, const float* hyper) {
-  long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i >= n) return;
-  unsigned char grp = gid[i >> 6];
-  if (grp > 2) return;
-  const uchar4 kv = *reinterpret_cast<const uchar4*>(keep + i);
-  const unsigned char kk[4] = {kv.x, kv.y, kv.z, kv.w};
-  if ((kk[0] | kk[1] | kk[2] | kk[3]) == 0) return;
-  const float lr = hyper[grp], mu = hyper[3 + grp], wd = hyper[6 + grp], gscale = hyper[9];
-  const int flags = (int)hyper[10];
-  const bool nesterov = (flags & 1) != 0, maximize = (flags & 2) != 0, first = (flags & 4) != 0;
-  const float undamped = 1.0f - hyper[11];
-  f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);
-  f32x4 gv = kod_load_once<f32x4>(g + i);
-  f32x4 bv = *reinterpret_cast<const f32x4*>(buf + i);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    if (!kk[e]) continue;
-    float gg = gv[e] * gscale;
-    if (maximize) gg = -gg;
-    if (wd != 0.f) gg = gg + wd * pv[e];
-    float b = (first || mu == 0.f) ? gg : mu * bv[e] + undamped * gg;
-    bv[e] = b;
-    pv[e] = pv[e] - lr * (nesterov ? gg + mu * b : b);
-  }
-  *reinterpret_cast<f32x4*>(p + i) = pv;
-  *reinterpret_cast<f32x4*>(buf + i) = bv;
-}
-
 // ------------------------------------------------------------------ gradient norm / clipping (include/kodhip.h: clip block)
 // Clip block (device, KOD_CLIP_FLOATS fp32): outputs [0] total norm | [1..3] norms of the groups bias, decay, norm | [4] clip
 // coefficient | [5] 1 when the total norm is NaN / Inf | [6] steps skipped so far | [7] spare; input [8] max_norm (norm
@@ -663,9 +596,9 @@ __global__ void sgd_nesterov_masked_kernel(float* p, const float* g, float* buf,
 #define KOD_CLIP_FLOATS 16
 #define KOD_NORM_BLOCKS 1024          // partial slots: 4 blocks of 256 lanes per CU on 256 CUs; fixed, so the bits do not
                                       // depend on the device the step runs on
-enum { KOD_CLIP_NORM = 0, KOD_CLIP_VALUE = 1 };
+enum { KOD_CLIP_NONE = -1, KOD_CLIP_NORM = 0, KOD_CLIP_VALUE = 1 };      // (0 / 1: the `mode` of kodhip.h; none: no clip block)
 
-// Sum of squares of the fp32 product gscale * g (what the SGD kernels form first) per optimizer group: squares and sums
+// Sum of squares of the fp32 product gscale * g (what sgd_nesterov_kernel forms first) per optimizer group: squares and sums
 // in fp64 per lane, fp64 wave / block reduction, ONE partial per block and group in a fixed slot - no atomics, the same
 // bits on every run.  count[i] == 0 (may be NULL: everything counts) leaves element i out: arena padding, frozen tensors.
 // NT: non-temporal loads of the gradients (the SGD kernel re-reads them right after; which form is faster is a
@@ -734,21 +667,32 @@ __global__ __launch_bounds__(64) void grad_norm_finalize_kernel(const double* __
   if (bad && skip_nonfinite) clip[6] = clip[6] + 1.0f;
 }
 
-// The SGD kernels above with the gradient clipped between the scale and the update (torch's order: DDP's average, then
-// clip_grad_*_): MODE norm: gg = (g * gscale) * coef; MODE value: gg = clamp(g * gscale, -v, +v) with clamp_'s NaN (it stays).
-// With coef == 1 the bits are those of sgd_nesterov(_masked)_kernel.  skip_nonfinite and a NaN / Inf norm: nothing is
-// touched (every lane reads the same flag: a uniform branch).
-template <bool MASKED, int MODE>
-__global__ void sgd_nesterov_clipped_kernel(float* p, const float* g, float* buf, const unsigned char* gid,
-                                            const unsigned char* keep, long n, const float* hyper, const float* clip,
-                                            int skip_nonfinite) {
+// ------------------------------------------------------------------ SGD
+// group id per 64-element granule: 0 bias, 1 decay, 2 norm, 255 padding
+// hyper (device memory, so a captured hipGraph sees per-step schedules): lr[3] | momentum[3] | wd[3] | grad_scale | flags |
+// dampening (12 floats; flags = nesterov + 2 maximize + 4 first step, small integers held in a float).  torch.optim.SGD
+// (torch/optim/sgd.py _single_tensor_sgd): g = maximize ? -g : g; g += wd * p; momentum != 0: buf = first step ? g :
+// mu * buf + (1 - dampening) * g; g = nesterov ? g + mu * buf : buf; p -= lr * g.  With dampening = 0 the first step needs no
+// flag (buf starts at zero: mu * 0 + g = g), which is the reference's configuration (smart_sgd.yaml).
+// MASKED, for a freeze plan (engine/freeze.py): keep[i] == 0 marks an element of a frozen tensor, which no weight decay,
+// momentum or update touches (torch.optim.SGD skips a parameter whose .grad is None).  Per element: the three head weights /
+// biases share 64-element chunks.
+// CLIP: the gradient is clipped between the scale and the update (torch's order: DDP's average, then clip_grad_*_): norm:
+// gg = (g * gscale) * coef; value: gg = clamp(g * gscale, -v, +v) with clamp_'s NaN (it stays); skip_nonfinite and a NaN / Inf
+// norm: nothing is touched (every lane reads the same flag: a uniform branch).  KOD_CLIP_NONE reads neither `clip` nor
+// skip_nonfinite, and only MASKED reads `keep`.
+template <bool MASKED, int CLIP>
+__global__ void sgd_nesterov_kernel(float* p, const float* g, float* buf, const unsigned char* gid, const unsigned char* keep,
+                                    long n, const float* hyper, const float* clip, int skip_nonfinite) {
   long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i >= n) return;
-  if (skip_nonfinite && clip[5] != 0.f) return;
+  if constexpr (CLIP != KOD_CLIP_NONE) {
+    if (skip_nonfinite && clip[5] != 0.f) return;
+  }
   unsigned char grp = gid[i >> 6];
   if (grp > 2) return;
   unsigned char kk[4] = {1, 1, 1, 1};
-  if (MASKED) {
+  if constexpr (MASKED) {
     const uchar4 kv = *reinterpret_cast<const uchar4*>(keep + i);
     kk[0] = kv.x; kk[1] = kv.y; kk[2] = kv.z; kk[3] = kv.w;
     if ((kk[0] | kk[1] | kk[2] | kk[3]) == 0) return;
@@ -757,7 +701,8 @@ __global__ void sgd_nesterov_clipped_kernel(float* p, const float* g, float* buf
   const int flags = (int)hyper[10];
   const bool nesterov = (flags & 1) != 0, maximize = (flags & 2) != 0, first = (flags & 4) != 0;
   const float undamped = 1.0f - hyper[11];
-  const float coef = clip[4], cv = clip[8];
+  float coef = 1.f, cv = 0.f;
+  if constexpr (CLIP != KOD_CLIP_NONE) { coef = clip[4]; cv = clip[8]; }
   f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);
   f32x4 gv = kod_load_once<f32x4>(g + i);
   f32x4 bv = *reinterpret_cast<const f32x4*>(buf + i);
@@ -765,11 +710,11 @@ __global__ void sgd_nesterov_clipped_kernel(float* p, const float* g, float* buf
   for (int e = 0; e < 4; ++e) {
     if (MASKED && !kk[e]) continue;
     float gg = gv[e] * gscale;
-    if (MODE == KOD_CLIP_NORM) gg = gg * coef;
-    else gg = gg < -cv ? -cv : (gg > cv ? cv : gg);
+    if constexpr (CLIP == KOD_CLIP_NORM) gg = gg * coef;
+    if constexpr (CLIP == KOD_CLIP_VALUE) gg = gg < -cv ? -cv : (gg > cv ? cv : gg);
     if (maximize) gg = -gg;
     if (wd != 0.f) gg = gg + wd * pv[e];
-    float b = (first || mu == 0.f) ? gg : mu * bv[e] + undamped * gg;
+    float b = (first || mu == 0.f) ? gg : mu * bv[e] + undamped * gg;      // (undamped = 1: mu * buf + g, bit for bit)
     bv[e] = b;
     pv[e] = pv[e] - lr * (nesterov ? gg + mu * b : b);
   }
@@ -929,24 +874,46 @@ int kodhip_head_bwd_prep(const float* g, void* dy, float* workspace, float* db_b
   return KOD_OK;
 }
 
-// hyper: DEVICE pointer to 10 floats = lr[3], momentum[3], weight_decay[3], grad_scale  (groups: bias, decay, norm)
+// One launcher for the three SGD entry points; `fn` names the one that was called in the messages.  hyper: DEVICE pointer
+// to the 12 floats described above sgd_nesterov_kernel (groups: bias, decay, norm); keep (may be NULL: everything
+// trainable): u8 per element; clip (NULL: no clipping): the clip block, with mode 0 norm (reads clip[4]) or 1 value (clip[8]).
+static int sgd_nesterov(const char* fn, float* params, const float* grads, float* momentum_buf, const void* group_ids,
+                        const void* keep_mask, long n, const float* hyper, const float* clip, int mode, int skip_nonfinite,
+                        hipStream_t stream) {
+  KOD_CHECK_ARG(params && grads && momentum_buf && group_ids && hyper && n > 0 && n % 64 == 0, "%s: bad args", fn);
+  KOD_CHECK_ARG(!clip || mode == KOD_CLIP_NORM || mode == KOD_CLIP_VALUE, "%s: unknown mode %d", fn, mode);
+  const int cl = clip ? mode : KOD_CLIP_NONE;
+#define KOD_SGD(M, CL) \
+  hipLaunchKernelGGL((sgd_nesterov_kernel<M, CL>), dim3(cdiv(n / 4, 256)), dim3(256), 0, stream, params, grads, momentum_buf, \
+                     (const unsigned char*)group_ids, (const unsigned char*)keep_mask, n, hyper, clip, skip_nonfinite)
+#define KOD_SGD_CLIP(M)                                                                                              \
+  do {                                                                                                               \
+    if (cl == KOD_CLIP_NONE) KOD_SGD(M, KOD_CLIP_NONE); else if (cl == KOD_CLIP_NORM) KOD_SGD(M, KOD_CLIP_NORM); else KOD_SGD(M, KOD_CLIP_VALUE); \
+  } while (0)
+  if (keep_mask) KOD_SGD_CLIP(true); else KOD_SGD_CLIP(false);
+#undef KOD_SGD_CLIP
+#undef KOD_SGD
+  KOD_LAUNCH_CHECK(fn);
+  return KOD_OK;
+}
+
 int kodhip_sgd_nesterov(float* params, const float* grads, float* momentum_buf, const void* group_ids,
                         long n, const float* hyper, hipStream_t stream) {
-  KOD_CHECK_ARG(params && grads && momentum_buf && group_ids && hyper && n > 0 && n % 64 == 0, "sgd_nesterov: bad args");
-  hipLaunchKernelGGL(sgd_nesterov_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, stream, params, grads, momentum_buf,
-                     (const unsigned char*)group_ids, n, hyper);
-  KOD_LAUNCH_CHECK("sgd_nesterov");
-  return KOD_OK;
+  return sgd_nesterov("sgd_nesterov", params, grads, momentum_buf, group_ids, nullptr, n, hyper, nullptr, 0, 0, stream);
 }
 
 int kodhip_sgd_nesterov_masked(float* params, const float* grads, float* momentum_buf, const void* group_ids,
                                const void* keep_mask, long n, const float* hyper, hipStream_t stream) {
-  KOD_CHECK_ARG(params && grads && momentum_buf && group_ids && keep_mask && hyper && n > 0 && n % 64 == 0,
-                "sgd_nesterov_masked: bad args");
-  hipLaunchKernelGGL(sgd_nesterov_masked_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, stream, params, grads, momentum_buf,
-                     (const unsigned char*)group_ids, (const unsigned char*)keep_mask, n, hyper);
-  KOD_LAUNCH_CHECK("sgd_nesterov_masked");
-  return KOD_OK;
+  KOD_CHECK_ARG(keep_mask, "sgd_nesterov_masked: bad args");
+  return sgd_nesterov("sgd_nesterov_masked", params, grads, momentum_buf, group_ids, keep_mask, n, hyper, nullptr, 0, 0, stream);
+}
+
+int kodhip_sgd_nesterov_clipped(float* params, const float* grads, float* momentum_buf, const void* group_ids,
+                                const void* keep_mask, long n, const float* hyper, const float* clip, int mode,
+                                int skip_nonfinite, hipStream_t stream) {
+  KOD_CHECK_ARG(clip, "sgd_nesterov_clipped: bad args");
+  return sgd_nesterov("sgd_nesterov_clipped", params, grads, momentum_buf, group_ids, keep_mask, n, hyper, clip, mode,
+                      skip_nonfinite, stream);
 }
 
 int kodhip_clip_block_bytes(void) { return KOD_CLIP_FLOATS * (int)sizeof(float); }
@@ -969,25 +936,6 @@ int kodhip_grad_norm(const float* grads, const void* group_ids, const void* coun
   KOD_LAUNCH_CHECK("grad_norm");
   hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(64), 0, stream, (const double*)workspace, grid, clip, skip_nonfinite);
   KOD_LAUNCH_CHECK("grad_norm_finalize");
-  return KOD_OK;
-}
-
-// keep_mask may be NULL (everything trainable); mode: 0 norm (reads clip[4]), 1 value (reads clip[8])
-int kodhip_sgd_nesterov_clipped(float* params, const float* grads, float* momentum_buf, const void* group_ids,
-                                const void* keep_mask, long n, const float* hyper, const float* clip, int mode,
-                                int skip_nonfinite, hipStream_t stream) {
-  KOD_CHECK_ARG(params && grads && momentum_buf && group_ids && hyper && clip && n > 0 && n % 64 == 0,
-                "sgd_nesterov_clipped: bad args");
-  KOD_CHECK_ARG(mode == KOD_CLIP_NORM || mode == KOD_CLIP_VALUE, "sgd_nesterov_clipped: unknown mode %d", mode);
-  const dim3 grid(cdiv(n / 4, 256)), blk(256);
-  const unsigned char* gid = (const unsigned char*)group_ids;
-  const unsigned char* keep = (const unsigned char*)keep_mask;
-#define KOD_SGD_CLIPPED(M, MODE) \
-  hipLaunchKernelGGL((sgd_nesterov_clipped_kernel<M, MODE>), grid, blk, 0, stream, params, grads, momentum_buf, gid, keep, n, hyper, clip, skip_nonfinite)
-  if (keep) { if (mode == KOD_CLIP_NORM) KOD_SGD_CLIPPED(true, KOD_CLIP_NORM); else KOD_SGD_CLIPPED(true, KOD_CLIP_VALUE); }
-  else { if (mode == KOD_CLIP_NORM) KOD_SGD_CLIPPED(false, KOD_CLIP_NORM); else KOD_SGD_CLIPPED(false, KOD_CLIP_VALUE); }
-#undef KOD_SGD_CLIPPED
-  KOD_LAUNCH_CHECK("sgd_nesterov_clipped");
   return KOD_OK;
 }
 
