@@ -403,6 +403,20 @@ int kodhip_map_match(const float* det, const int* ndet, const double* gt_boxes, 
                      const int* gt_start, void* tp, void* counted, int B, int max_det, int nc,
                      const double* iou_thresholds /* host */, int T, int max_per_class, kodStream_t stream);
 
+/* detection confusion matrix (YOLOv5 val.py ConfusionMatrix.process_batch, deterministic): the arrays of kodhip_map_match;
+ * matrix is device int64 [(nc+1)*(nc+1)], row = predicted class, column = true class, index nc = background, and is ADDED
+ * to.  Per image, class-agnostic, fp64 IoU without +1: a detection with score > conf_thres (fp32, strict) picks the
+ * ground truth of largest IoU > iou_thres (strict; ties -> lower ground-truth index); a ground truth takes, among the
+ * detections that picked it, the one of largest IoU (ties -> lower detection index); losers are not re-matched.  Matched
+ * pair -> [class][label], ground truth nobody took -> [nc][label], kept detection not taken -> [class][nc].  Classes
+ * outside [0, nc) take no part.  No cap on ground truths per image; max_det <= kodhip_confusion_max_det().
+ * kodhip_confusion_lds_classes(): the largest nc whose per-image matrix is summed on chip before the atomic flush. */
+int kodhip_confusion_max_det(void);
+int kodhip_confusion_lds_classes(void);
+int kodhip_confusion_match(const float* det, const int* ndet, const double* gt_boxes, const long* gt_labels,
+                           const int* gt_start, long long* matrix, int B, int max_det, int nc, float conf_thres,
+                           double iou_thres, kodStream_t stream);
+
 /* ---- data-parallel collectives (Lightning strategy=ddp + sync_batchnorm=True, kod/configs/trainer/ddp.yaml:4-9:
  *      torch DistributedDataParallel's bucketed gradient all-reduce, SyncBatchNorm's statistic exchange and the
  *      initial parameter/buffer broadcast).  RCCL enqueued on the caller's stream; hipGraph-capturable. ------ */

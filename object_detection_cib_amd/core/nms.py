@@ -16,6 +16,17 @@ from .. import _host, _lib
 _WORKSPACE = {}
 
 
+class PackedDetections(list):
+    """What non_max_suppression returns: the list of per-image [n, 6] tensors of the reference, which are views of ONE
+    device buffer.  A consumer that runs on the device (DeviceConfusionMatrix) takes the buffer and the device-side counts
+    as they are instead of re-packing the list: `packed` [B, max_det, 6] fp32 (rows beyond an image's count are
+    uninitialised), `counts` [B] int32 on the device.  They describe the list as it was returned."""
+
+    def __init__(self, items, packed: torch.Tensor, counts: torch.Tensor):
+        super().__init__(items)
+        self.packed, self.counts = packed, counts
+
+
 def non_max_suppression(detections: torch.Tensor, conf_thres: float = 0.25, nms_thres: float = 0.45,
                         classes=None) -> Sequence[torch.Tensor]:
     _lib.require_gpu()
@@ -48,4 +59,4 @@ def non_max_suppression(detections: torch.Tensor, conf_thres: float = 0.25, nms_
                                      nout.data_ptr(), B, rows, nc, float(conf_thres), float(nms_thres), max_det,
                                      max_nms, max_wh, torch.cuda.current_stream().cuda_stream), "nms")
     counts = _host.fetch(nout)[0].tolist()                           # one polling hand-off per batch (sizes the outputs)
-    return [out[b, :n] for b, n in enumerate(counts)]
+    return PackedDetections([out[b, :n] for b, n in enumerate(counts)], out, nout)

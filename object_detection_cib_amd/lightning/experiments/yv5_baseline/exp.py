@@ -16,6 +16,7 @@ import torch
 from .... import _lib
 from ....core.types import FeatureShape
 from ....core.nms import non_max_suppression
+from ....core.label_assignment.yv5 import BatchedTargets
 from ....nn.optim.smart import SmartOptimizer, FusedSGD, CLIP_ALGORITHMS
 from ....nn.optim.schedulers import LinearScheduler
 from ...callbacks.map_eval import DeviceMAPEvaluator
@@ -52,7 +53,8 @@ class DefaultYolov5Experiment:
                  val_nms_conf_threshold: float = 0.001, val_nms_iou_threshold: float = 0.6, *, max_epochs: int = 300,
                  graphed: bool = False, max_targets: int = 4096, world_size: int = 1,
                  gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
-                 eval_fused: Optional[bool] = None):
+                 eval_fused: Optional[bool] = None, val_confusion: bool = False, val_confusion_conf: float = 0.25,
+                 val_confusion_iou: float = 0.45):
         if gradient_clip_algorithm not in CLIP_ALGORITHMS:
             raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected one of {CLIP_ALGORITHMS}")
         # Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm): handed to the FusedSGD / the captured step
@@ -83,6 +85,12 @@ class DefaultYolov5Experiment:
         # own shard.  None = never a collective (rank-0-only validation cannot hang on its peers); an explicit process
         # group + "mean" / "global" = DeviceMAPEvaluator.get_report's two DDP modes
         self.val_process_group, self.val_sync = "auto", "mean"
+        # val_confusion: validate() also feeds every batch to a DeviceConfusionMatrix (YOLOv5's val.py diagnostic: the NMS
+        # output at the validation thresholds, filtered again at val_confusion_conf inside the kernel) and reports
+        # precision_<class> / recall_<class>; the object stays readable as `self.confusion`.  Its counts are SUMMED over
+        # the validation group, whatever val_sync says.
+        self.val_confusion, self.val_confusion_conf, self.val_confusion_iou = val_confusion, val_confusion_conf, val_confusion_iou
+        self.confusion = None
 
     # exp.py:156-162
     def configure_optimizers(self):
@@ -223,17 +231,33 @@ class DefaultYolov5Experiment:
 
     def validate(self, batches: Sequence, num_classes: int, class_names=None) -> dict:
         ev = DeviceMAPEvaluator(num_classes, class_names)
+        cm = None
+        if self.val_confusion:
+            from ...callbacks.confusion import DeviceConfusionMatrix
+            cm = self.confusion = DeviceConfusionMatrix(num_classes, class_names, self.val_confusion_conf, self.val_confusion_iou)
         _lib.limit_host_threads()
         if self.eval_fused is not None:
             self.net.fuse_eval(self.eval_fused)
         with _gc_paused():
             for b in batches:
                 targets, dets = self.validation_step(b)
-                ev.add_batch(targets, dets)
+                if cm is not None:         # both consumers take the batch's boxes as one device upload
+                    if not isinstance(targets, BatchedTargets):
+                        targets = BatchedTargets.from_targets(targets, dets[0].device if len(dets) else torch.device("cuda"))
+                    ev.add_batch(targets, dets)
+                    cm.add_batch(targets, dets)
+                else:
+                    ev.add_batch(targets, dets)
         pg = self._val_group()
         if pg is not None and self.val_process_group == "auto":
             self._all_ranks_validate(pg)
-        return ev.get_report(pg, self.val_sync)
+        report = ev.get_report(pg, self.val_sync)
+        if cm is not None:
+            pc = cm.per_class(pg)
+            for c, name in enumerate(cm.names):
+                report[f"precision_{name}"] = float(pc["precision"][c])
+                report[f"recall_{name}"] = float(pc["recall"][c])
+        return report
 
     def _all_ranks_validate(self, pg, timeout_s: float = 300.0):
         """The default cross-rank report ("auto") is a collective: every rank of the data-parallel group must call

@@ -1,4 +1,7 @@
-"""Validation loop throughput: device resize/letter-box -> eval forward -> decode -> NMS -> mAP matching.  Diagnostic."""
+"""Validation loop throughput: device resize/letter-box -> eval forward -> decode -> NMS -> mAP matching.  Diagnostic.
+--confusion: with the device confusion matrix on (DefaultYolov5Experiment(val_confusion=True)).  --repeats N: time the loop N
+times, print median and spread.  --ab: alternate feature off / on from repeat to repeat in this one process (same machine,
+same session; processes of the same code differ by a few per cent) and print both."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -17,7 +20,8 @@ cache = synth.coco_zipf_like(256, 500, 3, nc)          # original-size images (l
 pipe = DeviceValPipeline([c[0] for c in cache], [c[1] for c in cache], [c[2] for c in cache], S, dev)
 net, loss = bench.build(nc, dev)
 infos = (voc_anchor_info(8), voc_anchor_info(16), voc_anchor_info(32))
-exp = DefaultYolov5Experiment(net, loss, LayerwiseAnchorInfo(*infos), graphed="--eager" not in sys.argv)
+exp = DefaultYolov5Experiment(net, loss, LayerwiseAnchorInfo(*infos), graphed="--eager" not in sys.argv,
+                              val_confusion="--confusion" in sys.argv)
 # a few training-mode forwards so that BN running stats are sane, then eval
 x, tg = bench.synth_batch(B, S, nc, 1, dev)
 for _ in range(2): net(x)
@@ -48,7 +52,29 @@ if "--stages" in sys.argv:          # the same loop with a synchronize + clock a
         b, t_prep = T(lambda: next(it))
         (tg, dets), t_val = T(lambda: exp.validation_step(b))
         _, t_map = T(lambda: ev.add_batch(tg, dets))
+        if exp.val_confusion:              # host time of the launch-only add_batch, and with its kernel drained
+            a = time.perf_counter(); exp.confusion.add_batch(tg, dets); t_host = (time.perf_counter() - a) * 1e3
+            torch.cuda.synchronize(); t_all = (time.perf_counter() - a) * 1e3
+            print(f"stage times batch {i}: confusion add_batch host {t_host:.3f} ms, drained {t_all:.3f} ms")
         ms = torch.cuda.memory_stats()
         print(f"stage times batch {i}: prep {t_prep:.2f} validation_step {t_val:.2f} add_batch {t_map:.2f} ms | device allocs "
               f"{ms.get('num_device_alloc')} frees {ms.get('num_device_free')} reserved {ms.get('reserved_bytes.all.current', 0) / 1e9:.2f} GB")
 print(f"validation: {dt*1e3:.1f} ms/batch = {B/dt:.0f} img/s (random-init weights: worst case box counts); keys {list(rep)[:4]}")
+if "--repeats" in sys.argv or "--ab" in sys.argv:
+    reps = int(sys.argv[sys.argv.index("--repeats") + 1]) if "--repeats" in sys.argv else 5
+    modes = (False, True) if "--ab" in sys.argv else (exp.val_confusion,)
+    exp.val_confusion = True in modes
+    exp.validate(batches(4), nc)              # (the feature's own first-call allocations stay out of the timed repeats)
+    rates = {m: [] for m in modes}
+    n *= 4                                    # ~1 s per timed window
+    for r in range(reps):
+        for m in (modes if r % 2 == 0 else modes[::-1]):
+            exp.val_confusion = m
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            exp.validate(batches(n), nc)
+            torch.cuda.synchronize()
+            rates[m].append(B * n / (time.perf_counter() - t0))
+    for m in modes:
+        v = np.sort(rates[m])
+        print(f"validation confusion={'on' if m else 'off'}: median {np.median(v):.0f} img/s, min {v[0]:.0f}, max {v[-1]:.0f} over {reps} "
+              f"repeats of {n} batches; all {[round(x) for x in rates[m]]}")
