@@ -396,6 +396,27 @@ int kodhip_nms(const float* det, void* keys, int key_cap, int* ncand, float* out
                int B, int rows, int nc, float conf_thres, float nms_thres, int max_det, int max_nms, float max_wh,
                kodStream_t stream);
 
+/* kodhip_nms with the deployment options of YOLOv5's detect.py.  With best_class = 0, class_keep = NULL and
+ * letterbox = NULL it is kodhip_nms: the same launches, the same bits.
+ *   best_class = 1  (multi_label=False) one candidate per row: score = max over c of fp32(cls_c * obj), the LOWEST class
+ *                   index among equal maxima; kept if obj > conf and score > conf.  Keys, sort and greedy pass are those
+ *                   of kodhip_nms, candidates are listed in row order, and key_cap >= rows holds every candidate (the
+ *                   multi-label form needs rows * nc).
+ *   class_keep      u8 [nc]: a candidate whose class has 0 is dropped - in best-class mode AFTER the argmax (a row whose
+ *                   best class is not listed is gone even if a listed class passes conf); in multi-label mode this is
+ *                   the same as zeroing the class columns.
+ *   letterbox       [B]: NMS runs in the letterboxed frame; the rows written to `out` become
+ *                   x' = min(max(fp32(fp32(x - left) * scale_x), 0), width), y' likewise with top, scale_y, height
+ *                   (one small launch behind the greedy pass).  Boxes that clipping makes degenerate stay.
+ * Class-agnostic suppression needs no option: max_wh = 0.  max_det in 1..300, key_cap a power of two >= 64,
+ * best_class 0 or 1 - checked before any launch. */
+typedef struct KodLetterbox { float left, top, scale_x, scale_y, width, height; } KodLetterbox;   /* 24 bytes */
+int kodhip_letterbox_bytes(void);
+int kodhip_nms_ex(const float* det, void* keys, int key_cap, int* ncand, float* out, int* nout,
+                  int B, int rows, int nc, float conf_thres, float nms_thres, int max_det, int max_nms, float max_wh,
+                  int best_class, const unsigned char* class_keep /* [nc] or NULL */,
+                  const KodLetterbox* letterbox /* [B] or NULL */, kodStream_t stream);
+
 /* detection <-> ground-truth matching of COCO-style mAP (kod/lightning/callbacks/pycoco_map_eval.py:50-125 ->
  * vision_evaluation -> pycocotools COCOeval.evaluateImg); tp [B][max_det][T] u8, counted [B][max_det] u8.
  * At most 256 ground truths per image take part in the matching (later ones are never matched). */

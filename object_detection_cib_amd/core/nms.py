@@ -3,11 +3,16 @@
 Same signature and result (list of [n<=300, 6] tensors: x1, y1, x2, y2, conf, cls); the boolean-mask /
 nonzero / argsort / torchvision.ops.nms chain of the reference is three HIP kernels per batch
 (csrc/postproc.hip), so validation stays on the device.
+
+The keyword-only arguments are the options of YOLOv5's detect.py (kodhip_nms_ex): `agnostic`, `multi_label`, `max_det` and
+`letterbox`, which maps the kept boxes back into each image's own pixels.  With all of them at their defaults the call is
+the validation one, unchanged.
 """
 from __future__ import annotations
 
-from typing import Sequence
+from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from .. import _host, _lib
@@ -27,36 +32,73 @@ class PackedDetections(list):
         self.packed, self.counts = packed, counts
 
 
-def non_max_suppression(detections: torch.Tensor, conf_thres: float = 0.25, nms_thres: float = 0.45,
-                        classes=None) -> Sequence[torch.Tensor]:
-    _lib.require_gpu()
-    det = detections.contiguous().float()
-    B, rows, P = det.shape
-    nc = P - 5
-    if classes is not None:
-        # nms.py:52-54 drops candidates whose class is not listed, before the top-30000 cut: a zeroed class
-        # probability never passes `cls * obj > conf_thres`, so masking the columns is the same filter
-        keep = torch.zeros(nc, dtype=torch.bool, device=det.device)
-        keep[torch.as_tensor(list(classes), dtype=torch.long, device=det.device)] = True
-        det = det.clone()
-        det[..., 5:] *= keep.to(det.dtype)
-    max_wh, max_det, max_nms = 4096.0, 300, 30000                  # nms.py:22-26
-    need = rows * nc
-    key_cap = 64
-    while key_cap < need:
-        key_cap <<= 1
-    dev = det.device
+def _workspace(dev, n: int) -> torch.Tensor:
     # the sort keys are the one large workspace (B * key_cap * 8 B = 134 MB at 64 x 25200 x 10): kept across calls,
     # returning it to the caching allocator every batch makes later allocations fall through to hipMalloc (tens of ms)
     # (grow-only per device: alternating full and partial validation batches reuse the largest buffer)
     keys = _WORKSPACE.get(dev)
-    if keys is None or keys.numel() < B * key_cap:
-        keys = _WORKSPACE[dev] = torch.empty(B * key_cap, dtype=torch.int64, device=dev)
+    if keys is None or keys.numel() < n:
+        keys = _WORKSPACE[dev] = torch.empty(n, dtype=torch.int64, device=dev)
+    return keys
+
+
+def _key_cap(need: int) -> int:
+    key_cap = 64
+    while key_cap < need:
+        key_cap <<= 1
+    return key_cap
+
+
+def non_max_suppression(detections: torch.Tensor, conf_thres: float = 0.25, nms_thres: float = 0.45,
+                        classes=None, *, agnostic: bool = False, multi_label: Optional[bool] = None, max_det: int = 300,
+                        letterbox=None) -> Sequence[torch.Tensor]:
+    """detections [B, rows, 5 + nc].  classes: keep these class ids only.  agnostic: boxes of different classes suppress
+    each other.  multi_label: None = the reference's rule (nc > 1: every class over conf_thres is a candidate); False = one
+    candidate per row, its best class (detect.py; the key workspace then holds `rows` keys per image, not `rows * nc`).
+    max_det: 1..300 rows per image.  letterbox: float32 [B, 6] (left, top, scale_x, scale_y, width, height per image,
+    KodLetterbox): the kept boxes become min(max((x - left) * scale_x, 0), width) and likewise for y."""
+    _lib.require_gpu()
+    if not 1 <= int(max_det) <= 300:
+        raise ValueError(f"max_det {max_det}: expected 1..300 (the greedy pass keeps its survivors in LDS)")
+    det = detections.contiguous().float()
+    B, rows, P = det.shape
+    nc = P - 5
+    dev = det.device
+    max_wh, max_nms = 4096.0, 30000                                # nms.py:22-26
+    multi = nc > 1 if multi_label is None else bool(multi_label)
+    extended = agnostic or multi_label is not None or int(max_det) != 300 or letterbox is not None
+    keep = None
+    if classes is not None:
+        keep = torch.zeros(nc, dtype=torch.bool, device=dev)
+        keep[torch.as_tensor(list(classes), dtype=torch.long, device=dev)] = True
+        if not extended:
+            # nms.py:52-54 drops candidates whose class is not listed, before the top-30000 cut: a zeroed class
+            # probability never passes `cls * obj > conf_thres`, so masking the columns is the same filter
+            det = det.clone()
+            det[..., 5:] *= keep.to(det.dtype)
+    max_det = int(max_det)
+    key_cap = _key_cap(rows * nc if (multi or not extended) else rows)
+    keys = _workspace(dev, B * key_cap)
     ncand = torch.empty(B, dtype=torch.int32, device=dev)
     out = torch.empty((B, max_det, 6), dtype=torch.float32, device=dev)
     nout = torch.empty(B, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().kodhip_nms(det.data_ptr(), keys.data_ptr(), key_cap, ncand.data_ptr(), out.data_ptr(),
-                                     nout.data_ptr(), B, rows, nc, float(conf_thres), float(nms_thres), max_det,
-                                     max_nms, max_wh, torch.cuda.current_stream().cuda_stream), "nms")
+    stream = torch.cuda.current_stream().cuda_stream
+    if not extended:
+        _lib.check(_lib.lib().kodhip_nms(det.data_ptr(), keys.data_ptr(), key_cap, ncand.data_ptr(), out.data_ptr(),
+                                         nout.data_ptr(), B, rows, nc, float(conf_thres), float(nms_thres), max_det,
+                                         max_nms, max_wh, stream), "nms")
+    else:
+        lb = None
+        if letterbox is not None:
+            lb = letterbox if torch.is_tensor(letterbox) else torch.from_numpy(np.ascontiguousarray(letterbox, dtype=np.float32))
+            lb = lb.to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(lb.shape) != (B, 6):
+                raise ValueError(f"letterbox shape {tuple(lb.shape)}: expected ({B}, 6)")
+        mask = keep.to(torch.uint8) if keep is not None else None
+        _lib.check(_lib.lib().kodhip_nms_ex(det.data_ptr(), keys.data_ptr(), key_cap, ncand.data_ptr(), out.data_ptr(),
+                                            nout.data_ptr(), B, rows, nc, float(conf_thres), float(nms_thres), max_det,
+                                            max_nms, 0.0 if agnostic else max_wh, 0 if multi else 1,
+                                            mask.data_ptr() if mask is not None else None,
+                                            lb.data_ptr() if lb is not None else None, stream), "nms_ex")
     counts = _host.fetch(nout)[0].tolist()                           # one polling hand-off per batch (sizes the outputs)
     return PackedDetections([out[b, :n] for b, n in enumerate(counts)], out, nout)

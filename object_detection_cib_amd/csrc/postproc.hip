@@ -9,7 +9,16 @@
 //
 // Candidate compaction by ballot prefix sums (one block per image), a chip-wide bitonic sort of (score desc,
 // candidate index asc) 64-bit keys, then a wave-batched greedy pass that keeps the <=300 survivors in LDS.  Everything is integer / comparison logic on fp32 values => results are bit-identical to the reference.
+//
+//   nms_ex : the deployment form (YOLOv5 detect.py): best-class candidates (multi_label=False: one candidate per row, the
+//            argmax of cls * obj, lowest class index among equal maxima), a class filter applied to the candidate's class,
+//            and the kept rows mapped from the letterboxed frame back to the source image (subtract the pad, multiply by
+//            the inverse scale, clip - each operation rounded on its own).  Same keys, same sort, same greedy pass: the
+//            best-class form needs `rows` keys per image where the multi-label one needs `rows * nc`.
 #include "kodhip_common.h"
+
+struct KodLetterbox { float left, top, scale_x, scale_y, width, height; };      // include/kodhip.h
+static_assert(sizeof(KodLetterbox) == 24, "KodLetterbox is six floats");
 
 namespace {
 
@@ -98,6 +107,74 @@ __global__ __launch_bounds__(1024) void nms_candidates_kernel(NmsArgs a) {
           if (pos < a.kcap)
             K[pos] = ((unsigned long long)sortable_desc(s) << 32) | (unsigned int)(row * a.nc + c);
           ++pos;
+        }
+      }
+    }
+    __syncthreads();
+    if (tid == 0) base_s += total;
+    __syncthreads();
+  }
+  if (tid == 0) a.ncand[b] = base_s < a.kcap ? base_s : a.kcap;
+}
+
+// kodhip_nms_ex's compaction: the ballot / prefix-scan shape of nms_candidates_kernel with an optional class filter
+// (`keep` [nc], null = every class) and, with BEST, an argmax over the classes in place of the class loop - at most one
+// candidate per row, so `rows` keys hold every candidate.  The filter looks at the candidate's class AFTER the argmax
+// (YOLOv5 general.py: `x = x[(x[:, 5:6] == classes).any(1)]` follows `conf, j = x[:, 5:].max(1)`).
+template <bool BEST>
+__global__ __launch_bounds__(1024) void nms_candidates_ex_kernel(NmsArgs a, const unsigned char* __restrict__ keep) {
+  __shared__ int wtot[16];
+  __shared__ int base_s;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int P = 5 + a.nc;
+  const float* D = a.det + (size_t)b * a.rows * P;
+  unsigned long long* K = a.keys + (size_t)b * a.kcap;
+  if (tid == 0) base_s = 0;
+  __syncthreads();
+  for (int r0 = 0; r0 < a.rows; r0 += 1024) {
+    const int row = r0 + tid;
+    int cnt = 0, bc = 0;
+    float obj = 0.f, best = 0.f;
+    if (row < a.rows) {
+      const float* r = D + (size_t)row * P;
+      obj = r[4];
+      if (obj > a.conf) {
+        if (BEST) {
+          best = r[5] * obj;
+          for (int c = 1; c < a.nc; ++c) {
+            const float s = r[5 + c] * obj;
+            if (s > best) { best = s; bc = c; }          // equal maxima: the lowest class index stays
+          }
+          cnt = (best > a.conf && (!keep || keep[bc])) ? 1 : 0;
+        } else {
+          for (int c = 0; c < a.nc; ++c) cnt += (r[5 + c] * obj > a.conf && (!keep || keep[c])) ? 1 : 0;
+        }
+      }
+    }
+    int incl = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      int v = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += v;
+    }
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    int before = 0;
+    for (int w = 0; w < wave; ++w) before += wtot[w];
+    int total = 0;
+    for (int w = 0; w < 16; ++w) total += wtot[w];
+    int pos = base_s + before + incl - cnt;
+    if (cnt) {
+      if (BEST) {
+        if (pos < a.kcap) K[pos] = ((unsigned long long)sortable_desc(best) << 32) | (unsigned int)(row * a.nc + bc);
+      } else {
+        const float* r = D + (size_t)row * P;
+        for (int c = 0; c < a.nc; ++c) {
+          const float s = r[5 + c] * obj;
+          if (s > a.conf && (!keep || keep[c])) {
+            if (pos < a.kcap) K[pos] = ((unsigned long long)sortable_desc(s) << 32) | (unsigned int)(row * a.nc + c);
+            ++pos;
+          }
         }
       }
     }
@@ -252,6 +329,49 @@ __global__ __launch_bounds__(64) void nms_greedy_kernel(NmsArgs a) {
   if (lane == 0) a.nout[b] = nk;
 }
 
+// the kept rows back into the source image, one thread per (image, output slot): x' = min(max((x - left) * scale_x, 0), width)
+// and the same for y; runs behind the greedy pass, which stays as it is.  Rows beyond nout[b] are not touched.
+__global__ __launch_bounds__(256) void nms_unletterbox_kernel(float* out, const int* nout, const KodLetterbox* lb, int B, int max_det) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * max_det) return;
+  const int b = i / max_det;
+  if (i - b * max_det >= nout[b]) return;
+  const KodLetterbox L = lb[b];
+  float* o = out + (size_t)i * 6;
+  o[0] = fminf(fmaxf((o[0] - L.left) * L.scale_x, 0.f), L.width);
+  o[1] = fminf(fmaxf((o[1] - L.top) * L.scale_y, 0.f), L.height);
+  o[2] = fminf(fmaxf((o[2] - L.left) * L.scale_x, 0.f), L.width);
+  o[3] = fminf(fmaxf((o[3] - L.top) * L.scale_y, 0.f), L.height);
+}
+
+// the launches of kodhip_nms / kodhip_nms_ex (arguments already checked).  best_class = 0 and keep = null: the candidate
+// kernel of kodhip_nms; lb = null: nothing behind the greedy pass.
+int nms_launch(const NmsArgs& a, int best_class, const unsigned char* keep, const KodLetterbox* lb, hipStream_t stream) {
+  const int B = a.B, key_cap = a.kcap;
+  if (best_class)
+    hipLaunchKernelGGL(nms_candidates_ex_kernel<true>, dim3(B), dim3(1024), 0, stream, a, keep);
+  else if (keep)
+    hipLaunchKernelGGL(nms_candidates_ex_kernel<false>, dim3(B), dim3(1024), 0, stream, a, keep);
+  else
+    hipLaunchKernelGGL(nms_candidates_kernel, dim3(B), dim3(1024), 0, stream, a);
+  KOD_LAUNCH_CHECK("nms_candidates");
+  const int chunks = key_cap > SORT_CHUNK ? key_cap / SORT_CHUNK : 1;
+  hipLaunchKernelGGL(nms_sort_local_kernel, dim3(chunks, B), dim3(512), 0, stream, a);
+  for (int k = 2 * SORT_CHUNK; k <= key_cap; k <<= 1) {
+    for (int j = k >> 1; j >= SORT_CHUNK; j >>= 1)
+      hipLaunchKernelGGL(nms_sort_global_kernel, dim3(cdiv(key_cap / 2, 256), B), dim3(256), 0, stream, a, k, j);
+    hipLaunchKernelGGL(nms_sort_merge_kernel, dim3(chunks, B), dim3(512), 0, stream, a, k);
+  }
+  KOD_LAUNCH_CHECK("nms_sort");
+  hipLaunchKernelGGL(nms_greedy_kernel, dim3(B), dim3(64), 0, stream, a);
+  KOD_LAUNCH_CHECK("nms_greedy");
+  if (lb) {
+    hipLaunchKernelGGL(nms_unletterbox_kernel, dim3(cdiv((long)B * a.max_det, 256)), dim3(256), 0, stream, a.out, a.nout, lb, B, a.max_det);
+    KOD_LAUNCH_CHECK("nms_unletterbox");
+  }
+  return KOD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -289,19 +409,29 @@ int kodhip_nms(const float* det, void* keys, int key_cap, int* ncand, float* out
   a.det = det; a.keys = (unsigned long long*)keys; a.ncand = ncand; a.out = out; a.nout = nout;
   a.B = B; a.rows = rows; a.nc = nc; a.kcap = key_cap; a.max_det = max_det; a.max_nms = max_nms;
   a.conf = conf_thres; a.iou_thr = nms_thres; a.max_wh = max_wh;
-  hipLaunchKernelGGL(nms_candidates_kernel, dim3(B), dim3(1024), 0, stream, a);
-  KOD_LAUNCH_CHECK("nms_candidates");
-  const int chunks = key_cap > SORT_CHUNK ? key_cap / SORT_CHUNK : 1;
-  hipLaunchKernelGGL(nms_sort_local_kernel, dim3(chunks, B), dim3(512), 0, stream, a);
-  for (int k = 2 * SORT_CHUNK; k <= key_cap; k <<= 1) {
-    for (int j = k >> 1; j >= SORT_CHUNK; j >>= 1)
-      hipLaunchKernelGGL(nms_sort_global_kernel, dim3(cdiv(key_cap / 2, 256), B), dim3(256), 0, stream, a, k, j);
-    hipLaunchKernelGGL(nms_sort_merge_kernel, dim3(chunks, B), dim3(512), 0, stream, a, k);
-  }
-  KOD_LAUNCH_CHECK("nms_sort");
-  hipLaunchKernelGGL(nms_greedy_kernel, dim3(B), dim3(64), 0, stream, a);
-  KOD_LAUNCH_CHECK("nms_greedy");
-  return KOD_OK;
+  return nms_launch(a, 0, nullptr, nullptr, stream);
+}
+
+
+int kodhip_letterbox_bytes(void) { return (int)sizeof(KodLetterbox); }
+
+// kodhip_nms with the deployment options.  best_class: one candidate per row (key_cap >= rows holds them all);
+// class_keep [nc] u8: candidates of a class with 0 are dropped (best_class: after the argmax); letterbox [B]: the rows
+// written to `out` are mapped back and clipped.  best_class = 0 with both pointers null is kodhip_nms launch for launch.
+// Class-agnostic suppression is max_wh = 0.
+int kodhip_nms_ex(const float* det, void* keys, int key_cap, int* ncand, float* out, int* nout,
+                  int B, int rows, int nc, float conf_thres, float nms_thres, int max_det, int max_nms, float max_wh,
+                  int best_class, const unsigned char* class_keep, const KodLetterbox* letterbox, hipStream_t stream) {
+  KOD_CHECK_ARG(det && keys && ncand && out && nout && B > 0 && rows > 0 && nc > 0, "nms_ex: bad args");
+  KOD_CHECK_ARG(key_cap >= 64 && (key_cap & (key_cap - 1)) == 0, "nms_ex: key_cap must be a power of two >= 64");
+  KOD_CHECK_ARG(max_det > 0 && max_det <= 300 && max_nms > 0, "nms_ex: max_det must be in 1..300");
+  KOD_CHECK_ARG(best_class == 0 || best_class == 1, "nms_ex: best_class must be 0 or 1");
+  KOD_CHECK_ARG((long)rows * nc < (1l << 31), "nms_ex: too many candidates");
+  NmsArgs a = {};
+  a.det = det; a.keys = (unsigned long long*)keys; a.ncand = ncand; a.out = out; a.nout = nout;
+  a.B = B; a.rows = rows; a.nc = nc; a.kcap = key_cap; a.max_det = max_det; a.max_nms = max_nms;
+  a.conf = conf_thres; a.iou_thr = nms_thres; a.max_wh = max_wh;
+  return nms_launch(a, best_class, class_keep, letterbox, stream);
 }
 
 }  // extern "C"

@@ -1,0 +1,120 @@
+"""Detector - "what is in this image?" for a trained network: images of any sizes in, boxes in each image's own pixel
+coordinates out.
+
+Every stage runs on the device and is the one validation uses, so the network sees what it was trained and validated on:
+letterbox (`letterbox_geometry` + kodhip_val_prep_batch, csrc/val_prep.hip), the eval forward (eager, fused or replayed as
+a hipGraph), the prediction decode (kodhip_decode) and the NMS in YOLOv5's detect.py form (kodhip_nms_ex: one label per box
+by default, optional class filter / class-agnostic suppression / smaller max_det), whose last launch maps the kept boxes
+from the letterboxed frame back into the source image.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from .core.nms import non_max_suppression
+from .core.types import FeatureShape
+from .data.device_pipeline import VAL_DESC, ImagePool, _Stager, letterbox_geometry
+
+
+def letterbox_table(shapes: Sequence[Sequence[int]], image_size: int, first_index: int = 0):
+    """(h, w) per image -> (VAL_DESC records without pool offsets, KodLetterbox rows float32 [n, 6]): the geometry of the
+    validation letterbox and its inverse - left, top, fp32(w / nw), fp32(h / nh), w, h, the quotients formed in double."""
+    descs = np.zeros(len(shapes), dtype=VAL_DESC)
+    boxes = np.zeros((len(shapes), 6), dtype=np.float32)
+    for k, (h, w) in enumerate(shapes):
+        h, w = int(h), int(w)
+        if h < 1 or w < 1:
+            raise ValueError(f"image {first_index + k}: empty ({h} x {w})")
+        nh, nw, top, left = letterbox_geometry(h, w, image_size)
+        if nh < 1 or nw < 1:
+            raise ValueError(f"image {first_index + k}: {h} x {w} letterboxes to {nh} x {nw} at image_size {image_size}")
+        d = descs[k]
+        d["h"], d["w"], d["nh"], d["nw"], d["top"], d["left"] = h, w, nh, nw, top, left
+        d["scale_x"], d["scale_y"] = 1.0 / (nw / float(w)), 1.0 / (nh / float(h))     # (as DeviceValPipeline.make_batch)
+        boxes[k] = (left, top, np.float32(w / float(nw)), np.float32(h / float(nh)), w, h)
+    return descs, boxes
+
+
+class Detector:
+    """det = Detector(net, anchor_info, image_size=640, ...); results = det(images)
+
+    images: a sequence of HWC uint8 arrays (3 channels) of any sizes.  results: one [n, 6] tensor per image, (x1, y1, x2, y2,
+    score, class) in that image's own pixels, n <= max_det, best score first.  conf_thres / iou_thres / classes / agnostic
+    / multi_label / max_det are detect.py's arguments (non_max_suppression's keywords).  graphed=True replays the eval
+    forward + decode as a hipGraph (GraphedEvalForward); eval_fused is handed to `net.fuse_eval` (None: left alone).
+    Images are processed in chunks of `batch_size`; a final partial chunk is padded by repeating its last image, so one
+    engine shape set serves every call."""
+
+    def __init__(self, net, anchor_info, image_size: int = 640, batch_size: int = 16, conf_thres: float = 0.25,
+                 iou_thres: float = 0.45, classes=None, agnostic: bool = False, multi_label: bool = False, max_det: int = 300,
+                 graphed: bool = False, eval_fused: Optional[bool] = None):
+        _lib.require_gpu()
+        if int(image_size) < 32 or int(image_size) % 32:
+            raise ValueError(f"image_size {image_size}: expected a multiple of 32 (the network's largest stride)")
+        if int(batch_size) < 1:
+            raise ValueError(f"batch_size {batch_size}: expected >= 1")
+        if not 1 <= int(max_det) <= 300:
+            raise ValueError(f"max_det {max_det}: expected 1..300")
+        assert _lib.lib().kodhip_val_prep_desc_bytes() == VAL_DESC.itemsize
+        assert _lib.lib().kodhip_letterbox_bytes() == 6 * 4
+        self.net, self.anchor_info = net, anchor_info
+        self.S, self.B = int(image_size), int(batch_size)
+        self.conf_thres, self.iou_thres, self.classes = conf_thres, iou_thres, classes
+        self.agnostic, self.multi_label, self.max_det = bool(agnostic), bool(multi_label), int(max_det)
+        self.graphed, self.eval_fused = bool(graphed), eval_fused
+        self.device = next(net.parameters()).device
+        self._stager = _Stager(self.device)
+        self._geval = {}              # input shape -> GraphedEvalForward
+
+    def _forward(self, x: torch.Tensor) -> torch.Tensor:
+        """decoded detections [B, rows, 5 + nc] of a letterboxed batch"""
+        if self.graphed:
+            from .engine.graphed import GraphedEvalForward
+            key = tuple(x.shape)
+            if key not in self._geval:
+                self._geval[key] = GraphedEvalForward(self.net, self.anchor_info, key[0], key[2], key[3])
+            return self._geval[key](x)
+        from .lightning.experiments.yv5_baseline.layers import get_detections
+        # every submodule's own mode is restored afterwards, as validation_step does
+        modes = [(m, m.training) for m in self.net.modules()]
+        self.net.eval()
+        try:
+            res = self.net(x)
+        finally:
+            for m, was in modes:
+                m.training = was
+        return get_detections(FeatureShape(width=x.shape[3], height=x.shape[2]), res, self.anchor_info)
+
+    @torch.no_grad()
+    def __call__(self, images: Sequence[np.ndarray]) -> List[torch.Tensor]:
+        images = list(images)
+        for i, im in enumerate(images):
+            if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
+                raise ValueError(f"image {i}: expected an HWC uint8 array with 3 channels")
+        # (all geometry first: a bad image raises before anything is uploaded or launched)
+        tables = [letterbox_table([im.shape[:2] for im in images[i:i + self.B]], self.S, i) for i in range(0, len(images), self.B)]
+        if self.eval_fused is not None:
+            self.net.fuse_eval(self.eval_fused)
+        B, S = self.B, self.S
+        results = []
+        for c, (descs, boxes) in enumerate(tables):
+            chunk = images[c * B:(c + 1) * B]
+            n = len(chunk)
+            pool = ImagePool(chunk, self.device)
+            descs["off"] = pool.offsets
+            if n < B:              # pad with the last descriptor: the batch keeps its shape, the copies are dropped below
+                descs = np.concatenate((descs, np.repeat(descs[-1:], B - n)))
+                boxes = np.concatenate((boxes, np.repeat(boxes[-1:], B - n, axis=0)))
+            d_dev = self._stager.upload(descs)
+            x = torch.empty((B, 3, S, S), dtype=torch.float32, device=self.device)
+            _lib.check(_lib.lib().kodhip_val_prep_batch(pool.data.data_ptr(), d_dev.data_ptr(), x.data_ptr(), None, B, S,
+                                                        torch.cuda.current_stream().cuda_stream), "val_prep_batch")
+            det = self._forward(x)
+            out = non_max_suppression(det, self.conf_thres, self.iou_thres, self.classes, agnostic=self.agnostic,
+                                      multi_label=self.multi_label, max_det=self.max_det, letterbox=boxes)
+            results.extend(out[:n])
+        return results
