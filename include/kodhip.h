@@ -396,6 +396,35 @@ int kodhip_nms(const float* det, void* keys, int key_cap, int* ncand, float* out
                int B, int rows, int nc, float conf_thres, float nms_thres, int max_det, int max_nms, float max_wh,
                kodStream_t stream);
 
+/* ---- test-time augmentation (YOLOv5 models/yolo.py::_forward_augment, utils/torch_utils.py::scale_img): the batch also
+ *      goes through the network flipped left-right at 0.83 of its size and unflipped at 0.67; the three sets of
+ *      predictions are brought back into the full-size frame, trimmed (_clip_augmented) and concatenated for ONE NMS.
+ *
+ * kodhip_tta_view: one view of a batch that is already on the device.  x [B][3][H][W] fp32 is flipped left-right first
+ * (flip_lr), resized to h x w (bilinear, align_corners = False; down-scaling only) and placed top-left in an Hp x Wp
+ * canvas filled with `pad` (YOLOv5: 0.447).  out_pairs: bf16 [B][Hp][Wp/2][8], the network's input layout (what
+ * kodhip_nchw_to_nhwc4 produces, the same fp32 -> bf16 rounding); out_f32 [B][3][Hp][Wp] or NULL: the same fp32 values.
+ * The arithmetic, fp32, every operation rounded on its own (no FMA), per axis with n_in source and n_out view samples:
+ *     scale = fp32(n_in) / fp32(n_out)
+ *     src   = max(fp32(fp32(dst + 0.5f) * scale) - 0.5f, 0)
+ *     i0 = (int)src, i1 = i0 + (i0 < n_in - 1), l1 = src - i0, l0 = 1 - l1
+ *     out   = hy0 * (wx0 * a + wx1 * b) + hy1 * (wx0 * c + wx1 * d)       a, b on row y0; c, d on row y1
+ * (products rounded, then the inner sums, then the outer products, then the outer sum).  h = H and w = W give l1 = 0
+ * everywhere: the (flipped) pixels themselves.  Refused before any launch: a null x or out_pairs, h > H, w > W, Hp < h,
+ * Wp < w, odd Wp.
+ *
+ * kodhip_decode_view: kodhip_decode for one view of the merged [B][rows_total][5+nc] tensor.  `levels` describe the
+ * view's own head tensors; bit l of level_mask says whether level l takes part (the first view drops its last level, the
+ * last view its first).  The view's rows go to [row_offset, row_offset + own rows) of every image, nothing else is
+ * written.  Per row: cx, cy, w, h as in kodhip_decode at the view's strides, each divided by `scale` (IEEE fp32
+ * division), cx = full_width - cx when flip_lr, then the corners cx -+ 0.5f * w, cy -+ 0.5f * h; objectness and class
+ * scores untouched.  scale = 1, flip_lr = 0, level_mask = 7, row_offset = 0, rows_total = own rows is kodhip_decode bit
+ * for bit. */
+int kodhip_tta_view(const float* x, void* out_pairs, float* out_f32 /* or NULL */, int B, int H, int W, int h, int w,
+                    int Hp, int Wp, int flip_lr, float pad, kodStream_t stream);
+int kodhip_decode_view(const KodDecodeLevel* levels /* host[3] */, float* det, int B, int A, int nc, float scale,
+                       int flip_lr, float full_width, int level_mask, int row_offset, int rows_total, kodStream_t stream);
+
 /* kodhip_nms with the deployment options of YOLOv5's detect.py.  With best_class = 0, class_keep = NULL and
  * letterbox = NULL it is kodhip_nms: the same launches, the same bits.
  *   best_class = 1  (multi_label=False) one candidate per row: score = max over c of fp32(cls_c * obj), the LOWEST class

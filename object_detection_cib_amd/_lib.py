@@ -126,6 +126,8 @@ SIGNATURES = {
     "kodhip_val_prep_batch": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "kodhip_decode": (i32, [C.POINTER(KodDecodeLevel), vp, i32, i32, i32, vp]),
     "kodhip_nms": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, f32, vp]),
+    "kodhip_tta_view": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]),
+    "kodhip_decode_view": (i32, [C.POINTER(KodDecodeLevel), vp, i32, i32, i32, f32, i32, f32, i32, i32, i32, vp]),
     "kodhip_letterbox_bytes": (i32, []),
     "kodhip_nms_ex": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, f32, i32, vp, vp, vp]),
     "kodhip_map_match": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(f64), i32, i32, vp]),

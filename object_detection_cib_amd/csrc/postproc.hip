@@ -15,6 +15,9 @@
 //            and the kept rows mapped from the letterboxed frame back to the source image (subtract the pad, multiply by
 //            the inverse scale, clip - each operation rounded on its own).  Same keys, same sort, same greedy pass: the
 //            best-class form needs `rows` keys per image where the multi-label one needs `rows * nc`.
+//   decode_view : kodhip_decode for one view of test-time augmentation (YOLOv5 models/yolo.py::_forward_augment): the same
+//            per-row arithmetic (one __device__ function, decode_row), then cx, cy, w, h divided by the view's scale, cx
+//            mirrored about the full width for a flipped view, written to the view's own rows of the merged tensor.
 #include "kodhip_common.h"
 
 struct KodLetterbox { float left, top, scale_x, scale_y, width, height; };      // include/kodhip.h
@@ -25,11 +28,16 @@ namespace {
 struct DecodeLevel { const float* raw; int h, w, stride, row0; float aw[3], ah[3]; };
 struct DecodeArgs { DecodeLevel lv[3]; float* det; int B, A, nc, rows; };
 
-__global__ void decode_kernel(DecodeArgs a) {
+// What kodhip_decode_view adds to a row (test-time augmentation: the row belongs to one view of a merged tensor): the box
+// back in the full-size frame - cx, cy, w, h each divided by `scale` (IEEE fp32 division, YOLOv5's `p[..., :4] /= scale`),
+// then cx = full_w - cx for a left-right flipped view.
+struct DecodeView { float scale, full_w; int flip, row_offset, rows_total; };
+
+// One decoded row, shared by kodhip_decode and kodhip_decode_view: `row` counts the rows of the levels in `a` (level,
+// anchor, y, x), `o` is where its 5 + nc values go.  VIEW = false never looks at `v`.
+template <bool VIEW>
+__device__ __forceinline__ void decode_row(const DecodeArgs& a, int b, int row, float* o, const DecodeView& v) {
   const int P = 5 + a.nc;
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;      // one thread per (b, row)
-  if (i >= (long)a.B * a.rows) return;
-  int b = (int)(i / a.rows), row = (int)(i - (long)b * a.rows);
   int l = row >= a.lv[2].row0 ? 2 : (row >= a.lv[1].row0 ? 1 : 0);
   const DecodeLevel& L = a.lv[l];
   int r = row - L.row0;
@@ -37,14 +45,34 @@ __global__ void decode_kernel(DecodeArgs a) {
   int an = r / hw, cell = r - an * hw;
   int gy = cell / L.w, gx = cell - gy * L.w;
   const float* p = L.raw + ((size_t)(b * a.A + an) * hw + cell) * P;
-  float* o = a.det + (size_t)i * P;
   float sx = 1.f / (1.f + expf(-p[0])), sy = 1.f / (1.f + expf(-p[1]));
   float sw = 1.f / (1.f + expf(-p[2])), sh = 1.f / (1.f + expf(-p[3]));
   float cx = (sx * 2.f + (float)gx - 0.5f) * (float)L.stride;
   float cy = (sy * 2.f + (float)gy - 0.5f) * (float)L.stride;
   float w = (sw * 2.f) * (sw * 2.f) * L.aw[an], h = (sh * 2.f) * (sh * 2.f) * L.ah[an];
+  if (VIEW) {
+    cx = __fdiv_rn(cx, v.scale); cy = __fdiv_rn(cy, v.scale); w = __fdiv_rn(w, v.scale); h = __fdiv_rn(h, v.scale);
+    if (v.flip) cx = v.full_w - cx;
+  }
   o[0] = cx - 0.5f * w; o[1] = cy - 0.5f * h; o[2] = cx + 0.5f * w; o[3] = cy + 0.5f * h;
   for (int k = 4; k < P; ++k) o[k] = 1.f / (1.f + expf(-p[k]));
+}
+
+__global__ void decode_kernel(DecodeArgs a) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;      // one thread per (b, row)
+  if (i >= (long)a.B * a.rows) return;
+  int b = (int)(i / a.rows), row = (int)(i - (long)b * a.rows);
+  decode_row<false>(a, b, row, a.det + (size_t)i * (5 + a.nc), DecodeView{});
+}
+
+// the rows of one view: a.lv holds the view's levels, a masked-out level with no rows (its row0 is the next level's, so
+// no row selects it); a.rows = the view's own rows, written at [row_offset, row_offset + a.rows) of each image's
+// rows_total rows.  Nothing else is written.
+__global__ void decode_view_kernel(DecodeArgs a, DecodeView v) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;      // one thread per (b, own row)
+  if (i >= (long)a.B * a.rows) return;
+  int b = (int)(i / a.rows), row = (int)(i - (long)b * a.rows);
+  decode_row<true>(a, b, row, a.det + ((size_t)b * v.rows_total + v.row_offset + row) * (5 + a.nc), v);
 }
 
 // ------------------------------------------------------------------------------------------------ NMS
@@ -393,6 +421,35 @@ int kodhip_decode(const KodDecodeLevel* levels /* host[3] */, float* det, int B,
   a.det = det; a.B = B; a.A = A; a.nc = nc; a.rows = row0;
   hipLaunchKernelGGL(decode_kernel, dim3(cdiv((long)B * row0, 256)), dim3(256), 0, stream, a);
   KOD_LAUNCH_CHECK("decode");
+  return KOD_OK;
+}
+
+// kodhip_decode for one view of a merged [B][rows_total][5+nc] tensor (test-time augmentation).  `levels` are the view's
+// own three head tensors (h, w, stride of the VIEW's shape); level l takes part when bit l of level_mask is set (a
+// masked-out level may have a null `raw`).  The view's rows - the unmasked levels in level order - go to
+// [row_offset, row_offset + own rows) of every image; the box is brought back into the full-size frame first:
+// cx, cy, w, h each divided by `scale`, then cx = full_width - cx when flip_lr, then the corners as in kodhip_decode.
+// scale = 1, flip_lr = 0, level_mask = 7, row_offset = 0, rows_total = own rows: kodhip_decode bit for bit.
+int kodhip_decode_view(const KodDecodeLevel* levels /* host[3] */, float* det, int B, int A, int nc, float scale, int flip_lr,
+                       float full_width, int level_mask, int row_offset, int rows_total, hipStream_t stream) {
+  KOD_CHECK_ARG(levels && det && B > 0 && A == 3 && nc > 0, "decode_view: bad args (3 anchors per cell)");
+  KOD_CHECK_ARG(level_mask > 0 && level_mask < 8, "decode_view: level_mask must select at least one of the three levels");
+  KOD_CHECK_ARG(scale > 0.f && (flip_lr == 0 || flip_lr == 1), "decode_view: scale must be positive, flip_lr 0 or 1");
+  DecodeArgs a = {};
+  int row0 = 0;
+  for (int l = 0; l < 3; ++l) {
+    const bool on = (level_mask >> l) & 1;
+    KOD_CHECK_ARG(!on || (levels[l].raw && levels[l].h > 0 && levels[l].w > 0), "decode_view: null or empty level");
+    a.lv[l].raw = levels[l].raw; a.lv[l].h = levels[l].h; a.lv[l].w = levels[l].w; a.lv[l].stride = levels[l].stride;
+    a.lv[l].row0 = row0;
+    for (int k = 0; k < 3; ++k) { a.lv[l].aw[k] = levels[l].anchor_w[k]; a.lv[l].ah[k] = levels[l].anchor_h[k]; }
+    if (on) row0 += A * levels[l].h * levels[l].w;
+  }
+  KOD_CHECK_ARG(row_offset >= 0 && (long)row_offset + row0 <= rows_total, "decode_view: the view's rows do not fit in rows_total");
+  a.det = det; a.B = B; a.A = A; a.nc = nc; a.rows = row0;
+  DecodeView v = {scale, full_width, flip_lr, row_offset, rows_total};
+  hipLaunchKernelGGL(decode_view_kernel, dim3(cdiv((long)B * row0, 256)), dim3(256), 0, stream, a, v);
+  KOD_LAUNCH_CHECK("decode_view");
   return KOD_OK;
 }
 

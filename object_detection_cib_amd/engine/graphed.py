@@ -230,30 +230,26 @@ class GraphedTrainStep:
         return self.total, self.parts
 
 
-class GraphedEvalForward:
-    """Eval-mode forward + prediction decode captured once per input shape and replayed (validation loop).
-
-    Issued one launch at a time from Python the eval forward is host-bound like the training step (~230 launches,
-    ~15 ms of ctypes / Python per batch against ~7 ms of GPU time); replaying a hipGraph leaves the host only the copy
-    of the batch into the static input buffer.  Weight packs and the eval-mode BatchNorm constants are refreshed
-    eagerly before a replay when parameters / running statistics moved (both live in buffers with fixed addresses), so
-    the same graph serves every validation epoch."""
+class _GraphedEval:
+    """What the captured eval forwards share: the static fp32 input batch, the eager refresh of weight packs and eval-mode
+    BatchNorm constants before a replay when parameters / running statistics moved (both live in buffers with fixed
+    addresses, so the same graph serves every validation epoch), the `eval_fused` guard and the capture itself.  A
+    subclass says which engine shapes its launches touch (`_shapes`) and what is captured (`_forward`)."""
 
     def __init__(self, net, anchor_info, batch_size: int, height: int, width: int):
-        from ..lightning.experiments.yv5_baseline.layers import get_detections
-        self.net, self.anchor_info, self._decode = net, anchor_info, get_detections
+        self.net, self.anchor_info = net, anchor_info
         self.eng = net.engine()
         self.x = torch.zeros((batch_size, 3, height, width), dtype=torch.float32, device=self.eng.device)
         self.shape = FeatureShape(width=width, height=height)
         self.graph, self.det = None, None
         self._eval_fused = None           # EngineOptions.eval_fused the graph was captured with
 
+    def _shapes(self):
+        """the (B, H, W) buffer sets the graph bakes addresses of"""
+        return [(self.x.shape[0], self.x.shape[2], self.x.shape[3])]
+
     def _forward(self):
-        from ..nn.networks.yolov5 import Yolov5NetworkResult
-        from ..nn.heads.types import DetectionHeadResult
-        raws = self.eng.forward(self.x, training=False)
-        res = Yolov5NetworkResult(*[DetectionHeadResult(t[..., 0:4], t[..., 4:5], t[..., 5:]) for t in raws])
-        return self._decode(self.shape, res, self.anchor_info)
+        raise NotImplementedError
 
     def _refresh(self):
         eng = self.eng
@@ -264,7 +260,8 @@ class GraphedEvalForward:
     @torch.no_grad()
     def capture(self, images: torch.Tensor):
         eng = self.eng
-        eng.pin_shape(*[self.x.shape[0], self.x.shape[2], self.x.shape[3]])
+        for shp in self._shapes():
+            eng.pin_shape(*shp)
         self.x.copy_(images)
         side = torch.cuda.Stream(device=eng.device)
         side.wait_stream(torch.cuda.current_stream())
@@ -289,9 +286,50 @@ class GraphedEvalForward:
         if bool(self.eng.opt.eval_fused) != self._eval_fused:
             # the graph replays the launches of the form it was captured with (one fused launch per unit, or conv + apply)
             raise RuntimeError("EngineOptions.eval_fused changed after capture(): the captured forward holds the old launches; "
-                               "build a new GraphedEvalForward and capture() again")
+                               f"build a new {type(self).__name__} and capture() again")
         self._refresh()
         self.x.copy_(images, non_blocking=True)
-        # a replay needs this shape's buffer set to be what the graph captured - it is pinned, nothing to swap
+        # a replay needs its shapes' buffer sets to be what the graph captured - they are pinned, nothing to swap
         self.graph.replay()
         return self.det
+
+
+class GraphedEvalForward(_GraphedEval):
+    """Eval-mode forward + prediction decode captured once per input shape and replayed (validation loop).
+
+    Issued one launch at a time from Python the eval forward is host-bound like the training step (~230 launches,
+    ~15 ms of ctypes / Python per batch against ~7 ms of GPU time); replaying a hipGraph leaves the host only the copy
+    of the batch into the static input buffer.  Weight packs and the eval-mode BatchNorm constants are refreshed
+    eagerly before a replay when parameters / running statistics moved (both live in buffers with fixed addresses), so
+    the same graph serves every validation epoch."""
+
+    def __init__(self, net, anchor_info, batch_size: int, height: int, width: int):
+        from ..lightning.experiments.yv5_baseline.layers import get_detections
+        super().__init__(net, anchor_info, batch_size, height, width)
+        self._decode = get_detections
+
+    def _forward(self):
+        from ..nn.networks.yolov5 import Yolov5NetworkResult
+        from ..nn.heads.types import DetectionHeadResult
+        raws = self.eng.forward(self.x, training=False)
+        res = Yolov5NetworkResult(*[DetectionHeadResult(t[..., 0:4], t[..., 4:5], t[..., 5:]) for t in raws])
+        return self._decode(self.shape, res, self.anchor_info)
+
+
+class GraphedAugmentedForward(_GraphedEval):
+    """The test-time-augmented eval forward (layers.get_detections_augmented: three views, three forwards, one merged
+    decoded tensor) captured as ONE hipGraph and replayed.  All launches of the three views sit on one stream in one
+    linear chain - view, forward, decode, next view: the eval forward uses no side stream, so the graph has no parallel
+    branch - and the buffer sets of all the views' shapes are pinned, as the graph bakes their addresses in."""
+
+    def __init__(self, net, anchor_info, batch_size: int, height: int, width: int):
+        from ..lightning.experiments.yv5_baseline.layers import get_detections_augmented
+        from .tta import tta_plan
+        super().__init__(net, anchor_info, batch_size, height, width)
+        self._augmented, self.plan = get_detections_augmented, tta_plan(height, width)
+
+    def _shapes(self):
+        return [(self.x.shape[0], hp, wp) for hp, wp in self.plan.shapes()]
+
+    def _forward(self):
+        return self._augmented(self.x, self.net, self.anchor_info)

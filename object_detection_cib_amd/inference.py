@@ -5,7 +5,9 @@ Every stage runs on the device and is the one validation uses, so the network se
 letterbox (`letterbox_geometry` + kodhip_val_prep_batch, csrc/val_prep.hip), the eval forward (eager, fused or replayed as
 a hipGraph), the prediction decode (kodhip_decode) and the NMS in YOLOv5's detect.py form (kodhip_nms_ex: one label per box
 by default, optional class filter / class-agnostic suppression / smaller max_det), whose last launch maps the kept boxes
-from the letterboxed frame back into the source image.
+from the letterboxed frame back into the source image.  `AugmentedDetector` is detect.py's `--augment`: the letterboxed batch
+goes through the network three times (as is, flipped at 0.83 of its size, at 0.67: kodhip_tta_view / kodhip_decode_view) and
+ONE NMS runs over the merged predictions.
 """
 from __future__ import annotations
 
@@ -47,7 +49,11 @@ class Detector:
     / multi_label / max_det are detect.py's arguments (non_max_suppression's keywords).  graphed=True replays the eval
     forward + decode as a hipGraph (GraphedEvalForward); eval_fused is handed to `net.fuse_eval` (None: left alone).
     Images are processed in chunks of `batch_size`; a final partial chunk is padded by repeating its last image, so one
-    engine shape set serves every call."""
+    engine shape set serves every call.
+
+    `augment` (class attribute, False here; True in AugmentedDetector) routes the forward through test-time augmentation."""
+
+    augment = False
 
     def __init__(self, net, anchor_info, image_size: int = 640, batch_size: int = 16, conf_thres: float = 0.25,
                  iou_thres: float = 0.45, classes=None, agnostic: bool = False, multi_label: bool = False, max_det: int = 300,
@@ -68,17 +74,20 @@ class Detector:
         self.graphed, self.eval_fused = bool(graphed), eval_fused
         self.device = next(net.parameters()).device
         self._stager = _Stager(self.device)
-        self._geval = {}              # input shape -> GraphedEvalForward
+        self._geval = {}              # input shape -> GraphedEvalForward (augment: GraphedAugmentedForward)
 
     def _forward(self, x: torch.Tensor) -> torch.Tensor:
         """decoded detections [B, rows, 5 + nc] of a letterboxed batch"""
         if self.graphed:
-            from .engine.graphed import GraphedEvalForward
+            from .engine.graphed import GraphedAugmentedForward, GraphedEvalForward
             key = tuple(x.shape)
             if key not in self._geval:
-                self._geval[key] = GraphedEvalForward(self.net, self.anchor_info, key[0], key[2], key[3])
+                cls = GraphedAugmentedForward if self.augment else GraphedEvalForward
+                self._geval[key] = cls(self.net, self.anchor_info, key[0], key[2], key[3])
             return self._geval[key](x)
-        from .lightning.experiments.yv5_baseline.layers import get_detections
+        from .lightning.experiments.yv5_baseline.layers import get_detections, get_detections_augmented
+        if self.augment:           # (the engine's eval forward, called directly: no module mode is touched)
+            return get_detections_augmented(x, self.net, self.anchor_info)
         # every submodule's own mode is restored afterwards, as validation_step does
         modes = [(m, m.training) for m in self.net.modules()]
         self.net.eval()
@@ -118,3 +127,16 @@ class Detector:
                                       multi_label=self.multi_label, max_det=self.max_det, letterbox=boxes)
             results.extend(out[:n])
         return results
+
+
+class AugmentedDetector(Detector):
+    """Detector with test-time augmentation (YOLOv5 detect.py `--augment`): same constructor, same call, same results format.
+
+    The forward becomes `get_detections_augmented` - three views of the letterboxed batch, up to three engine shape sets -
+    eager, or one hipGraph over all three views with graphed=True (GraphedAugmentedForward).  Everything after the forward is
+    unchanged: the NMS options, the un-letterbox launch and the chunk padding apply to the merged tensor, which lives in the
+    letterboxed full-size frame.  It has about 1.8 times the rows of one forward (45147 against 25200 at 640 px), so with
+    multi_label=True the NMS key workspace roughly doubles: 45147 * 80 keys need a 4 Mi-key capacity per image at nc = 80,
+    against 2 Mi without augmentation."""
+
+    augment = True

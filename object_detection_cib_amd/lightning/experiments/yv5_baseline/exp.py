@@ -20,7 +20,7 @@ from ....core.label_assignment.yv5 import BatchedTargets
 from ....nn.optim.smart import SmartOptimizer, FusedSGD, CLIP_ALGORITHMS
 from ....nn.optim.schedulers import LinearScheduler
 from ...callbacks.map_eval import DeviceMAPEvaluator
-from .layers import get_detections
+from .layers import get_detections, get_detections_augmented
 from .type_defs import LayerwiseAnchorInfo
 from .warmup import OptimizerWarmupUpdater
 
@@ -45,7 +45,10 @@ class DefaultYolov5Experiment:
     """Constructor = the reference's (exp.py:37-58: net, loss, anchor_info, smart_optimizer, lr_scheduler,
     optimizer_warmup_updater, val_nms_conf_threshold, val_nms_iou_threshold); the keyword-only extras stand in for
     what Lightning's Trainer supplies (`trainer.max_epochs`) or are build-side switches.  smart_optimizer /
-    lr_scheduler default to the reference's configs (configs/nn/optimizers/smart_sgd.yaml, schedulers/linear.yaml)."""
+    lr_scheduler default to the reference's configs (configs/nn/optimizers/smart_sgd.yaml, schedulers/linear.yaml).
+    val_augment=True: validation_step runs YOLOv5's test-time augmentation (val.py --augment) - three views of the batch, one
+    NMS over the merged predictions.  The merged tensor has 45147 rows at 640 px against 25200, so the NMS key workspace
+    roughly doubles: at nc = 80, 45147 * 80 keys need a 4 Mi-key capacity per image, against 2 Mi without it."""
 
     def __init__(self, net, loss, anchor_info: LayerwiseAnchorInfo, smart_optimizer: Optional[SmartOptimizer] = None,
                  lr_scheduler: Optional[Callable] = None,
@@ -54,7 +57,7 @@ class DefaultYolov5Experiment:
                  graphed: bool = False, max_targets: int = 4096, world_size: int = 1,
                  gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
                  eval_fused: Optional[bool] = None, val_confusion: bool = False, val_confusion_conf: float = 0.25,
-                 val_confusion_iou: float = 0.45):
+                 val_confusion_iou: float = 0.45, val_augment: bool = False):
         if gradient_clip_algorithm not in CLIP_ALGORITHMS:
             raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected one of {CLIP_ALGORITHMS}")
         # Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm): handed to the FusedSGD / the captured step
@@ -91,6 +94,9 @@ class DefaultYolov5Experiment:
         # the validation group, whatever val_sync says.
         self.val_confusion, self.val_confusion_conf, self.val_confusion_iou = val_confusion, val_confusion_conf, val_confusion_iou
         self.confusion = None
+        # val_augment: the forward of validation_step becomes layers.get_detections_augmented (graphed: GraphedAugmentedForward, one
+        # hipGraph over all three views); validate(), the mAP evaluator and val_confusion receive the NMS output as without it
+        self.val_augment = bool(val_augment)
 
     # exp.py:156-162
     def configure_optimizers(self):
@@ -138,11 +144,16 @@ class DefaultYolov5Experiment:
     def validation_step(self, batch, batch_idx: int = 0):
         images, targets, _ = batch
         if self.graphed:          # eval forward + decode replayed as one hipGraph per input shape (engine/graphed.py)
-            from ....engine.graphed import GraphedEvalForward
+            from ....engine.graphed import GraphedAugmentedForward, GraphedEvalForward
             key = tuple(images.shape)
             if key not in self._geval:
-                self._geval[key] = GraphedEvalForward(self.net, self.anchor_info, key[0], key[2], key[3])
+                cls = GraphedAugmentedForward if self.val_augment else GraphedEvalForward
+                self._geval[key] = cls(self.net, self.anchor_info, key[0], key[2], key[3])
             det = self._geval[key](images if images.dtype == torch.float32 else images.float())
+            return targets, non_max_suppression(det, self.val_nms_conf_threshold, self.val_nms_iou_threshold)
+        if self.val_augment:      # (the engine's eval forward, called directly: no module mode is touched)
+            x = (images if images.dtype == torch.float32 else images.float()).contiguous()
+            det = get_detections_augmented(x, self.net, self.anchor_info)
             return targets, non_max_suppression(det, self.val_nms_conf_threshold, self.val_nms_iou_threshold)
         # every submodule's own mode is restored afterwards (as Lightning's validation loop does): net.train(was) would
         # put a backbone the user keeps in eval mode (frozen BatchNorm) back into train mode
