@@ -145,9 +145,9 @@ class _Builder:
              kernel_sizes=5):
         """SPPFBottleneck (sppf.py:14-84): conv2(cat[x, pools...]), x = conv1(in).  kernel_sizes: an int k = the cascade
         cat[x, p(x), p(p(x)), p(p(p(x)))] of k x k pools (sppf.py:49-55,74-77); a sequence = parallel pools cat[x, p_k0(x),
-        p_k1(x), ...] (sppf.py:56-63,78-82) - run as a cascade of the first size where the sequence is one (k, 2k - 1,
-        3k - 2, ...: a stride-1 max-pool of k applied j times IS the max-pool of j (k - 1) + 1, values and gradient routing
-        alike; the SPP sequence (5, 9, 13)), else each pool reads x.  use_conv_first=False (sppf.py:37-39): no conv1, the
+        p_k1(x), ...] (sppf.py:56-63,78-82), each pool reading x - also for a sequence like the SPP windows (5, 9, 13): a
+        stride-1 max-pool of k applied j times has the VALUES of the max-pool of j (k - 1) + 1, but among tied maxima it
+        picks another pixel, so its gradient is not the reference's.  use_conv_first=False (sppf.py:37-39): no conv1, the
         module's input IS the first slice of the concat buffer (src = None: the caller takes the returned view as its input)."""
         pre = name + "." if name else ""
         name = name or "_"
@@ -309,9 +309,9 @@ def sppf_pool_plan(kernel_sizes):
     ks = [ok(int(k)) for k in kernel_sizes]
     if not ks:
         raise ValueError("SPPF needs at least one window")
-    if ks[0] > 1 and all(k == (j + 1) * (ks[0] - 1) + 1 for j, k in enumerate(ks)):
-        return [(q, ks[0]) for q in range(len(ks))]                          # parallel pools that ARE a cascade of the first
-    return [(0, k) for k in ks]                                              # parallel pools of x
+    # parallel pools of x, also where the sequence is (k, 2k - 1, 3k - 2, ...): a cascade of k x k pools has those pools'
+    # VALUES, but under ties (bf16 activations tie often) it routes the gradient to other pixels than the reference's pools
+    return [(0, k) for k in ks]
 
 
 def build_sppf_graph(cin: int, cout: int, mid_channels_scale: float = 0.5, use_conv_first: bool = True, kernel_sizes=5) -> Graph:

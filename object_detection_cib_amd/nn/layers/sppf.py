@@ -14,8 +14,8 @@ from ..graph_module import GraphModule, check_norm_act
 class SPPFBottleneck(GraphModule):
     """conv2(cat[x, pools...]), x = conv1(in) (or the input itself with use_conv_first=False); the pools write channel
     slices of the concat buffer.  kernel_sizes as in the reference (sppf.py:27-67): an int k = three cascaded k x k / stride 1
-    pools (5 is what the network uses), a sequence = parallel pools of those sizes (run as a cascade where the sequence is
-    one, e.g. the SPP windows (5, 9, 13)); any odd window up to 15.  Window 5 takes the tuned kernels
+    pools (5 is what the network uses), a sequence = parallel pools of those sizes, every one reading x (the SPP windows
+    (5, 9, 13) too: a cascade has their values but not their gradient routing under ties); any odd window up to 15.  Window 5 takes the tuned kernels
     (csrc/misc_ops.hip maxpool5_*), other windows the plain ones (maxpool_k_*)."""
 
     def __init__(self, in_channels: int, out_channels: int, kernel_sizes: int | Sequence[int] = 5, use_conv_first: bool = True,

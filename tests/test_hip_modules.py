@@ -166,8 +166,9 @@ def test_sppf_bottleneck():
 @pytest.mark.parametrize("ks,first", [(3, True), ((3, 7), True), ((7,), False), (9, True), ((3, 5, 7), True)])
 def test_sppf_other_windows(ks, first):
     """SPPFBottleneck with windows other than 5 (kod/nn/layers/sppf.py:27-67 takes any size or sequence): cascades of k x k
-    pools, parallel pools that are no cascade ((3, 7): both read x and their gradients meet in x's slice), one window
-    without the leading conv, and a sequence that IS a cascade ((3, 5, 7) = three 3 x 3 pools) - against the oracle module,
+    pools, parallel pools ((3, 7): both read x and their gradients meet in x's slice), one window without the leading
+    conv, and a sequence with a cascade's values ((3, 5, 7): run as three pools of x like any sequence, because a cascade
+    of 3 x 3 pools routes tied gradients differently, tests/test_hip_small_ops.py) - against the oracle module,
     whose forms 'k3', 'k3_7', 'k7_noconv' are pinned to the reference by tests/golden/sppf.npz."""
     cin = 128 if first else 64
     x = torch.randn(3, cin, 16, 16, generator=torch.Generator().manual_seed(21))
@@ -178,8 +179,9 @@ def test_sppf_other_windows(ks, first):
 
 @pytest.mark.parametrize("first", [True, False])
 def test_sppf_parallel_pools_and_no_leading_conv(first):
-    """SPPFBottleneck's other forms (kod/nn/layers/sppf.py:37-39,56-63,78-82): the parallel pools of sizes (5, 9, 13) - the
-    same arithmetic as the cascade the network uses - with and without the leading 1x1 conv, against the oracle module
+    """SPPFBottleneck's other forms (kod/nn/layers/sppf.py:37-39,56-63,78-82): the parallel pools of sizes (5, 9, 13) - every
+    one reading x: the cascade the network uses has the same values but not the same gradient routing under ties
+    (tests/test_hip_small_ops.py) - with and without the leading 1x1 conv, against the oracle module
     (pinned to the reference by tests/golden/sppf.npz)."""
     cin = 128 if first else 64
     x = torch.randn(3, cin, 16, 16, generator=torch.Generator().manual_seed(12))
