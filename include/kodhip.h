@@ -467,6 +467,37 @@ int kodhip_confusion_match(const float* det, const int* ndet, const double* gt_b
                            const int* gt_start, long long* matrix, int B, int max_det, int nc, float conf_thres,
                            double iou_thres, kodStream_t stream);
 
+/* ---- auto-anchor (YOLOv5 utils/autoanchor.py: check_anchors / kmean_anchors), csrc/anchors.hip.  Box sizes wh are device
+ * fp32 [N][2], positive and finite, 8-byte aligned.  Every launch uses min(ceil(N / kodhip_anchor_block_size()),
+ * kodhip_anchor_grid_cap()) blocks, grid-strided beyond: sums are ordered by N alone and repeat bit for bit.  The functions
+ * only enqueue kernels (no allocation, copy or synchronisation: capturable); `workspace` is device memory of at least
+ * kodhip_anchor_workspace_bytes(N, sets) bytes, sets = P (metric, evolve) or R (k-means step), 8-byte aligned.
+ * Limits: n <= kodhip_anchor_max_anchors(), P <= kodhip_anchor_max_population(), R <= kodhip_anchor_max_restarts(). */
+int kodhip_anchor_max_anchors(void);
+int kodhip_anchor_max_population(void);
+int kodhip_anchor_max_restarts(void);
+int kodhip_anchor_block_size(void);
+int kodhip_anchor_grid_cap(void);
+int kodhip_anchor_trace_bytes(void);                 /* one trace entry: { int winner; int accepted; double fitness_sum; } */
+long kodhip_anchor_workspace_bytes(long N, int sets);
+/* P anchor sets [P][n][2] in one launch pair.  Per box and anchor, fp32: r = wh / k, x = min(min(r_w, 1 / r_w), min(r_h, 1 / r_h)),
+ * best = max over the anchors.  fitness_sum[p] = sum of best where best > t (fp64), n_recalled[p] = boxes with best > t,
+ * n_pairs[p] = (box, anchor) pairs with x > t; t = float32(1 / thr), comparisons strict.  Outputs are device arrays [P]. */
+int kodhip_anchor_metric(const float* wh, long N, const float* anchors, int P, int n, float t, void* workspace,
+                         double* fitness_sum, long long* n_recalled, long long* n_pairs, kodStream_t stream);
+/* The whole genetic search, 2 * gen launches: in generation g candidate p is max(anchors * mutations[g][p], 2.0f) (fp32
+ * multiply, then max); the candidate with the largest fitness sum (equal sums: lower index) replaces `anchors` [n][2] and
+ * `*fitness` (device fp64, in/out) when it is strictly better; trace[g] (device) records winner, accepted, winner's sum.
+ * mutations: device fp32 [gen][P][n][2].  gen = 0 launches nothing. */
+int kodhip_anchor_evolve(const float* wh, long N, float* anchors, double* fitness, const float* mutations, int gen, int P, int n,
+                         float t, void* trace, void* workspace, kodStream_t stream);
+/* One Lloyd step of R independent restarts: points [N][2], centroids [R][n][2] in/out.  A point joins the centroid of least
+ * (x-cx)*(x-cx) + (y-cy)*(y-cy) (fp32, equal distances: lower index); new centroid = float32(fp64 sum / count), an empty
+ * cluster keeps its centroid.  distortion [R] fp64 = sum of the winning squared distances (to the OLD centroids),
+ * counts [R][n] int64, labels [R][N] int32 or NULL - all device. */
+int kodhip_anchor_kmeans_step(const float* points, long N, float* centroids, int R, int n, void* workspace, double* distortion,
+                              long long* counts, int* labels, kodStream_t stream);
+
 /* ---- data-parallel collectives (Lightning strategy=ddp + sync_batchnorm=True, kod/configs/trainer/ddp.yaml:4-9:
  *      torch DistributedDataParallel's bucketed gradient all-reduce, SyncBatchNorm's statistic exchange and the
  *      initial parameter/buffer broadcast).  RCCL enqueued on the caller's stream; hipGraph-capturable. ------ */

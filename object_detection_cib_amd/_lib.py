@@ -134,7 +134,17 @@ SIGNATURES = {
     "kodhip_confusion_max_det": (i32, []),
     "kodhip_confusion_lds_classes": (i32, []),
     "kodhip_confusion_match": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f64, vp]),
-    "kodhip_assign_targets": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, C.POINTER(KodAssignLevel), vp]),
+    "kodhip_anchor_max_anchors": (i32, []),
+    "kodhip_anchor_max_population": (i32, []),
+    "kodhip_anchor_max_restarts": (i32, []),
+    "kodhip_anchor_block_size": (i32, []),
+    "kodhip_anchor_grid_cap": (i32, []),
+    "kodhip_anchor_trace_bytes": (i32, []),
+    "kodhip_anchor_workspace_bytes": (i64, [i64, i32]),
+    "kodhip_anchor_metric": (i32, [vp, i64, vp, i32, i32, f32, vp, vp, vp, vp, vp]),
+    "kodhip_anchor_evolve": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp]),
+    "kodhip_anchor_kmeans_step": (i32, [vp, i64, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "kodhip_assign_targets":(i32, [vp, vp, vp, i32, i32, i32, i32, f32, C.POINTER(KodAssignLevel), vp]),
     "kodhip_iou_fwd": (i32, [vp, vp, vp, i64, i32, f32, vp]),
     "kodhip_iou_bwd": (i32, [vp, vp, vp, vp, vp, i64, i32, f32, vp]),
     "kodhip_yolo_loss": (i32, [C.POINTER(KodLossLevel), i32, i32, i32, i32, f32, f32, f32, vp, vp, vp, i32, vp,
