@@ -446,6 +446,42 @@ int kodhip_nms_ex(const float* det, void* keys, int key_cap, int* ncand, float* 
                   int best_class, const unsigned char* class_keep /* [nc] or NULL */,
                   const KodLetterbox* letterbox /* [B] or NULL */, kodStream_t stream);
 
+/* ---- tiled (sliced) inference: an image larger than the network's input is cut into overlapping S x S tiles at its
+ *      native resolution, the tiles (and one letterboxed view of the whole image) go through the network and
+ *      kodhip_nms_ex, whose KodLetterbox rows (tile at (x0, y0): left = -x0, top = -y0, scale 1, the image's width and
+ *      height) put the kept rows into image pixels, and ONE merge per image joins what the views found.
+ *
+ * kodhip_tile_batch: descs is a device array [T] of { long off; int h, w, x0, y0; } (kodhip_tile_desc_bytes() = 24);
+ * slot t is the S x S window of the u8 HWC image at pool + off with its corner at (x0, y0).  A pixel inside the image is
+ * (float)u8 / 255.f, a pixel outside it (an image smaller than the tile) 114 / 255.f: the values of kodhip_val_prep_batch,
+ * so a tile is bit-identical to a letterbox at scale 1.  out_f32 [T][3][S][S] and / or out_pairs bf16 [T][S][S/2][8] (the
+ * network's input layout, the same fp32 -> bf16 rounding, a zero fourth channel); both 16-byte aligned.  Refused before
+ * any launch: a null pool or descs, both outputs null, T < 1, S < 2, odd S, a misaligned output.
+ *
+ * kodhip_merge_detections: rows [V][max_rows][6] (x1, y1, x2, y2, score, class: kodhip_nms_ex's `out`, in image pixels)
+ * and counts [V]; rows at or beyond a view's count are never read.  The views of image i are view_start[i] ..
+ * view_start[i + 1] (view_start: device int [n_images + 1]).  An image's candidates are its views' valid rows in (view,
+ * rank) order; they are sorted by score, best first, equal scores in that order (key = sortable score << 32 | slot, slot =
+ * (view - first view) * max_rows + rank; the bitonic network of kodhip_nms).  Then, candidate by candidate: one that an
+ * earlier keeper has absorbed is skipped; otherwise it is kept as output row nk and absorbs every later candidate, not
+ * yet absorbed, of the same class (any class when agnostic) whose metric against the keeper's ORIGINAL box exceeds thr.
+ * mode 0 (NMS): the absorbed candidate is dropped.  mode 1 (NMM): the keeper's output box also becomes the hull (fminf of
+ * the x1 / y1, fmaxf of the x2 / y2; exact); score and class stay the keeper's.  No further row is kept once max_det are.
+ * All fp32, every operation rounded on its own: area = (x2 - x1) * (y2 - y1); inter = max(0, min(x2) - max(x1)) *
+ * max(0, min(y2) - max(y1)); metric 0 (IoU) = inter / (aa + ab - inter), metric 1 (IoS) = inter / fminf(aa, ab); 0 / 0 is
+ * NaN and matches nothing.  Classes are compared directly: there is no class offset.
+ * keys: n_images * key_cap u64 workspace, key_cap a power of two in 64 .. kodhip_merge_max_rows() (65536) and at least an
+ * image's views * max_rows.  out [n_images][max_det][6], best score first; nout [n_images] (used as scratch between the
+ * launches).  Refused before any launch: null pointers, n_images < 1, max_rows < 1, max_det outside 1..300, metric / mode /
+ * agnostic other than 0 or 1, thr outside [0, 1], a bad key_cap. */
+int kodhip_tile_desc_bytes(void);
+int kodhip_tile_batch(const void* pool, const void* descs, float* out_f32 /* or NULL */, void* out_pairs /* or NULL */,
+                      int T, int S, kodStream_t stream);
+int kodhip_merge_max_rows(void);
+int kodhip_merge_detections(const float* rows, const int* counts, const int* view_start, void* keys, int key_cap,
+                            float* out, int* nout, int n_images, int max_rows, int max_det, int metric, float thr,
+                            int mode, int agnostic, kodStream_t stream);
+
 /* detection <-> ground-truth matching of COCO-style mAP (kod/lightning/callbacks/pycoco_map_eval.py:50-125 ->
  * vision_evaluation -> pycocotools COCOeval.evaluateImg); tp [B][max_det][T] u8, counted [B][max_det] u8.
  * At most 256 ground truths per image take part in the matching (later ones are never matched). */

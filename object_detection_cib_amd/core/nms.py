@@ -102,3 +102,51 @@ def non_max_suppression(detections: torch.Tensor, conf_thres: float = 0.25, nms_
                                             lb.data_ptr() if lb is not None else None, stream), "nms_ex")
     counts = _host.fetch(nout)[0].tolist()                           # one polling hand-off per batch (sizes the outputs)
     return PackedDetections([out[b, :n] for b, n in enumerate(counts)], out, nout)
+
+
+_MERGE_METRICS = {"iou": 0, "ios": 1}
+_MERGE_MODES = {"nms": 0, "nmm": 1}
+
+
+def merge_detections(rows: torch.Tensor, counts: torch.Tensor, view_start, *, thres: float = 0.5, metric: str = "ios",
+                     mode: str = "nmm", agnostic: bool = False, max_det: int = 300) -> PackedDetections:
+    """The cross-view merge of tiled inference (kodhip_merge_detections): rows [V, max_rows, 6] and counts [V] are what
+    kodhip_nms_ex left for each view, in image pixels; the views of image i are view_start[i] .. view_start[i + 1]
+    (`view_start`: a host sequence of n_images + 1 ints).  metric "iou" | "ios" (intersection over the smaller area), mode
+    "nms" (an absorbed row is dropped) | "nmm" (the keeper's box grows to the hull of what it absorbs); classes are
+    compared directly, `agnostic` lets every class absorb every other.  -> per image [n <= max_det, 6], best score first."""
+    _lib.require_gpu()
+    if metric not in _MERGE_METRICS:
+        raise ValueError(f"metric {metric!r}: expected 'iou' or 'ios'")
+    if mode not in _MERGE_MODES:
+        raise ValueError(f"mode {mode!r}: expected 'nms' or 'nmm'")
+    if not 1 <= int(max_det) <= 300:
+        raise ValueError(f"max_det {max_det}: expected 1..300")
+    if not 0.0 <= float(thres) <= 1.0:
+        raise ValueError(f"thres {thres}: expected a value in [0, 1]")
+    start = np.asarray(view_start, dtype=np.int64).reshape(-1)
+    V, max_rows = int(rows.shape[0]), int(rows.shape[1])
+    n_images = len(start) - 1
+    if n_images < 1 or start[0] != 0 or start[-1] > V or (np.diff(start) < 0).any():
+        raise ValueError(f"view_start {start.tolist()}: expected 0 = s[0] <= s[1] <= ... <= {V} for at least one image")
+    if tuple(rows.shape[2:]) != (6,) or counts.numel() < V:
+        raise ValueError(f"rows {tuple(rows.shape)} / counts {tuple(counts.shape)}: expected [V, max_rows, 6] and [V]")
+    limit = _lib.lib().kodhip_merge_max_rows()
+    need = int(np.diff(start).max()) * max_rows
+    if need > limit:
+        raise ValueError(f"an image brings {need} rows to the merge (views x max_rows), more than {limit}")
+    dev = rows.device
+    rows, counts = rows.contiguous(), counts.contiguous()
+    assert rows.dtype == torch.float32 and counts.dtype == torch.int32
+    max_det = int(max_det)
+    key_cap = _key_cap(need)
+    keys = _workspace(dev, n_images * key_cap)
+    vs = torch.from_numpy(start.astype(np.int32)).to(dev)
+    out = torch.empty((n_images, max_det, 6), dtype=torch.float32, device=dev)
+    nout = torch.empty(n_images, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().kodhip_merge_detections(rows.data_ptr(), counts.data_ptr(), vs.data_ptr(), keys.data_ptr(), key_cap,
+                                                  out.data_ptr(), nout.data_ptr(), n_images, max_rows, max_det,
+                                                  _MERGE_METRICS[metric], float(thres), _MERGE_MODES[mode], 1 if agnostic else 0,
+                                                  torch.cuda.current_stream().cuda_stream), "merge_detections")
+    kept = _host.fetch(nout)[0].tolist()                             # the one hand-off of a tiled call (sizes the outputs)
+    return PackedDetections([out[b, :n] for b, n in enumerate(kept)], out, nout)

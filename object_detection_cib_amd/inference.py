@@ -7,7 +7,9 @@ a hipGraph), the prediction decode (kodhip_decode) and the NMS in YOLOv5's detec
 by default, optional class filter / class-agnostic suppression / smaller max_det), whose last launch maps the kept boxes
 from the letterboxed frame back into the source image.  `AugmentedDetector` is detect.py's `--augment`: the letterboxed batch
 goes through the network three times (as is, flipped at 0.83 of its size, at 0.67: kodhip_tta_view / kodhip_decode_view) and
-ONE NMS runs over the merged predictions.
+ONE NMS runs over the merged predictions.  `TiledDetector` is sliced inference for images much larger than `image_size`: the
+image is cut into overlapping tiles at its native resolution (engine/tiles.py, kodhip_tile_batch), every tile and the letterboxed
+whole image go through the network and kodhip_nms_ex, and one kodhip_merge_detections per image joins what the views found.
 """
 from __future__ import annotations
 
@@ -17,9 +19,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .core.nms import non_max_suppression
+from .core.nms import _key_cap, _workspace, merge_detections, non_max_suppression
 from .core.types import FeatureShape
 from .data.device_pipeline import VAL_DESC, ImagePool, _Stager, letterbox_geometry
+from .engine.tiles import tile_plan
 
 
 def letterbox_table(shapes: Sequence[Sequence[int]], image_size: int, first_index: int = 0):
@@ -140,3 +143,129 @@ class AugmentedDetector(Detector):
     against 2 Mi without augmentation."""
 
     augment = True
+
+
+TILE_DESC = np.dtype([("off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("x0", "<i4"), ("y0", "<i4")], align=True)
+
+
+def tiled_plans(shapes: Sequence[Sequence[int]], image_size: int, overlap: float = 0.2, full_view: bool = True,
+                tile_max_det: int = 300):
+    """one `tile_plan` per (h, w); raises ValueError for a bad image or for one whose views bring more rows to the merge
+    than kodhip_merge_max_rows() allows - host arithmetic only, nothing is uploaded or launched"""
+    limit = _lib.lib().kodhip_merge_max_rows()
+    plans = []
+    for i, (h, w) in enumerate(shapes):
+        try:
+            plan = tile_plan(h, w, image_size, overlap, full_view)
+        except ValueError as e:
+            raise ValueError(f"image {i}: {e}") from None
+        if len(plan.views) * int(tile_max_det) > limit:
+            raise ValueError(f"image {i} ({int(h)} x {int(w)}): {len(plan.views)} views x tile_max_det {tile_max_det} rows exceed the "
+                             f"merge's {limit} rows per image; lower tile_max_det, or raise image_size or lower overlap for fewer tiles")
+        plans.append(plan)
+    return plans
+
+
+class TiledDetector(Detector):
+    """det = TiledDetector(net, anchor_info, image_size=640, overlap=0.2, ...); results = det(images)
+
+    Sliced inference for images much larger than `image_size` (aerial, inspection, microscopy): same call and result format as
+    `Detector`, but the image is not shrunk.  Each image is cut into overlapping image_size x image_size tiles at its native
+    resolution (engine/tiles.py; kodhip_tile_batch), with `full_view` the letterboxed whole image is one more view, every view
+    goes through the network and its own NMS (Detector's arguments; at most `tile_max_det` rows per view, mapped into image
+    pixels by the view's KodLetterbox row), and ONE merge per image (kodhip_merge_detections) joins what neighbouring tiles found
+    twice or in halves: `merge` "nmm" (the keeper grows to the hull of what it absorbs) | "nms", `merge_metric` "ios"
+    (intersection over the smaller area) | "iou", `merge_thres`; classes are compared directly unless `agnostic`.
+
+    The views of all images of a call form one stream of slots, processed in chunks of `batch_size` (the final chunk is padded
+    by repeating its last slot: one engine shape set, one GraphedEvalForward); every chunk's NMS writes into call-wide buffers
+    on the device, and the host sees nothing before the merge's counts."""
+
+    def __init__(self, net, anchor_info, image_size: int = 640, batch_size: int = 16, overlap: float = 0.2, full_view: bool = True,
+                 merge: str = "nmm", merge_metric: str = "ios", merge_thres: float = 0.5, tile_max_det: int = 300,
+                 conf_thres: float = 0.25, iou_thres: float = 0.45, classes=None, agnostic: bool = False, multi_label: bool = False,
+                 max_det: int = 300, graphed: bool = False, eval_fused: Optional[bool] = None):
+        super().__init__(net, anchor_info, image_size, batch_size, conf_thres, iou_thres, classes, agnostic, multi_label, max_det,
+                         graphed, eval_fused)
+        if merge not in ("nmm", "nms"):
+            raise ValueError(f"merge {merge!r}: expected 'nmm' or 'nms'")
+        if merge_metric not in ("ios", "iou"):
+            raise ValueError(f"merge_metric {merge_metric!r}: expected 'ios' or 'iou'")
+        if not 0.0 <= float(merge_thres) <= 1.0:
+            raise ValueError(f"merge_thres {merge_thres}: expected a value in [0, 1]")
+        if not 1 <= int(tile_max_det) <= 300:
+            raise ValueError(f"tile_max_det {tile_max_det}: expected 1..300")
+        tile_plan(self.S, self.S, self.S, overlap, full_view)                  # (the overlap's own ValueError, now)
+        assert _lib.lib().kodhip_tile_desc_bytes() == TILE_DESC.itemsize
+        self.overlap, self.full_view = float(overlap), bool(full_view)
+        self.merge, self.merge_metric, self.merge_thres = merge, merge_metric, float(merge_thres)
+        self.tile_max_det = int(tile_max_det)
+
+    def plans(self, shapes: Sequence[Sequence[int]]):
+        """the tile plan of each (h, w); raises what a call with such images would raise"""
+        return tiled_plans(shapes, self.S, self.overlap, self.full_view, self.tile_max_det)
+
+    @torch.no_grad()
+    def __call__(self, images: Sequence[np.ndarray]) -> List[torch.Tensor]:
+        images = list(images)
+        for i, im in enumerate(images):
+            if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
+                raise ValueError(f"image {i}: expected an HWC uint8 array with 3 channels")
+        plans = self.plans([im.shape[:2] for im in images])                    # (all geometry first, as Detector)
+        if not images:
+            return []
+        if self.eval_fused is not None:
+            self.net.fuse_eval(self.eval_fused)
+        lib, B, S, dev = _lib.lib(), self.B, self.S, self.device
+        pool = ImagePool(images, dev)
+        # the slot stream: every view of every image, then the last slot again up to a whole number of chunks
+        slots = [(i, v) for i, plan in enumerate(plans) for v in plan.views]
+        view_start = np.concatenate(([0], np.cumsum([len(p.views) for p in plans])))
+        V = len(slots)
+        slots += [slots[-1]] * (-V % B)
+        tdesc, vdesc = np.zeros(len(slots), dtype=TILE_DESC), np.zeros(len(slots), dtype=VAL_DESC)
+        boxes = np.zeros((len(slots), 6), dtype=np.float32)
+        for k, (i, v) in enumerate(slots):
+            h, w = plans[i].h, plans[i].w
+            if v.full:
+                vdesc[k], row = (a[0] for a in letterbox_table([(h, w)], S, i))
+                vdesc[k]["off"] = pool.offsets[i]
+                assert tuple(row) == tuple(np.float32(v.letterbox))
+            else:
+                tdesc[k] = (pool.offsets[i], h, w, v.x0, v.y0)
+            boxes[k] = v.letterbox
+        t_dev, v_dev, lb_dev = self._stager.upload(tdesc), self._stager.upload(vdesc), self._stager.upload(boxes)
+        stream = torch.cuda.current_stream().cuda_stream
+        rows_all = torch.empty((len(slots), self.tile_max_det, 6), dtype=torch.float32, device=dev)
+        counts_all = torch.empty(len(slots), dtype=torch.int32, device=dev)
+        ncand = torch.empty(B, dtype=torch.int32, device=dev)
+        keep = None
+        x = torch.empty((B, 3, S, S), dtype=torch.float32, device=dev)
+        for c0 in range(0, len(slots), B):
+            k = c0
+            while k < c0 + B:                                                   # runs of tiles / of full views: one launch each
+                e = k + 1
+                while e < c0 + B and slots[e][1].full == slots[k][1].full:
+                    e += 1
+                if slots[k][1].full:
+                    _lib.check(lib.kodhip_val_prep_batch(pool.data.data_ptr(), v_dev.data_ptr() + k * VAL_DESC.itemsize,
+                                                         x[k - c0].data_ptr(), None, e - k, S, stream), "val_prep_batch")
+                else:
+                    _lib.check(lib.kodhip_tile_batch(pool.data.data_ptr(), t_dev.data_ptr() + k * TILE_DESC.itemsize,
+                                                     x[k - c0].data_ptr(), None, e - k, S, stream), "tile_batch")
+                k = e
+            det = self._forward(x).contiguous()
+            assert det.dtype == torch.float32
+            _, rows, P = det.shape
+            nc = P - 5
+            if self.classes is not None and keep is None:
+                keep = torch.zeros(nc, dtype=torch.uint8, device=dev)
+                keep[torch.as_tensor(list(self.classes), dtype=torch.long, device=dev)] = 1
+            key_cap = _key_cap(rows * nc if self.multi_label else rows)
+            keys = _workspace(dev, B * key_cap)
+            _lib.check(lib.kodhip_nms_ex(det.data_ptr(), keys.data_ptr(), key_cap, ncand.data_ptr(), rows_all[c0].data_ptr(),
+                                         counts_all[c0:].data_ptr(), B, rows, nc, float(self.conf_thres), float(self.iou_thres),
+                                         self.tile_max_det, 30000, 0.0 if self.agnostic else 4096.0, 0 if self.multi_label else 1,
+                                         keep.data_ptr() if keep is not None else None, lb_dev.data_ptr() + c0 * 24, stream), "nms_ex")
+        return list(merge_detections(rows_all[:V], counts_all[:V], view_start, thres=self.merge_thres, metric=self.merge_metric,
+                                     mode=self.merge, agnostic=self.agnostic, max_det=self.max_det))
