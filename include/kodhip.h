@@ -482,6 +482,30 @@ int kodhip_merge_detections(const float* rows, const int* counts, const int* vie
                             float* out, int* nout, int n_images, int max_rows, int max_det, int metric, float thr,
                             int mode, int agnostic, kodStream_t stream);
 
+/* ---- model ensembles: weighted boxes fusion (WBF; Solovyev, Wang, Gabruseva 2021), csrc/fusion.hip.  The views of an
+ *      image are the members of an ensemble (model 0 .. M-1); rows, counts and view_start are kodhip_merge_detections'.
+ *
+ * kodhip_fuse_detections, per image, all fp32 with every operation rounded on its own: W = the sum of its views' weights
+ * in view order.  A row of view v with score s is a candidate iff t = s * view_weight[v] > 0 (zero, negative and NaN
+ * scores are dropped); candidates are taken by t descending, equal t by view, then rank (key = sortable t << 32 | slot,
+ * the bitonic network of kodhip_nms).  Each candidate (box b, class c) meets every cluster of class c (every cluster
+ * when agnostic) through the cluster's CURRENT fused box F: area = (x2 - x1) * (y2 - y1), inter = max(0, min(x2) -
+ * max(x1)) * max(0, min(y2) - max(y1)), an empty intersection never matches, iou = inter / ((area_F + area_b) - inter).
+ * It joins the cluster of largest iou > thr (strict, NaN never matches; equal IoUs: the cluster created first): per
+ * coordinate acc += t * x, then st += t, n += 1, F = acc / st.  Without a match it opens a cluster: F = its own four
+ * floats bit for bit, acc = t * x, st = t, n = 1, class c (an agnostic cluster keeps its first member's class).  Final
+ * score of a cluster = (st / n) * (min(n, W) / W), n as a float.  out: the clusters by final score descending, equal
+ * scores by creation order, the first max_det of them as x1, y1, x2, y2, score, class.  Nothing is cut before that ranking.
+ * view_weight: device fp32 [V], finite and > 0.  keys: n_images * key_cap u64 workspace, key_cap a power of two in 64 ..
+ * kodhip_fuse_max_rows() (4096 = 13 models x 300 rows) and at least an image's views * max_rows (views that do not fit
+ * are left out; nothing is written beyond key_cap).  out [n_images][max_det][6]; nout [n_images] (used as scratch between
+ * the launches).  Refused before any launch: null pointers, n_images < 1, max_rows < 1, max_det outside 1..300, agnostic
+ * other than 0 or 1, thr outside [0, 1], a bad key_cap. */
+int kodhip_fuse_max_rows(void);
+int kodhip_fuse_detections(const float* rows, const int* counts, const int* view_start, const float* view_weight,
+                           void* keys, int key_cap, float* out, int* nout, int n_images, int max_rows, int max_det,
+                           float thr, int agnostic, kodStream_t stream);
+
 /* detection <-> ground-truth matching of COCO-style mAP (kod/lightning/callbacks/pycoco_map_eval.py:50-125 ->
  * vision_evaluation -> pycocotools COCOeval.evaluateImg); tp [B][max_det][T] u8, counted [B][max_det] u8.
  * At most 256 ground truths per image take part in the matching (later ones are never matched). */

@@ -134,6 +134,8 @@ SIGNATURES = {
     "kodhip_tile_batch": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "kodhip_merge_max_rows": (i32, []),
     "kodhip_merge_detections": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp]),
+    "kodhip_fuse_max_rows": (i32, []),
+    "kodhip_fuse_detections": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, f32, i32, vp]),
     "kodhip_map_match": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(f64), i32, i32, vp]),
     "kodhip_confusion_max_det": (i32, []),
     "kodhip_confusion_lds_classes": (i32, []),

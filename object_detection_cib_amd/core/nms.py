@@ -150,3 +150,51 @@ def merge_detections(rows: torch.Tensor, counts: torch.Tensor, view_start, *, th
                                                   torch.cuda.current_stream().cuda_stream), "merge_detections")
     kept = _host.fetch(nout)[0].tolist()                             # the one hand-off of a tiled call (sizes the outputs)
     return PackedDetections([out[b, :n] for b, n in enumerate(kept)], out, nout)
+
+
+def fuse_detections(rows: torch.Tensor, counts: torch.Tensor, view_start, weights=None, *, thres: float = 0.55,
+                    agnostic: bool = False, max_det: int = 300) -> PackedDetections:
+    """Weighted boxes fusion of an ensemble's detections (kodhip_fuse_detections): rows [V, max_rows, 6], counts [V] and
+    `view_start` as in merge_detections, the views of an image being the ensemble's members.  weights: None (all ones) or
+    one float per view, finite and > 0.  Rows are taken by score * weight, best first; each joins the cluster of its class
+    (any class when `agnostic`) whose current fused box it overlaps most, with IoU > thres, or opens a cluster; a cluster's
+    box is the score-weighted mean of its members, its score their mean score scaled by min(members, sum of the image's
+    weights) / that sum.  -> per image [n <= max_det, 6], best fused score first."""
+    _lib.require_gpu()
+    if not 1 <= int(max_det) <= 300:
+        raise ValueError(f"max_det {max_det}: expected 1..300")
+    if not 0.0 <= float(thres) <= 1.0:
+        raise ValueError(f"thres {thres}: expected a value in [0, 1]")
+    start = np.asarray(view_start, dtype=np.int64).reshape(-1)
+    V, max_rows = int(rows.shape[0]), int(rows.shape[1])
+    n_images = len(start) - 1
+    if n_images < 1 or start[0] != 0 or start[-1] > V or (np.diff(start) < 0).any():
+        raise ValueError(f"view_start {start.tolist()}: expected 0 = s[0] <= s[1] <= ... <= {V} for at least one image")
+    if rows.dim() != 3 or tuple(rows.shape[2:]) != (6,) or max_rows < 1 or counts.numel() < V:
+        raise ValueError(f"rows {tuple(rows.shape)} / counts {tuple(counts.shape)}: expected [V, max_rows, 6] and [V]")
+    if weights is None:
+        w = np.ones(V, dtype=np.float32)
+    else:
+        w = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float32).reshape(-1)
+        if len(w) != V or not (np.isfinite(w).all() and (w > 0).all()):
+            raise ValueError(f"weights {w.tolist()}: expected {V} finite values > 0, one per view")
+    limit = _lib.lib().kodhip_fuse_max_rows()
+    need = int(np.diff(start).max()) * max_rows
+    if need > limit:
+        raise ValueError(f"an image brings {need} rows to the fusion (views x max_rows), more than {limit}")
+    dev = rows.device
+    rows, counts = rows.contiguous(), counts.contiguous()
+    assert rows.dtype == torch.float32 and counts.dtype == torch.int32
+    max_det = int(max_det)
+    key_cap = _key_cap(need)
+    keys = _workspace(dev, n_images * key_cap)
+    vs = torch.from_numpy(start.astype(np.int32)).to(dev)
+    vw = torch.from_numpy(w).to(dev)
+    out = torch.empty((n_images, max_det, 6), dtype=torch.float32, device=dev)
+    nout = torch.empty(n_images, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().kodhip_fuse_detections(rows.data_ptr(), counts.data_ptr(), vs.data_ptr(), vw.data_ptr(), keys.data_ptr(),
+                                                 key_cap, out.data_ptr(), nout.data_ptr(), n_images, max_rows, max_det,
+                                                 float(thres), 1 if agnostic else 0,
+                                                 torch.cuda.current_stream().cuda_stream), "fuse_detections")
+    kept = _host.fetch(nout)[0].tolist()                             # the one hand-off of the fusion (sizes the outputs)
+    return PackedDetections([out[b, :n] for b, n in enumerate(kept)], out, nout)

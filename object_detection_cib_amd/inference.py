@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .core.nms import _key_cap, _workspace, merge_detections, non_max_suppression
+from .core.nms import _key_cap, _workspace, fuse_detections, merge_detections, non_max_suppression
 from .core.types import FeatureShape
 from .data.device_pipeline import VAL_DESC, ImagePool, _Stager, letterbox_geometry
 from .engine.tiles import tile_plan
@@ -143,6 +143,111 @@ class AugmentedDetector(Detector):
     against 2 Mi without augmentation."""
 
     augment = True
+
+
+class EnsembleDetector:
+    """det = EnsembleDetector([net_a, net_b], anchor_info, image_size=640, ...); results = det(images)
+
+    Several networks on the same images (YOLOv5 `detect.py --weights a.pt b.pt`): Detector's call and result format.  `nets`
+    are one or more networks on one device with the same class count - widths, depths and parameters may differ;
+    `anchor_info` is one LayerwiseAnchorInfo for all of them or one per network.  Validation, letterboxing and chunk padding
+    happen once per chunk, every member's forward reads the same input tensor (graphed=True: one GraphedEvalForward per
+    member and input shape; eval_fused is handed to every member).
+
+    merge "wbf" (default): each member's detections go through non_max_suppression with the detector's options and the
+    letterbox, and ONE weighted boxes fusion per chunk (core.nms.fuse_detections: `weights` per member, `fuse_thres`,
+    `agnostic`, `max_det`) averages what the members agree on and ranks it by how many of them found it.  fuse_thres must
+    not be below iou_thres: one member's surviving boxes could then fuse with each other.  A single member has nothing to
+    fuse and is returned as its NMS leaves it.
+    merge "nms": YOLOv5's `Ensemble` - the members' decoded tensors are concatenated along the row axis and go through one
+    non_max_suppression; `weights` must be None."""
+
+    def __init__(self, nets, anchor_info, image_size: int = 640, batch_size: int = 16, conf_thres: float = 0.25,
+                 iou_thres: float = 0.45, classes=None, agnostic: bool = False, multi_label: bool = False, max_det: int = 300,
+                 graphed: bool = False, eval_fused: Optional[bool] = None, merge: str = "wbf", weights=None,
+                 fuse_thres: float = 0.55):
+        nets = list(nets)
+        if not nets:
+            raise ValueError("nets: expected at least one network")
+        if merge not in ("wbf", "nms"):
+            raise ValueError(f"merge {merge!r}: expected 'wbf' or 'nms'")
+        # (a LayerwiseAnchorInfo is itself a named tuple: a plain list or tuple holds one per network)
+        per_net = isinstance(anchor_info, (list, tuple)) and not hasattr(anchor_info, "_fields")
+        infos = list(anchor_info) if per_net else [anchor_info] * len(nets)
+        if len(infos) != len(nets):
+            raise ValueError(f"anchor_info: {len(infos)} entries for {len(nets)} networks (expected one, or one per network)")
+        if merge == "nms" and weights is not None:
+            raise ValueError("weights: merge 'nms' takes none (every member's rows enter one NMS as they are)")
+        if weights is None:
+            w = np.ones(len(nets), dtype=np.float32)
+        else:
+            w = np.asarray(weights, dtype=np.float32).reshape(-1)
+            if len(w) != len(nets) or not (np.isfinite(w).all() and (w > 0).all()):
+                raise ValueError(f"weights {w.tolist()}: expected {len(nets)} finite values > 0, one per network")
+        if not 0.0 <= float(fuse_thres) <= 1.0:
+            raise ValueError(f"fuse_thres {fuse_thres}: expected a value in [0, 1]")
+        if merge == "wbf" and float(fuse_thres) < float(iou_thres):
+            raise ValueError(f"fuse_thres {fuse_thres} below iou_thres {iou_thres}: one member's surviving boxes could fuse with each other")
+        # (Detector's own checks: image_size, batch_size, max_det, a GPU)
+        self.members = [Detector(net, info, image_size, batch_size, conf_thres, iou_thres, classes, agnostic, multi_label, max_det,
+                                 graphed, eval_fused) for net, info in zip(nets, infos)]
+        first = self.members[0]
+        if any(m.device != first.device for m in self.members):
+            raise ValueError("nets: expected every network on the same device")
+        if merge == "wbf" and len(nets) * int(max_det) > _lib.lib().kodhip_fuse_max_rows():
+            raise ValueError(f"{len(nets)} networks x max_det {max_det} rows exceed the fusion's {_lib.lib().kodhip_fuse_max_rows()} "
+                             f"rows per image; lower max_det")
+        self.S, self.B, self.device = first.S, first.B, first.device
+        self.conf_thres, self.iou_thres, self.classes = conf_thres, iou_thres, classes
+        self.agnostic, self.multi_label, self.max_det = bool(agnostic), bool(multi_label), int(max_det)
+        self.graphed, self.eval_fused = bool(graphed), eval_fused
+        self.merge, self.weights, self.fuse_thres = merge, w, float(fuse_thres)
+        self._stager = first._stager
+
+    @torch.no_grad()
+    def __call__(self, images: Sequence[np.ndarray]) -> List[torch.Tensor]:
+        images = list(images)
+        for i, im in enumerate(images):
+            if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
+                raise ValueError(f"image {i}: expected an HWC uint8 array with 3 channels")
+        tables = [letterbox_table([im.shape[:2] for im in images[i:i + self.B]], self.S, i) for i in range(0, len(images), self.B)]
+        if self.eval_fused is not None:
+            for m in self.members:
+                m.net.fuse_eval(self.eval_fused)
+        B, S, M = self.B, self.S, len(self.members)
+        nms = dict(agnostic=self.agnostic, multi_label=self.multi_label, max_det=self.max_det)
+        results = []
+        for c, (descs, boxes) in enumerate(tables):
+            chunk = images[c * B:(c + 1) * B]
+            n = len(chunk)
+            pool = ImagePool(chunk, self.device)
+            descs["off"] = pool.offsets
+            if n < B:              # pad with the last descriptor, as Detector does
+                descs = np.concatenate((descs, np.repeat(descs[-1:], B - n)))
+                boxes = np.concatenate((boxes, np.repeat(boxes[-1:], B - n, axis=0)))
+            d_dev = self._stager.upload(descs)
+            x = torch.empty((B, 3, S, S), dtype=torch.float32, device=self.device)
+            _lib.check(_lib.lib().kodhip_val_prep_batch(pool.data.data_ptr(), d_dev.data_ptr(), x.data_ptr(), None, B, S,
+                                                        torch.cuda.current_stream().cuda_stream), "val_prep_batch")
+            dets = [m._forward(x) for m in self.members]
+            nc = {int(d.shape[2]) - 5 for d in dets}
+            if len(nc) != 1:
+                raise ValueError(f"nets: class counts {sorted(nc)} differ")
+            if self.merge == "nms":
+                out = non_max_suppression(torch.cat([d.float() for d in dets], dim=1), self.conf_thres, self.iou_thres, self.classes,
+                                          letterbox=boxes, **nms)
+            else:
+                outs = [non_max_suppression(d, self.conf_thres, self.iou_thres, self.classes, letterbox=boxes, **nms) for d in dets]
+                if M == 1:
+                    out = outs[0]
+                else:
+                    # image-major: view b * M + m is model m of image b
+                    rows = torch.stack([o.packed for o in outs], dim=1).reshape(B * M, self.max_det, 6)
+                    counts = torch.stack([o.counts for o in outs], dim=1).reshape(B * M)
+                    out = fuse_detections(rows, counts, np.arange(B + 1) * M, np.tile(self.weights, B), thres=self.fuse_thres,
+                                          agnostic=self.agnostic, max_det=self.max_det)
+            results.extend(out[:n])
+        return results
 
 
 TILE_DESC = np.dtype([("off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("x0", "<i4"), ("y0", "<i4")], align=True)
