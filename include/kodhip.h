@@ -527,6 +527,42 @@ int kodhip_confusion_match(const float* det, const int* ndet, const double* gt_b
                            const int* gt_start, long long* matrix, int B, int max_det, int nc, float conf_thres,
                            double iou_thres, kodStream_t stream);
 
+/* ---- YOLOv5 validation metrics (val.py process_batch + utils/metrics.py ap_per_class), csrc/val_metrics.hip.
+ * A record is kodhip_val_record_bytes() = 8 bytes: {score fp32 bits : 32, class : 16 | mask over the IoU thresholds : 16}.
+ * records / count / nt are device memory owned by the caller: records [capacity] (8-byte aligned), count int32 [1] (the
+ * running record count), nt int64 [nc] (ground truths per class, ADDED to).  capacity <= 2^30; nothing is ever written at
+ * or beyond it, so a caller that keeps capacity >= the sum of B * max_det over its batches never loses a record.
+ *
+ * kodhip_val_match: the arrays of kodhip_confusion_match plus T <= kodhip_val_max_thresholds() host fp64 IoU thresholds
+ * (used as given).  Per image, fp64 IoU without +1 or epsilon (a zero or NaN union is never a candidate): a detection
+ * picks the ground truth of its own class with the largest IoU (ties -> lower ground-truth index) and is correct at
+ * threshold t iff run < t <= IoU, run = the largest IoU among LOWER-index detections that picked the same ground truth
+ * (-1 if none); a detection that loses its ground truth is not re-matched.  Every detection with a class in [0, nc) appends
+ * one record, in image order then detection order; offsets is device scratch int32 [B].  max_det <= kodhip_val_max_det().
+ *
+ * kodhip_val_append: appends the first min(*src_count, src_bound) records of src behind dst's and advances *dst_count.
+ *
+ * kodhip_val_curves: sorts the records by (class ascending, score descending, arrival ascending) and evaluates, per class
+ * with nt > 0 and at least one record (zero rows otherwise), ap_per_class in fp64 and its operation order:
+ * r [nc][npx] = interp(-px, -conf, recall, left = 0) and p [nc][npx] = interp(-px, -conf, precision, left = 1) at
+ * threshold 0, ap [nc][T] = trapezoid sum over xr of interp(xr, [0, recall, 1], envelope of [1, precision, 0]); n_p [nc]
+ * int64 = records per class.  px [npx] and xr [nx <= 1024] are DEVICE copies of the host's fp64 grids (np.linspace(0, 1,
+ * 1000) and np.linspace(0, 1, 101)): the kernels never recompute a grid value.  workspace: device memory of at least
+ * kodhip_val_curves_workspace_bytes(capacity, nc, T) bytes (-1 for bad arguments), 16-byte aligned.  Scores >= 0.
+ * All three only enqueue (no allocation, copy to the host or synchronisation). */
+int kodhip_val_max_det(void);
+int kodhip_val_max_thresholds(void);
+int kodhip_val_record_bytes(void);
+int kodhip_val_match(const float* det, const int* ndet, const double* gt_boxes, const long* gt_labels, const int* gt_start,
+                     const double* iou_thresholds /* host */, int T, void* records, int* count, long long capacity,
+                     long long* nt, int* offsets, int B, int max_det, int nc, kodStream_t stream);
+int kodhip_val_append(void* dst, int* dst_count, long long dst_capacity, const void* src, const int* src_count,
+                      long long src_bound, kodStream_t stream);
+long long kodhip_val_curves_workspace_bytes(long long capacity, int nc, int T);
+int kodhip_val_curves(const void* records, const int* count, long long capacity, const long long* nt, const double* px, int npx,
+                      const double* xr, int nx, int nc, int T, void* workspace, double* p, double* r, double* ap,
+                      long long* n_p, kodStream_t stream);
+
 /* ---- auto-anchor (YOLOv5 utils/autoanchor.py: check_anchors / kmean_anchors), csrc/anchors.hip.  Box sizes wh are device
  * fp32 [N][2], positive and finite, 8-byte aligned.  Every launch uses min(ceil(N / kodhip_anchor_block_size()),
  * kodhip_anchor_grid_cap()) blocks, grid-strided beyond: sums are ordered by N alone and repeat bit for bit.  The functions

@@ -140,6 +140,13 @@ SIGNATURES = {
     "kodhip_confusion_max_det": (i32, []),
     "kodhip_confusion_lds_classes": (i32, []),
     "kodhip_confusion_match": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f64, vp]),
+    "kodhip_val_max_det": (i32, []),
+    "kodhip_val_max_thresholds": (i32, []),
+    "kodhip_val_record_bytes": (i32, []),
+    "kodhip_val_match": (i32, [vp, vp, vp, vp, vp, C.POINTER(f64), i32, vp, vp, C.c_longlong, vp, vp, i32, i32, i32, vp]),
+    "kodhip_val_append": (i32, [vp, vp, C.c_longlong, vp, vp, C.c_longlong, vp]),
+    "kodhip_val_curves_workspace_bytes": (C.c_longlong, [C.c_longlong, i32, i32]),
+    "kodhip_val_curves": (i32, [vp, vp, C.c_longlong, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "kodhip_anchor_max_anchors": (i32, []),
     "kodhip_anchor_max_population": (i32, []),
     "kodhip_anchor_max_restarts": (i32, []),

@@ -25,7 +25,7 @@ from ... import _lib
 from ...core.label_assignment.yv5 import BatchedTargets
 from ...core.nms import PackedDetections
 
-_RING = 8          # pinned upload slots for the per-image detection counts (see _upload_counts)
+_RING = 8          # pinned upload slots for the per-image detection counts (see PinnedCountUpload)
 
 
 def reduce_counts(counts: torch.Tensor, process_group=None) -> torch.Tensor:
@@ -62,24 +62,15 @@ def per_class_from(matrix: np.ndarray) -> dict:
     return {"precision": precision, "recall": recall, "f1": f1, "missed": m[nc, :nc].copy(), "background_fp": m[:nc, nc].copy()}
 
 
-class DeviceConfusionMatrix:
-    def __init__(self, num_classes: int, class_names: Sequence[str] | None = None, conf_thres: float = 0.25,
-                 iou_thres: float = 0.45):
-        self.nc = num_classes
-        self.names = list(class_names) if class_names else [str(i) for i in range(num_classes)]
-        self.conf_thres, self.iou_thres = float(conf_thres), float(iou_thres)
-        self._m = None                  # device int64 [(nc+1)^2], allocated with the first batch (its device)
+class PinnedCountUpload:
+    """The per-image detection counts are host integers (tensor shapes).  torch.tensor(counts, device=dev) is a
+    pageable copy: it blocks the host until the stream has drained.  Here: an asynchronous copy out of a pinned slot;
+    a slot is reused _RING batches later, behind the event recorded after its copy (long complete by then)."""
+
+    def __init__(self):
         self._ring, self._slot = [], 0
-        self._arange = {}
 
-    def reset(self):
-        if self._m is not None:
-            self._m.zero_()
-
-    def _upload_counts(self, counts, dev) -> torch.Tensor:
-        """The per-image detection counts are host integers (tensor shapes).  torch.tensor(counts, device=dev) is a
-        pageable copy: it blocks the host until the stream has drained.  Here: an asynchronous copy out of a pinned slot;
-        a slot is reused _RING batches later, behind the event recorded after its copy (long complete by then)."""
+    def __call__(self, counts, dev) -> torch.Tensor:
         B = len(counts)
         if not self._ring or self._ring[0][0].numel() < B:
             self._ring = [[torch.empty(max(B, 64), dtype=torch.int32).pin_memory(), None] for _ in range(_RING)]
@@ -94,6 +85,21 @@ class DeviceConfusionMatrix:
         slot[1] = torch.cuda.Event()
         slot[1].record()
         return ndet
+
+
+class DeviceConfusionMatrix:
+    def __init__(self, num_classes: int, class_names: Sequence[str] | None = None, conf_thres: float = 0.25,
+                 iou_thres: float = 0.45):
+        self.nc = num_classes
+        self.names = list(class_names) if class_names else [str(i) for i in range(num_classes)]
+        self.conf_thres, self.iou_thres = float(conf_thres), float(iou_thres)
+        self._m = None                  # device int64 [(nc+1)^2], allocated with the first batch (its device)
+        self._upload_counts = PinnedCountUpload()
+        self._arange = {}
+
+    def reset(self):
+        if self._m is not None:
+            self._m.zero_()
 
     def add_batch(self, targets, detections: Sequence[torch.Tensor]):
         """detections: list of [n, 6] tensors (non_max_suppression output, descending score; its PackedDetections is used in

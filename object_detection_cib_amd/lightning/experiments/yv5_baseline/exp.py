@@ -57,7 +57,7 @@ class DefaultYolov5Experiment:
                  graphed: bool = False, max_targets: int = 4096, world_size: int = 1,
                  gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
                  eval_fused: Optional[bool] = None, val_confusion: bool = False, val_confusion_conf: float = 0.25,
-                 val_confusion_iou: float = 0.45, val_augment: bool = False):
+                 val_confusion_iou: float = 0.45, val_augment: bool = False, val_metrics: bool = False):
         if gradient_clip_algorithm not in CLIP_ALGORITHMS:
             raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected one of {CLIP_ALGORITHMS}")
         # Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm): handed to the FusedSGD / the captured step
@@ -97,6 +97,12 @@ class DefaultYolov5Experiment:
         # val_augment: the forward of validation_step becomes layers.get_detections_augmented (graphed: GraphedAugmentedForward, one
         # hipGraph over all three views); validate(), the mAP evaluator and val_confusion receive the NMS output as without it
         self.val_augment = bool(val_augment)
+        # val_metrics: validate() also feeds every batch to a DeviceDetectionMetrics (YOLOv5's val.py table: process_batch +
+        # ap_per_class on the device) and reports metrics/precision, metrics/recall, metrics/f1, metrics/best_conf,
+        # metrics/mAP_0.5 and metrics/mAP_0.5:0.95; the object stays readable as `self.metrics`.  Under a validation group its
+        # records are GATHERED (the whole validation set's values), whatever val_sync says.
+        self.val_metrics = bool(val_metrics)
+        self.metrics = None
 
     # exp.py:156-162
     def configure_optimizers(self):
@@ -246,17 +252,23 @@ class DefaultYolov5Experiment:
         if self.val_confusion:
             from ...callbacks.confusion import DeviceConfusionMatrix
             cm = self.confusion = DeviceConfusionMatrix(num_classes, class_names, self.val_confusion_conf, self.val_confusion_iou)
+        vm = None
+        if self.val_metrics:
+            from ...callbacks.val_metrics import DeviceDetectionMetrics
+            vm = self.metrics = DeviceDetectionMetrics(num_classes, class_names)
+        extra = [c for c in (cm, vm) if c is not None]
         _lib.limit_host_threads()
         if self.eval_fused is not None:
             self.net.fuse_eval(self.eval_fused)
         with _gc_paused():
             for b in batches:
                 targets, dets = self.validation_step(b)
-                if cm is not None:         # both consumers take the batch's boxes as one device upload
+                if extra:                  # every consumer takes the batch's boxes as one device upload
                     if not isinstance(targets, BatchedTargets):
                         targets = BatchedTargets.from_targets(targets, dets[0].device if len(dets) else torch.device("cuda"))
                     ev.add_batch(targets, dets)
-                    cm.add_batch(targets, dets)
+                    for c in extra:
+                        c.add_batch(targets, dets)
                 else:
                     ev.add_batch(targets, dets)
         pg = self._val_group()
@@ -268,6 +280,11 @@ class DefaultYolov5Experiment:
             for c, name in enumerate(cm.names):
                 report[f"precision_{name}"] = float(pc["precision"][c])
                 report[f"recall_{name}"] = float(pc["recall"][c])
+        if vm is not None:
+            res = vm.compute(pg)
+            report.update({"metrics/precision": res["mp"], "metrics/recall": res["mr"], "metrics/f1": res["mf1"],
+                           "metrics/best_conf": res["best_conf"], "metrics/mAP_0.5": res["map50"],
+                           "metrics/mAP_0.5:0.95": res["map"]})
         return report
 
     def _all_ranks_validate(self, pg, timeout_s: float = 300.0):
