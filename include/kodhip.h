@@ -506,6 +506,64 @@ int kodhip_fuse_detections(const float* rows, const int* counts, const int* view
                            void* keys, int key_cap, float* out, int* nout, int n_images, int max_rows, int max_det,
                            float thr, int agnostic, kodStream_t stream);
 
+/* ---- multi-object tracking in ByteTrack's form (Zhang et al., ECCV 2022), csrc/tracking.hip: which of this frame's boxes is
+ *      the object seen in the frame before.  All state lives in the caller's device buffer; a call is one launch, one block
+ *      per stream, and can be captured in a hipGraph (no synchronisation, no allocation, every loop bounded by cap and max_rows).
+ *
+ * state: per stream kodhip_track_header_bytes() (16: KodTrackHeader) + cap * kodhip_track_bytes() (112: KodTrack), 16-byte
+ * aligned; cap a power of two in 64..1024.  kodhip_track_reset frees all slots of S streams: every byte 0, next_id = 1.
+ * kf holds, per coordinate c of (cx, cy, a = w / h, h), p, v, Ppp, Ppv, Pvv: ByteTrack's 8-state constant-velocity Kalman
+ * filter, whose covariance never leaves four independent 2 x 2 blocks.  All arithmetic is fp32, every operation rounded on
+ * its own, in the order written here; wp = 0.05f, wv = 0.00625f:
+ *   measurement of a row: w = x2 - x1, h = y2 - y1, cx = x1 + w / 2, cy = y1 + h / 2, a = w / h; a row with !(w > 0 && h > 0)
+ *              or a NaN score takes part in nothing;
+ *   track box: w = a * h, x1 = cx - w / 2, y1 = cy - h / 2, x2 = x1 + w, y2 = y1 + h (from the p values);
+ *   initiate : p = z, v = 0, Ppv = 0, Ppp = s * s with s = 0.1f * h (a: 1e-2f), Pvv = s * s with s = 0.0625f * h (a: 1e-5f);
+ *   predict  : hh = h's p before; sp = wp * hh (a: 1e-2f), sv = wv * hh (a: 1e-5f); from the old values p = p + v,
+ *              Ppp = ((Ppp + 2 * Ppv) + Pvv) + sp * sp, Ppv = Ppv + Pvv, Pvv = Pvv + sv * sv;
+ *   update(z): hh = h's p before; sr = wp * hh (a: 1e-1f); S = Ppp + sr * sr, kp = Ppp / S, kv = Ppv / S, y = z - p;
+ *              p = p + kp * y, v = v + kv * y, Ppp = Ppp - (kp * kp) * S, Ppv = Ppv - (kp * kv) * S, Pvv = Pvv - (kv * kv) * S.
+ * Similarity of a track box A and a row B: kodhip_fuse_detections' IoU (area = (x2 - x1) * (y2 - y1), inter = max(0, min(x2)
+ * - max(x1)) * max(0, min(y2) - max(y1)), iou = inter / ((aa + ab) - inter)), times the row's score where fuse_score applies;
+ * NaN matches nothing; with agnostic 0 a pair of different classes is not admissible.
+ * Association is greedy and fully ordered (NOT ByteTrack's optimal linear assignment, whose ties are undetermined): the
+ * admissible pairs (slot t, row d) with sim > thr (strict) by sim descending, equal sims by lower t, then lower d; a pair is
+ * accepted iff neither side is taken yet.
+ * One frame (frame += 1 first): 1. every tracked or lost track is predicted, a lost one with v of h set to 0 first; new
+ * tracks are not.  2. a row is "high" iff score > high_thres, "low" iff low_thres < score <= high_thres.  3. tracked and
+ * lost tracks against the high rows, fuse_score as given, thr = sim1; a match updates the filter, sets state = tracked and
+ * score, cls, last_frame from the row (a lost track keeps its id).  4. tracks still unmatched whose state is tracked
+ * against the low rows, plain IoU, thr = sim2.  5. tracked tracks still unmatched become lost (last_frame stays).  6. new
+ * tracks against the high rows left over, fuse_score as given, thr = sim3; an unmatched new track becomes free.  7. high
+ * rows still unmatched with score >= new_thres start tracks, in row order into the lowest free slots (those of step 6
+ * included): id = next_id++, the filter initiated, state = tracked if frame == 1 else new, start_frame = last_frame = frame;
+ * without a free slot the row is dropped and dropped += 1.  8. lost tracks with frame - last_frame > max_lost become free
+ * (only `state` changes; the slot is usable from the next frame).  9. every track in state tracked, by slot ascending:
+ * out row = track box of the updated filter, score, class; out_ids row = id, the matched row (a frame-1 creation: its own).
+ *
+ * kodhip_track_update: rows [S][F][max_rows][6] (kodhip_nms_ex's `out`), counts [S][F] (rows at or beyond a count are never
+ * read); a stream's F frames run one after the other inside the launch (a clip: a batch of consecutive frames through the
+ * network, then one call).  out [S][F][cap][6], out_ids [S][F][cap][2], nout [S][F]; nothing is written behind the emitted
+ * rows.  workspace: kodhip_track_workspace_bytes() bytes - 0 today, the pointer is not read and may be null.  Refused before
+ * any launch: null pointers, S < 1, F < 1, max_rows outside 1..300, a bad cap, a threshold outside [0, 1], low_thres >
+ * high_thres, fuse_score / agnostic other than 0 or 1, max_lost < 0. */
+typedef struct KodTrackHeader { int frame, next_id, dropped, pad; } KodTrackHeader;               /* 16 bytes */
+typedef struct KodTrack {                                                                         /* 112 bytes */
+  int state;                    /* 0 free, 1 new, 2 tracked, 3 lost */
+  int id, last_frame, start_frame;
+  float score, cls;
+  float kf[4][5];
+  int pad[2];
+} KodTrack;
+int kodhip_track_header_bytes(void);
+int kodhip_track_bytes(void);
+long long kodhip_track_workspace_bytes(int S, int cap, int max_rows);
+int kodhip_track_reset(void* state, int S, int cap, kodStream_t stream);
+int kodhip_track_update(void* state, const float* rows, const int* counts, int S, int F, int max_rows, int cap,
+                        float high_thres, float low_thres, float new_thres, float sim1, float sim2, float sim3,
+                        int fuse_score, int agnostic, int max_lost, float* out, int* out_ids, int* nout, void* workspace,
+                        kodStream_t stream);
+
 /* detection <-> ground-truth matching of COCO-style mAP (kod/lightning/callbacks/pycoco_map_eval.py:50-125 ->
  * vision_evaluation -> pycocotools COCOeval.evaluateImg); tp [B][max_det][T] u8, counted [B][max_det] u8.
  * At most 256 ground truths per image take part in the matching (later ones are never matched). */

@@ -136,7 +136,12 @@ SIGNATURES = {
     "kodhip_merge_detections": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp]),
     "kodhip_fuse_max_rows": (i32, []),
     "kodhip_fuse_detections": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, f32, i32, vp]),
-    "kodhip_map_match": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(f64), i32, i32, vp]),
+    "kodhip_track_header_bytes": (i32, []),
+    "kodhip_track_bytes": (i32, []),
+    "kodhip_track_workspace_bytes": (C.c_longlong, [i32, i32, i32]),
+    "kodhip_track_reset": (i32, [vp, i32, i32, vp]),
+    "kodhip_track_update": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, f32, f32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "kodhip_map_match":(i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(f64), i32, i32, vp]),
     "kodhip_confusion_max_det": (i32, []),
     "kodhip_confusion_lds_classes": (i32, []),
     "kodhip_confusion_match": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f64, vp]),

@@ -10,6 +10,7 @@ goes through the network three times (as is, flipped at 0.83 of its size, at 0.6
 ONE NMS runs over the merged predictions.  `TiledDetector` is sliced inference for images much larger than `image_size`: the
 image is cut into overlapping tiles at its native resolution (engine/tiles.py, kodhip_tile_batch), every tile and the letterboxed
 whole image go through the network and kodhip_nms_ex, and one kodhip_merge_detections per image joins what the views found.
+`TrackedDetector` follows the boxes through a video: Detector, then ByteTrack on the device (core/tracking.py, kodhip_track_update).
 """
 from __future__ import annotations
 
@@ -20,6 +21,7 @@ import torch
 
 from . import _lib
 from .core.nms import _key_cap, _workspace, fuse_detections, merge_detections, non_max_suppression
+from .core.tracking import ByteTracker, Tracks
 from .core.types import FeatureShape
 from .data.device_pipeline import VAL_DESC, ImagePool, _Stager, letterbox_geometry
 from .engine.tiles import tile_plan
@@ -101,8 +103,9 @@ class Detector:
                 m.training = was
         return get_detections(FeatureShape(width=x.shape[3], height=x.shape[2]), res, self.anchor_info)
 
-    @torch.no_grad()
-    def __call__(self, images: Sequence[np.ndarray]) -> List[torch.Tensor]:
+    def _chunks(self, images):
+        """images in chunks of batch_size through letterbox, forward and NMS -> (real images of the chunk, the padded chunk's
+        PackedDetections), chunk after chunk"""
         images = list(images)
         for i, im in enumerate(images):
             if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
@@ -112,7 +115,6 @@ class Detector:
         if self.eval_fused is not None:
             self.net.fuse_eval(self.eval_fused)
         B, S = self.B, self.S
-        results = []
         for c, (descs, boxes) in enumerate(tables):
             chunk = images[c * B:(c + 1) * B]
             n = len(chunk)
@@ -128,6 +130,12 @@ class Detector:
             det = self._forward(x)
             out = non_max_suppression(det, self.conf_thres, self.iou_thres, self.classes, agnostic=self.agnostic,
                                       multi_label=self.multi_label, max_det=self.max_det, letterbox=boxes)
+            yield n, out
+
+    @torch.no_grad()
+    def __call__(self, images: Sequence[np.ndarray]) -> List[torch.Tensor]:
+        results = []
+        for n, out in self._chunks(images):
             results.extend(out[:n])
         return results
 
@@ -374,3 +382,57 @@ class TiledDetector(Detector):
                                          keep.data_ptr() if keep is not None else None, lb_dev.data_ptr() + c0 * 24, stream), "nms_ex")
         return list(merge_detections(rows_all[:V], counts_all[:V], view_start, thres=self.merge_thres, metric=self.merge_metric,
                                      mode=self.merge, agnostic=self.agnostic, max_det=self.max_det))
+
+
+class TrackedDetector(Detector):
+    """det = TrackedDetector(net, anchor_info, streams=4, ...); tracks = det(frames)
+
+    Detector followed by ByteTracker (core/tracking.py; kodhip_track_update): `det(frames)` takes the next frame of every
+    stream - `streams` HWC uint8 arrays, stream s at index s, of any sizes - and returns `Tracks`: per stream the [n, 6] tensor
+    of the tracked boxes in that frame's own pixels, with `.ids` and `.det_index`.  `clip(frames, stream)` takes consecutive
+    frames of ONE stream: they go through the network in chunks of `batch_size` and every chunk is one tracker launch over
+    the chunk's real frames (the padded copies never reach the tracker).
+
+    The constructor is Detector's plus ByteTracker's keywords (its `agnostic` is `track_agnostic` here: `agnostic` is the
+    NMS's).  conf_thres is the NMS threshold and defaults to low_thresh: the
+    second association needs the boxes below track_thresh, so a conf_thres above track_thresh is refused.  max_det rows per
+    frame reach the tracker."""
+
+    def __init__(self, net, anchor_info, image_size: int = 640, batch_size: int = 16, conf_thres: Optional[float] = None,
+                 iou_thres: float = 0.45, classes=None, agnostic: bool = False, multi_label: bool = False, max_det: int = 300,
+                 graphed: bool = False, eval_fused: Optional[bool] = None, streams: int = 1, capacity: int = 256,
+                 track_thresh: float = 0.5, low_thresh: float = 0.1, new_thresh: Optional[float] = None, match_thresh: float = 0.8,
+                 match_thresh_low: float = 0.5, match_thresh_new: float = 0.7, fuse_score: bool = True, track_agnostic: bool = True,
+                 track_buffer: int = 30):
+        conf = float(low_thresh) if conf_thres is None else float(conf_thres)
+        if conf > float(track_thresh):
+            raise ValueError(f"conf_thres {conf} above track_thresh {track_thresh}: no detection would reach the first association")
+        super().__init__(net, anchor_info, image_size, batch_size, conf, iou_thres, classes, agnostic, multi_label, max_det, graphed,
+                         eval_fused)
+        self.tracker = ByteTracker(streams, capacity, track_thresh, low_thresh, new_thresh, match_thresh, match_thresh_low,
+                                   match_thresh_new, fuse_score, track_agnostic, track_buffer, device=self.device)
+        self.streams = self.tracker.streams
+
+    def reset(self, stream: Optional[int] = None):
+        self.tracker.reset(stream)
+
+    @torch.no_grad()
+    def __call__(self, frames: Sequence[np.ndarray]) -> Tracks:
+        frames = list(frames)
+        if len(frames) != self.streams:
+            raise ValueError(f"{len(frames)} frames for {self.streams} streams: expected one frame per stream")
+        rows, counts = [], []
+        for n, out in self._chunks(frames):
+            rows.append(out.packed[:n]); counts.append(out.counts[:n])
+        return self.tracker.update((torch.cat(rows), torch.cat(counts)) if len(rows) > 1 else (rows[0], counts[0]))
+
+    @torch.no_grad()
+    def clip(self, frames: Sequence[np.ndarray], stream: int = 0) -> Tracks:
+        """consecutive frames of one stream -> Tracks with one entry per frame; the other streams are left alone"""
+        frames = list(frames)
+        if not 0 <= int(stream) < self.streams:
+            raise ValueError(f"stream {stream}: expected 0..{self.streams - 1}")
+        if not frames:
+            raise ValueError("clip: expected at least one frame")
+        parts = [self.tracker.update((out.packed[:n], out.counts[:n]), stream=int(stream)) for n, out in self._chunks(frames)]
+        return parts[0] if len(parts) == 1 else Tracks.concat(parts)
