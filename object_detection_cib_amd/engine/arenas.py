@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .freshness import freshness_key, track_data_edits
 from .graph import Graph, head_param
 
 
@@ -107,6 +108,7 @@ class ArenaMixin:
                 self.p_arena[o:o + k].copy_(p.detach().reshape(-1).to(device))
                 p.data = self.p_arena[o:o + k].view(p.shape)
                 p.grad = None
+                track_data_edits(p)
         # BN running statistics arena
         roff = 0
         self.rs_layout = {}
@@ -126,6 +128,10 @@ class ArenaMixin:
                 b = self.buffers[f"{u.name}.1.num_batches_tracked"]
                 self.nbt_arena[i] = b.to(device)
                 b.data = self.nbt_arena[i]
+        # what freshness_key() reads: the arenas and every tensor bound into them, held once (engine/freshness.py)
+        self._fresh_params = [self.p_arena] + [self.params[n] for n in layout]
+        self._fresh_stats = [self.rm_arena, self.rv_arena] + [self.buffers[f"{u.name}.1.{key}"] for u in exec_units
+                                                              for key in ("running_mean", "running_var")]
         # weight packs
         descs = []
         foff = doff = 0
@@ -225,12 +231,18 @@ class ArenaMixin:
         a = self.g_arena[self.g_cur] if arena is None else arena
         return a[o:o + k].view(self.params[name].shape)
 
-    def pack_weights(self):
+    def pack_weights(self, key=None):
+        """key: the caller's reading of freshness_key(), if it has one"""
         _lib.check(self.lib.kodhip_pack_weights(self.p_arena.data_ptr(), self.fpack.data_ptr(),
                                                 self.dpack.data_ptr(), self.pack_descs.data_ptr(),
                                                 self.pack_descs.shape[0], self.pack_blocks, self._stream()),
                    "pack_weights")
-        self._packed_version = self.param_version
+        self._packed_key = (key or self.freshness_key())[0]
+
+    def freshness_key(self):
+        """(parameter half, statistics half): moves whenever a parameter / a running statistic may have changed, whoever
+        changed it (engine/freshness.py).  The weight packs are keyed on the first half, the eval constants on both."""
+        return freshness_key(self.param_version, self.stats_version, self._fresh_params, self._fresh_stats)
 
     def _publish_grads(self):
         """Expose the arena slices as .grad (accumulating into an existing .grad like autograd would).  Under a freeze plan

@@ -68,7 +68,8 @@ class Engine(ArenaMixin, BufferMixin, ForwardMixin, BackwardMixin):
         self.bucket_bytes = int(self.opt.bucket_mb * (1 << 20))
         self._checked_shapes = set()   # local batch shapes already compared across the ranks (SyncBN, see forward)
         self._pending = []
-        self._packed_version = -1
+        self._packed_key = None        # parameter half of freshness_key() the weight packs were made from
+        self._fresh = None             # the last forward's reading of freshness_key()
         self.param_version = 0
         self.stats_version = 0         # bumped by every eager training forward (BatchNorm running statistics moved)
         self._eval_aff = None          # eval-mode BN constants of all units (flat), see _eval_affine_ptrs

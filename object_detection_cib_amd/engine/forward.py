@@ -29,7 +29,7 @@ class _ForwardPass:
         self.s = eng._stream()           # the stream the unit stages launch on (side_branch switches it)
         self.fp, self.pa = eng.fpack.data_ptr(), eng.p_arena.data_ptr()
         self.rm, self.rv = eng.rm_arena.data_ptr(), eng.rv_arena.data_ptr()
-        self.eval_aff = None if training else eng._eval_affine_ptrs()
+        self.eval_aff = None if training else eng._eval_affine_ptrs(eng._fresh)
         self.sync = sync = training and eng.sync_bn and eng.collectives
         if sync:
             eng._check_equal_local_batch(self.bs.shape)
@@ -327,10 +327,11 @@ class ForwardMixin:
             B, Cimg, H, W = x.shape
             assert Cimg == 3 and x.dtype == torch.float32 and x.is_contiguous() and x.device == self.device
             self.allocate(B, H, W)
-        if self._packed_version != self.param_version:
+        self._fresh = self.freshness_key()      # read once per forward; the eval constants below use the same reading
+        if self._packed_key != self._fresh[0]:
             # (round 6: the re-pack on a side stream beside the input's layout change measured 1.3 % SLOWER in the replayed
             # step - a second root node moves the forward chain's head to another hardware queue; LOG round 6)
-            self.pack_weights()
+            self.pack_weights(self._fresh)
         if not self.g.inputs and not image_ready:
             chk(self.lib.kodhip_nchw_to_nhwc4(x.data_ptr(), self.cur.act["image"].data_ptr(), B, 3, H, W, self._stream()),
                 "nchw_to_nhwc4")
@@ -372,15 +373,17 @@ class ForwardMixin:
             self._bn_eval_tables[key] = t
         return t, len(units)
 
-    def _eval_affine_ptrs(self):
+    def _eval_affine_ptrs(self, key=None):
         """Eval-mode BatchNorm constants of every unit (scale = gamma * rsqrt(running_var + eps), shift = beta -
         running_mean * scale) in ONE flat buffer, recomputed with five whole-network tensor ops only when parameters or
         running statistics changed - not per layer per forward (a validation epoch forwards many batches with frozen
         weights).  Kept apart from the training constants (st.aff), so an eval forward never disturbs a pending backward.
         Returns {unit name: (scale ptr, shift ptr)}."""
-        # keyed on the arenas' own version counters too: in-place edits that bypass the engine (EMA swap,
-        # reset_running_stats, a non-fused optimizer, a user-captured graph replay bumps nothing - see invalidate_eval_constants)
-        key = (self.param_version, self.stats_version, self.p_arena._version, self.rm_arena._version, self.rv_arena._version)
+        # keyed on the version counters of the arenas and of every tensor bound into them too (engine/freshness.py): in-place
+        # edits that bypass the engine - EMA swap, reset_running_stats, nn.init, a non-fused optimizer (a user-captured graph
+        # replay bumps nothing - see invalidate_eval_constants).  key: the caller's reading of freshness_key(), if it has one
+        if key is None:
+            key = self.freshness_key()
         if self._eval_aff is None:
             gi, bi, ri, off = [], [], [], 0
             self._eval_off = {}

@@ -253,9 +253,10 @@ class _GraphedEval:
 
     def _refresh(self):
         eng = self.eng
-        if eng._packed_version != eng.param_version:
-            eng.pack_weights()
-        eng._eval_affine_ptrs()
+        key = eng.freshness_key()
+        if eng._packed_key != key[0]:
+            eng.pack_weights(key)
+        eng._eval_affine_ptrs(key)
 
     @torch.no_grad()
     def capture(self, images: torch.Tensor):

@@ -57,8 +57,10 @@ def optimizer_state_dict(net, optimizer) -> Dict:
                 state[idx] = {"momentum_buffer": eng.m_arena[off:off + numel].view(params[n].shape).detach().clone().cpu()}
             ids.append(idx)
             idx += 1
-        pgs.append(dict(lr=float(g["lr"]), momentum=float(g["momentum"]), dampening=0, weight_decay=float(g["weight_decay"]),
-                        nesterov=True, maximize=False, foreach=None, differentiable=False, name=g["name"],
+        # (dampening / nesterov / maximize are the optimizer's own: a plain torch.optim.SGD that loads this steps the same way)
+        pgs.append(dict(lr=float(g["lr"]), momentum=float(g["momentum"]), dampening=g.get("dampening", 0),
+                        weight_decay=float(g["weight_decay"]), nesterov=bool(g.get("nesterov", True)),
+                        maximize=bool(g.get("maximize", False)), foreach=None, differentiable=False, name=g["name"],
                         initial_lr=float(g.get("initial_lr", g["lr"])), params=ids))
     return {"state": state, "param_groups": pgs}
 

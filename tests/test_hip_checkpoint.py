@@ -92,3 +92,43 @@ def test_lightning_ckpt_round_trip(tmp_path):
     opt2.load_state_dict(ck["optimizer_states"][0])          # torch validates group sizes / ids
     bufs = opt2.state_dict()["state"]
     assert len(bufs) == 189 and all(torch.isfinite(s["momentum_buffer"]).all() for s in bufs.values())
+
+    # ... by value: every momentum_buffer is the matching slice of the momentum arena, every network tensor the HIP one
+    eng = net.engine()
+    order = [n for names in optimizer_param_order(net) for n in names]
+    hip_params = dict(net.named_parameters())
+    moving = 0
+    for i, n in enumerate(order):
+        o, k = eng.layout[n]
+        want_buf = eng.m_arena[o:o + k].view(hip_params[n].shape).cpu()
+        assert torch.equal(bufs[i]["momentum_buffer"], want_buf), n
+        moving += int(want_buf.any())
+    print("momentum buffers with a non-zero entry:", moving, "of", len(order))
+    assert moving > len(order) // 2               # (the comparison is not zeros against zeros)
+    hip_sd = net.state_dict()
+    assert list(ref2.state_dict()) == list(hip_sd)
+    for k, v in ref2.state_dict().items():
+        assert torch.equal(v, hip_sd[k].cpu()), k
+    ids = [id(p) for g in opt2.param_groups for p in g["params"]]
+    ref2_params = dict(ref2.named_parameters())
+    assert ids == [id(ref2_params[n]) for n in order]                 # state index i <-> order[i] on the torch side too
+
+    # one more step on both sides from the same (HIP) gradients: torch.optim.SGD.step() against FusedSGD.step(), parameter
+    # by parameter within the bound of the first half
+    opt.zero_grad()
+    lr_ = loss(FeatureShape(width=size, height=size), net(x.cuda()), tuple(DetectionTarget(t.boxes, t.labels) for t in tg))
+    (2 * (lr_.localization + lr_.classification + lr_.objectness)).backward()
+    eng.wait_grads()
+    torch.cuda.synchronize()
+    for n, p in ref2_params.items():
+        p.grad = hip_params[n].grad.detach().clone().cpu()
+    opt2.step()
+    opt.step()
+    torch.cuda.synchronize()
+    worst = 0.0
+    for n, p in ref2_params.items():
+        pexp = p.detach()
+        err = (hip_params[n].detach().cpu() - pexp).abs().max().item()
+        worst = max(worst, err / (1e-6 + 1e-5 * pexp.abs().max().item()))
+        assert err <= 1e-6 + 1e-5 * pexp.abs().max().item(), (n, err)
+    print("step after the HIP-side checkpoint: worst error / bound", worst)
