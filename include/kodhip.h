@@ -387,6 +387,14 @@ int kodhip_compose_color(const void* pool, const void* descs, const void* biline
 int kodhip_val_prep_desc_bytes(void);
 int kodhip_val_prep_batch(const void* pool, const void* descs /* device [B] */, float* out_f32, void* out_pairs,
                           int B, int S, kodStream_t stream);
+/* kodhip_letterbox_batch: the same records and the same arithmetic, bit for bit (OpenCV's fixed-point INTER_LINEAR, padding
+ * 114, / 255.f, the copy path when nothing is resized), on an H x W canvas: a record's top / left are PadIfNeeded's centre
+ * position on that canvas (engine/rect.py rect_geometry; nh <= H and nw <= W are the caller's to hold).  out_f32 [B,3,H,W]
+ * (8-byte aligned) and / or out_pairs bf16 [B,H,W/2,8] (16-byte aligned), W even; the network takes multiples of 32.  One
+ * thread per pixel pair; every tap is one 4-byte load, so the pool must stay readable 1 byte behind its last image
+ * (ImagePool leaves 8).  With H = W = S the outputs are kodhip_val_prep_batch's. */
+int kodhip_letterbox_batch(const void* pool, const void* descs /* device [B] */, float* out_f32 /* or NULL */,
+                           void* out_pairs /* or NULL */, int B, int H, int W, kodStream_t stream);
 
 /* ---- evaluation post-process (kod/lightning/experiments/yv5_baseline/layers.py:55-155, exp.py:70-102;
  *      kod/core/nms.py:9-75 + torchvision.ops.nms) -------------------------------------------------- */

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..engine.rect import rect_batches, rect_geometry
 from .detection import DetectionTarget
 
 
@@ -260,14 +261,26 @@ class DeviceValPipeline:
         self.boxes, self.labels = list(boxes), list(labels)
         self._stager = _Stager(self.device)
 
-    def make_batch(self, batch_indices: Sequence[int], out_f32: bool = True, out_pairs: bool = False):
-        """Returns (images f32 [B,3,S,S] or None, pairs bf16 [B,S,S/2,8] or None, tuple of DetectionTarget)."""
+    def rect_batches(self, batch_size: int, sort: bool = True):
+        """The rectangular-validation plan of this pool (YOLOv5 val.py `rect`; engine/rect.py): [(indices, H, W)], the images
+        sorted by aspect ratio, in chunks of batch_size, each with its minimum-padding canvas - what
+        `make_batch(indices, canvas=(H, W))` takes."""
+        return rect_batches(self.pool.shapes, self.S, batch_size, sort)
+
+    def make_batch(self, batch_indices: Sequence[int], out_f32: bool = True, out_pairs: bool = False, canvas=None):
+        """Returns (images f32 [B,3,S,S] or None, pairs bf16 [B,S,S/2,8] or None, tuple of DetectionTarget).
+        canvas (H, W): the batch on that canvas instead of the S x S square ([B,3,H,W] / [B,H,W/2,8];
+        kodhip_letterbox_batch), the resize unchanged, images and targets centred on it.  Every canvas is an input shape of
+        its own to the network: a buffer set, and a capture where the validation forward is graphed."""
         B, S = len(batch_indices), self.S
+        H, W = (S, S) if canvas is None else (int(canvas[0]), int(canvas[1]))
         descs = np.zeros(B, dtype=VAL_DESC)
         targets = []
         for k, i in enumerate(batch_indices):
             h, w = self.pool.shapes[i]
-            nh, nw, top, left = letterbox_geometry(h, w, S)
+            nh, nw, top, left = letterbox_geometry(h, w, S) if canvas is None else rect_geometry(h, w, S, H, W)
+            if nh > H or nw > W:
+                raise ValueError(f"image {i}: {h} x {w} letterboxes to {nh} x {nw}, larger than the canvas {H} x {W}")
             d = descs[k]
             d["off"], d["h"], d["w"], d["nh"], d["nw"], d["top"], d["left"] = self.pool.offsets[i], h, w, nh, nw, top, left
             d["scale_x"], d["scale_y"] = 1.0 / (nw / float(w)), 1.0 / (nh / float(h))     # OpenCV: 1 / inv_scale
@@ -277,11 +290,14 @@ class DeviceValPipeline:
                 bb[:, [1, 3]] = bb[:, [1, 3]] / h * nh + top
             targets.append(DetectionTarget(torch.from_numpy(bb), torch.from_numpy(np.asarray(self.labels[i], dtype=np.int64))))
         d_dev = self._stager.upload(descs)
-        img = torch.empty((B, 3, S, S), dtype=torch.float32, device=self.device) if out_f32 else None
-        pairs = torch.empty((B, S, S // 2, 8), dtype=torch.bfloat16, device=self.device) if out_pairs else None
-        _lib.check(_lib.lib().kodhip_val_prep_batch(self.pool.data.data_ptr(), d_dev.data_ptr(),
-                                                    img.data_ptr() if out_f32 else None,
-                                                    pairs.data_ptr() if out_pairs else None, B, S,
-                                                    torch.cuda.current_stream().cuda_stream), "val_prep_batch")
+        img = torch.empty((B, 3, H, W), dtype=torch.float32, device=self.device) if out_f32 else None
+        pairs = torch.empty((B, H, W // 2, 8), dtype=torch.bfloat16, device=self.device) if out_pairs else None
+        args = (self.pool.data.data_ptr(), d_dev.data_ptr(), img.data_ptr() if out_f32 else None,
+                pairs.data_ptr() if out_pairs else None, B)
+        stream = torch.cuda.current_stream().cuda_stream
+        if canvas is None:
+            _lib.check(_lib.lib().kodhip_val_prep_batch(*args, S, stream), "val_prep_batch")
+        else:
+            _lib.check(_lib.lib().kodhip_letterbox_batch(*args, H, W, stream), "letterbox_batch")
         self._keep = d_dev
         return img, pairs, tuple(targets)

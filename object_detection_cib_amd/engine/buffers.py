@@ -87,8 +87,24 @@ class BufferSet:
 class BufferMixin:
     # ------------------------------------------------------------------ shape sets
     def pin_shape(self, B: int, H: int, W: int):
-        """A captured graph replays into the buffer set of this shape: keep it for the engine's lifetime."""
-        self._pinned.add((B, H, W))
+        """A captured graph replays into the buffer set of this shape: keep it until every pin is released (`unpin_shape`).
+        Pins are counted - a training step and several eval graphs may hold the same shape."""
+        key = (B, H, W)
+        self._pin_counts[key] = self._pin_counts.get(key, 0) + 1
+        self._pinned.add(key)
+
+    def unpin_shape(self, B: int, H: int, W: int):
+        """Release one pin of this shape (the graph that took it is gone).  With the last pin the set becomes an ordinary
+        one again: it stays until `allocate` drops it least-recently-used beyond KODHIP_MAX_SHAPE_SETS."""
+        key = (B, H, W)
+        n = self._pin_counts.get(key, 0)
+        if n < 1:
+            raise ValueError(f"unpin_shape{key}: the shape is not pinned")
+        if n == 1:
+            del self._pin_counts[key]
+            self._pinned.discard(key)
+        else:
+            self._pin_counts[key] = n - 1
 
     def allocate(self, B: int, H: int, W: int):
         """Make the buffer set of (B, H, W) current.  Sets are kept (a dict keyed by shape, least recently used first),

@@ -50,6 +50,7 @@ class Engine(ArenaMixin, BufferMixin, ForwardMixin, BackwardMixin):
         # shape (validation batch, partial last batch) must never free what a graph replays into
         self._sets: Dict[tuple, BufferSet] = {}   # shape -> set, least recently used first (the current one is last)
         self._pinned = set()          # shapes a captured graph depends on: never evicted
+        self._pin_counts: Dict[tuple, int] = {}   # how many graphs hold each of them (pin_shape / unpin_shape)
         self.max_shape_sets = self.opt.max_shape_sets
         self.training_ready = False
         self.bn_eps, self.bn_momentum = BN_EPS, BN_MOMENTUM     # the network's BatchNorm2d constants (set by the nn.Module that owns the engine)

@@ -14,6 +14,7 @@ run at device speed (bench.py measures exactly this replay).  What makes the ste
 """
 from __future__ import annotations
 
+from collections import OrderedDict
 from typing import Optional, Sequence
 
 import torch
@@ -243,6 +244,16 @@ class _GraphedEval:
         self.shape = FeatureShape(width=width, height=height)
         self.graph, self.det = None, None
         self._eval_fused = None           # EngineOptions.eval_fused the graph was captured with
+        self._held = []                   # the shapes capture() pinned, until release()
+
+    def release(self):
+        """Drop the captured graph and give back its pins (Engine.unpin_shape): the buffer sets become ordinary ones that
+        the engine may drop.  The caller makes sure that no replay is still running (GraphCache synchronises the stream);
+        a later call captures again."""
+        self.graph, self.det = None, None
+        for shp in self._held:
+            self.eng.unpin_shape(*shp)
+        self._held = []
 
     def _shapes(self):
         """the (B, H, W) buffer sets the graph bakes addresses of"""
@@ -261,8 +272,10 @@ class _GraphedEval:
     @torch.no_grad()
     def capture(self, images: torch.Tensor):
         eng = self.eng
-        for shp in self._shapes():
-            eng.pin_shape(*shp)
+        if not self._held:                # (a second capture() of the same object keeps its pins)
+            for shp in self._shapes():
+                eng.pin_shape(*shp)
+                self._held.append(shp)
         self.x.copy_(images)
         side = torch.cuda.Stream(device=eng.device)
         side.wait_stream(torch.cuda.current_stream())
@@ -334,3 +347,43 @@ class GraphedAugmentedForward(_GraphedEval):
 
     def _forward(self):
         return self._augmented(self.x, self.net, self.anchor_info)
+
+
+class GraphCache(OrderedDict):
+    """input shape (B, 3, H, W) -> captured eval forward, least recently used first, at most `max_graphs` of them.
+
+    A front end that sees changing input shapes (rectangular inference: one canvas per batch) would otherwise keep a graph,
+    a static input batch, a static output and up to three pinned engine buffer sets per shape for its lifetime.  `forward`
+    returns the shape's graph, building it when it is new; beyond `max_graphs` the least recently used one goes first: the
+    current stream is synchronised (its last replay and whatever read its output have finished), the graph is dropped and
+    its shapes are unpinned (`_GraphedEval.release`; pins are counted, so a shape that a training step or another graph
+    also holds stays pinned).  The trade-off: a shape that comes back after its eviction pays a buffer-set allocation and
+    a capture again, so `max_graphs` should cover the shapes of one pass over the data where memory allows."""
+
+    def __init__(self, max_graphs: int = 8):
+        super().__init__()
+        self.max_graphs = 1
+        self.resize(max_graphs)
+
+    def resize(self, max_graphs: int):
+        """a new bound; graphs beyond it go now, least recently used first"""
+        if int(max_graphs) < 1:
+            raise ValueError(f"max_graphs {max_graphs}: expected >= 1")
+        self.max_graphs = int(max_graphs)
+        self._evict(self.max_graphs)
+
+    def _evict(self, keep: int):
+        while len(self) > keep:
+            _, old = self.popitem(last=False)
+            torch.cuda.current_stream().synchronize()
+            old.release()
+
+    def forward(self, key, build):
+        """the graph of input shape `key`, now the most recently used; `build()` makes a missing one"""
+        g = self.get(key)
+        if g is not None:
+            self.move_to_end(key)
+            return g
+        self._evict(self.max_graphs - 1)
+        g = self[key] = build()
+        return g

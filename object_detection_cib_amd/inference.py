@@ -11,6 +11,9 @@ ONE NMS runs over the merged predictions.  `TiledDetector` is sliced inference f
 image is cut into overlapping tiles at its native resolution (engine/tiles.py, kodhip_tile_batch), every tile and the letterboxed
 whole image go through the network and kodhip_nms_ex, and one kodhip_merge_detections per image joins what the views found.
 `TrackedDetector` follows the boxes through a video: Detector, then ByteTrack on the device (core/tracking.py, kodhip_track_update).
+Rectangular mode (`Detector.rectangular()`, also AugmentedDetector's; `rect=True` on EnsembleDetector and TrackedDetector)
+letterboxes every chunk onto the smallest canvas of multiples of 32 that holds its images instead of the image_size square
+(engine/rect.py, kodhip_letterbox_batch).
 """
 from __future__ import annotations
 
@@ -24,19 +27,50 @@ from .core.nms import _key_cap, _workspace, fuse_detections, merge_detections, n
 from .core.tracking import ByteTracker, Tracks
 from .core.types import FeatureShape
 from .data.device_pipeline import VAL_DESC, ImagePool, _Stager, letterbox_geometry
+from .engine.graphed import GraphCache
+from .engine.rect import rect_canvas, rect_geometry, rect_order
 from .engine.tiles import tile_plan
 
 
-def letterbox_table(shapes: Sequence[Sequence[int]], image_size: int, first_index: int = 0):
+def _check_images(images):
+    for i, im in enumerate(images):
+        if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
+            raise ValueError(f"image {i}: expected an HWC uint8 array with 3 channels")
+
+
+def _chunk_tables(shapes, image_size: int, batch_size: int, rect: bool):
+    """[(canvas (H, W), VAL_DESC records, KodLetterbox rows)] of consecutive chunks of batch_size images; rect: every chunk
+    on the `rect_canvas` of its own images.  Host arithmetic only: a bad image raises before anything is uploaded."""
+    tables = []
+    for i in range(0, len(shapes), batch_size):
+        part = shapes[i:i + batch_size]
+        descs, boxes = letterbox_table(part, image_size, i)
+        canvas = (image_size, image_size)
+        if rect:
+            canvas = rect_canvas(part, image_size)
+            descs, boxes = letterbox_table(part, image_size, i, canvas)
+        tables.append((canvas, descs, boxes))
+    return tables
+
+
+def letterbox_table(shapes: Sequence[Sequence[int]], image_size: int, first_index: int = 0, canvas=None):
     """(h, w) per image -> (VAL_DESC records without pool offsets, KodLetterbox rows float32 [n, 6]): the geometry of the
-    validation letterbox and its inverse - left, top, fp32(w / nw), fp32(h / nh), w, h, the quotients formed in double."""
+    validation letterbox and its inverse - left, top, fp32(w / nw), fp32(h / nh), w, h, the quotients formed in double.
+    canvas (H, W): the same resize centred on an H x W canvas (engine/rect.py), top / left relative to it; None: the
+    image_size square."""
     descs = np.zeros(len(shapes), dtype=VAL_DESC)
     boxes = np.zeros((len(shapes), 6), dtype=np.float32)
     for k, (h, w) in enumerate(shapes):
         h, w = int(h), int(w)
         if h < 1 or w < 1:
             raise ValueError(f"image {first_index + k}: empty ({h} x {w})")
-        nh, nw, top, left = letterbox_geometry(h, w, image_size)
+        if canvas is None:
+            nh, nw, top, left = letterbox_geometry(h, w, image_size)
+        else:
+            nh, nw, top, left = rect_geometry(h, w, image_size, int(canvas[0]), int(canvas[1]))
+            if nh > canvas[0] or nw > canvas[1]:
+                raise ValueError(f"image {first_index + k}: {h} x {w} letterboxes to {nh} x {nw}, larger than the canvas "
+                                 f"{int(canvas[0])} x {int(canvas[1])}")
         if nh < 1 or nw < 1:
             raise ValueError(f"image {first_index + k}: {h} x {w} letterboxes to {nh} x {nw} at image_size {image_size}")
         d = descs[k]
@@ -56,9 +90,20 @@ class Detector:
     Images are processed in chunks of `batch_size`; a final partial chunk is padded by repeating its last image, so one
     engine shape set serves every call.
 
+    `det.rectangular()` switches to detect.py's minimum-padding letterbox (`rect`, False by default; the constructor's
+    argument list is the one it always had): every chunk is letterboxed onto the smallest canvas of multiples of 32
+    that holds its images (engine/rect.py rect_canvas; kodhip_letterbox_batch), so a chunk of 16:9 frames is 384 x 640 at
+    image_size 640, 0.60 of the square's pixels.  A call sorts its images by aspect ratio first (rect_order) and returns the
+    results in the caller's order.  Every distinct canvas is an input shape of its own: the engine builds a buffer set for it
+    (KODHIP_MAX_SHAPE_SETS are kept; sorted chunks visit each shape in one run, so each is allocated once per call), and
+    with graphed=True it is captured on first use; at most `max_graphs` captured forwards are kept, least recently used
+    first (engine/graphed.GraphCache) - a shape that comes back after its eviction is allocated and captured again.  The
+    network sees the grey border closer to the content than it did in training; what that does to accuracy is not measured.
+
     `augment` (class attribute, False here; True in AugmentedDetector) routes the forward through test-time augmentation."""
 
     augment = False
+    rect = False                  # set by rectangular()
 
     def __init__(self, net, anchor_info, image_size: int = 640, batch_size: int = 16, conf_thres: float = 0.25,
                  iou_thres: float = 0.45, classes=None, agnostic: bool = False, multi_label: bool = False, max_det: int = 300,
@@ -79,17 +124,29 @@ class Detector:
         self.graphed, self.eval_fused = bool(graphed), eval_fused
         self.device = next(net.parameters()).device
         self._stager = _Stager(self.device)
-        self._geval = {}              # input shape -> GraphedEvalForward (augment: GraphedAugmentedForward)
+        # input shape -> GraphedEvalForward (augment: GraphedAugmentedForward), at most max_graphs (8 until rectangular() says
+        # otherwise), least recently used first
+        self._geval = GraphCache()
+
+    def rectangular(self, rect: bool = True, max_graphs: Optional[int] = None):
+        """Switch the minimum-padding letterbox on (or off) and, with max_graphs, bound the captured forwards that changing
+        canvases may leave behind; returns self: `det = Detector(net, anchor_info, graphed=True).rectangular(max_graphs=8)`."""
+        if max_graphs is not None:
+            self._geval.resize(max_graphs)
+        self.rect = bool(rect)
+        return self
+
+    @property
+    def max_graphs(self) -> int:
+        return self._geval.max_graphs
 
     def _forward(self, x: torch.Tensor) -> torch.Tensor:
         """decoded detections [B, rows, 5 + nc] of a letterboxed batch"""
         if self.graphed:
             from .engine.graphed import GraphedAugmentedForward, GraphedEvalForward
             key = tuple(x.shape)
-            if key not in self._geval:
-                cls = GraphedAugmentedForward if self.augment else GraphedEvalForward
-                self._geval[key] = cls(self.net, self.anchor_info, key[0], key[2], key[3])
-            return self._geval[key](x)
+            cls = GraphedAugmentedForward if self.augment else GraphedEvalForward
+            return self._geval.forward(key, lambda: cls(self.net, self.anchor_info, key[0], key[2], key[3]))(x)
         from .lightning.experiments.yv5_baseline.layers import get_detections, get_detections_augmented
         if self.augment:           # (the engine's eval forward, called directly: no module mode is touched)
             return get_detections_augmented(x, self.net, self.anchor_info)
@@ -107,36 +164,61 @@ class Detector:
         """images in chunks of batch_size through letterbox, forward and NMS -> (real images of the chunk, the padded chunk's
         PackedDetections), chunk after chunk"""
         images = list(images)
-        for i, im in enumerate(images):
-            if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
-                raise ValueError(f"image {i}: expected an HWC uint8 array with 3 channels")
+        _check_images(images)
         # (all geometry first: a bad image raises before anything is uploaded or launched)
-        tables = [letterbox_table([im.shape[:2] for im in images[i:i + self.B]], self.S, i) for i in range(0, len(images), self.B)]
+        tables = _chunk_tables([im.shape[:2] for im in images], self.S, self.B, self.rect)
         if self.eval_fused is not None:
             self.net.fuse_eval(self.eval_fused)
-        B, S = self.B, self.S
-        for c, (descs, boxes) in enumerate(tables):
-            chunk = images[c * B:(c + 1) * B]
-            n = len(chunk)
-            pool = ImagePool(chunk, self.device)
-            descs["off"] = pool.offsets
-            if n < B:              # pad with the last descriptor: the batch keeps its shape, the copies are dropped below
-                descs = np.concatenate((descs, np.repeat(descs[-1:], B - n)))
-                boxes = np.concatenate((boxes, np.repeat(boxes[-1:], B - n, axis=0)))
-            d_dev = self._stager.upload(descs)
-            x = torch.empty((B, 3, S, S), dtype=torch.float32, device=self.device)
-            _lib.check(_lib.lib().kodhip_val_prep_batch(pool.data.data_ptr(), d_dev.data_ptr(), x.data_ptr(), None, B, S,
-                                                        torch.cuda.current_stream().cuda_stream), "val_prep_batch")
+        for c, (canvas, descs, boxes) in enumerate(tables):
+            chunk = images[c * self.B:(c + 1) * self.B]
+            x, boxes = self._letterbox(chunk, canvas, descs, boxes)
             det = self._forward(x)
             out = non_max_suppression(det, self.conf_thres, self.iou_thres, self.classes, agnostic=self.agnostic,
                                       multi_label=self.multi_label, max_det=self.max_det, letterbox=boxes)
-            yield n, out
+            yield len(chunk), out
+
+    def _letterbox(self, chunk, canvas, descs, boxes):
+        """one chunk on the device: the upload of its images and the letterbox launch -> (x fp32 [B, 3, H, W] on `canvas`,
+        the KodLetterbox rows of the padded chunk)"""
+        B, (H, W), n = self.B, canvas, len(chunk)
+        pool = ImagePool(chunk, self.device)
+        descs["off"] = pool.offsets
+        if n < B:              # pad with the last descriptor: the batch keeps its shape, the copies are dropped by the caller
+            descs = np.concatenate((descs, np.repeat(descs[-1:], B - n)))
+            boxes = np.concatenate((boxes, np.repeat(boxes[-1:], B - n, axis=0)))
+        d_dev = self._stager.upload(descs)
+        x = torch.empty((B, 3, H, W), dtype=torch.float32, device=self.device)
+        stream = torch.cuda.current_stream().cuda_stream
+        if self.rect:
+            _lib.check(_lib.lib().kodhip_letterbox_batch(pool.data.data_ptr(), d_dev.data_ptr(), x.data_ptr(), None, B, H, W, stream),
+                       "letterbox_batch")
+        else:
+            _lib.check(_lib.lib().kodhip_val_prep_batch(pool.data.data_ptr(), d_dev.data_ptr(), x.data_ptr(), None, B, H, stream),
+                       "val_prep_batch")
+        return x, boxes
+
+    def _order(self, images):
+        """rect: the images' positions sorted by aspect ratio (every chunk then holds alike shapes), after the checks a call
+        in the caller's order would make; otherwise None"""
+        if not self.rect or len(images) < 2:
+            return None
+        _check_images(images)
+        shapes = [im.shape[:2] for im in images]
+        letterbox_table(shapes, self.S)                       # (its ValueErrors name the caller's index)
+        return rect_order(shapes).tolist()
 
     @torch.no_grad()
     def __call__(self, images: Sequence[np.ndarray]) -> List[torch.Tensor]:
+        images = list(images)
+        order = self._order(images)
         results = []
-        for n, out in self._chunks(images):
+        for n, out in self._chunks(images if order is None else [images[k] for k in order]):
             results.extend(out[:n])
+        if order is not None:
+            back = [None] * len(images)
+            for k, r in zip(order, results):
+                back[k] = r
+            results = back
         return results
 
 
@@ -160,7 +242,8 @@ class EnsembleDetector:
     are one or more networks on one device with the same class count - widths, depths and parameters may differ;
     `anchor_info` is one LayerwiseAnchorInfo for all of them or one per network.  Validation, letterboxing and chunk padding
     happen once per chunk, every member's forward reads the same input tensor (graphed=True: one GraphedEvalForward per
-    member and input shape; eval_fused is handed to every member).
+    member and input shape; eval_fused is handed to every member).  rect / max_graphs are `Detector.rectangular`'s: every chunk
+    on its own minimum-padding canvas, the call's images sorted by aspect ratio, at most max_graphs captured forwards per member.
 
     merge "wbf" (default): each member's detections go through non_max_suppression with the detector's options and the
     letterbox, and ONE weighted boxes fusion per chunk (core.nms.fuse_detections: `weights` per member, `fuse_thres`,
@@ -173,7 +256,7 @@ class EnsembleDetector:
     def __init__(self, nets, anchor_info, image_size: int = 640, batch_size: int = 16, conf_thres: float = 0.25,
                  iou_thres: float = 0.45, classes=None, agnostic: bool = False, multi_label: bool = False, max_det: int = 300,
                  graphed: bool = False, eval_fused: Optional[bool] = None, merge: str = "wbf", weights=None,
-                 fuse_thres: float = 0.55):
+                 fuse_thres: float = 0.55, rect: bool = False, max_graphs: int = 8):
         nets = list(nets)
         if not nets:
             raise ValueError("nets: expected at least one network")
@@ -198,7 +281,7 @@ class EnsembleDetector:
             raise ValueError(f"fuse_thres {fuse_thres} below iou_thres {iou_thres}: one member's surviving boxes could fuse with each other")
         # (Detector's own checks: image_size, batch_size, max_det, a GPU)
         self.members = [Detector(net, info, image_size, batch_size, conf_thres, iou_thres, classes, agnostic, multi_label, max_det,
-                                 graphed, eval_fused) for net, info in zip(nets, infos)]
+                                 graphed, eval_fused).rectangular(rect, max_graphs) for net, info in zip(nets, infos)]
         first = self.members[0]
         if any(m.device != first.device for m in self.members):
             raise ValueError("nets: expected every network on the same device")
@@ -208,35 +291,29 @@ class EnsembleDetector:
         self.S, self.B, self.device = first.S, first.B, first.device
         self.conf_thres, self.iou_thres, self.classes = conf_thres, iou_thres, classes
         self.agnostic, self.multi_label, self.max_det = bool(agnostic), bool(multi_label), int(max_det)
-        self.graphed, self.eval_fused = bool(graphed), eval_fused
+        self.graphed, self.eval_fused, self.rect = bool(graphed), eval_fused, bool(rect)
         self.merge, self.weights, self.fuse_thres = merge, w, float(fuse_thres)
         self._stager = first._stager
 
     @torch.no_grad()
     def __call__(self, images: Sequence[np.ndarray]) -> List[torch.Tensor]:
         images = list(images)
-        for i, im in enumerate(images):
-            if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
-                raise ValueError(f"image {i}: expected an HWC uint8 array with 3 channels")
-        tables = [letterbox_table([im.shape[:2] for im in images[i:i + self.B]], self.S, i) for i in range(0, len(images), self.B)]
+        _check_images(images)
+        first = self.members[0]
+        order = first._order(images)                        # rect: sorted by aspect ratio, as Detector does
+        if order is not None:
+            images = [images[k] for k in order]
+        tables = _chunk_tables([im.shape[:2] for im in images], self.S, self.B, self.rect)
         if self.eval_fused is not None:
             for m in self.members:
                 m.net.fuse_eval(self.eval_fused)
-        B, S, M = self.B, self.S, len(self.members)
+        B, M = self.B, len(self.members)
         nms = dict(agnostic=self.agnostic, multi_label=self.multi_label, max_det=self.max_det)
         results = []
-        for c, (descs, boxes) in enumerate(tables):
+        for c, (canvas, descs, boxes) in enumerate(tables):
             chunk = images[c * B:(c + 1) * B]
             n = len(chunk)
-            pool = ImagePool(chunk, self.device)
-            descs["off"] = pool.offsets
-            if n < B:              # pad with the last descriptor, as Detector does
-                descs = np.concatenate((descs, np.repeat(descs[-1:], B - n)))
-                boxes = np.concatenate((boxes, np.repeat(boxes[-1:], B - n, axis=0)))
-            d_dev = self._stager.upload(descs)
-            x = torch.empty((B, 3, S, S), dtype=torch.float32, device=self.device)
-            _lib.check(_lib.lib().kodhip_val_prep_batch(pool.data.data_ptr(), d_dev.data_ptr(), x.data_ptr(), None, B, S,
-                                                        torch.cuda.current_stream().cuda_stream), "val_prep_batch")
+            x, boxes = first._letterbox(chunk, canvas, descs, boxes)      # (padded with the last descriptor, as Detector does)
             dets = [m._forward(x) for m in self.members]
             nc = {int(d.shape[2]) - 5 for d in dets}
             if len(nc) != 1:
@@ -255,6 +332,11 @@ class EnsembleDetector:
                     out = fuse_detections(rows, counts, np.arange(B + 1) * M, np.tile(self.weights, B), thres=self.fuse_thres,
                                           agnostic=self.agnostic, max_det=self.max_det)
             results.extend(out[:n])
+        if order is not None:
+            back = [None] * len(images)
+            for k, r in zip(order, results):
+                back[k] = r
+            results = back
         return results
 
 
@@ -292,14 +374,17 @@ class TiledDetector(Detector):
 
     The views of all images of a call form one stream of slots, processed in chunks of `batch_size` (the final chunk is padded
     by repeating its last slot: one engine shape set, one GraphedEvalForward); every chunk's NMS writes into call-wide buffers
-    on the device, and the host sees nothing before the merge's counts."""
+    on the device, and the host sees nothing before the merge's counts.  There is no rectangular mode: tiles are full squares
+    by construction and the full view is batched with them, so rect=True is refused."""
 
     def __init__(self, net, anchor_info, image_size: int = 640, batch_size: int = 16, overlap: float = 0.2, full_view: bool = True,
                  merge: str = "nmm", merge_metric: str = "ios", merge_thres: float = 0.5, tile_max_det: int = 300,
                  conf_thres: float = 0.25, iou_thres: float = 0.45, classes=None, agnostic: bool = False, multi_label: bool = False,
-                 max_det: int = 300, graphed: bool = False, eval_fused: Optional[bool] = None):
+                 max_det: int = 300, graphed: bool = False, eval_fused: Optional[bool] = None, rect: bool = False,
+                 max_graphs: int = 8):
         super().__init__(net, anchor_info, image_size, batch_size, conf_thres, iou_thres, classes, agnostic, multi_label, max_det,
                          graphed, eval_fused)
+        self.rectangular(rect, max_graphs)
         if merge not in ("nmm", "nms"):
             raise ValueError(f"merge {merge!r}: expected 'nmm' or 'nms'")
         if merge_metric not in ("ios", "iou"):
@@ -313,6 +398,12 @@ class TiledDetector(Detector):
         self.overlap, self.full_view = float(overlap), bool(full_view)
         self.merge, self.merge_metric, self.merge_thres = merge, merge_metric, float(merge_thres)
         self.tile_max_det = int(tile_max_det)
+
+    def rectangular(self, rect: bool = True, max_graphs: Optional[int] = None):
+        if rect:
+            raise ValueError("rect=True: TiledDetector has no rectangular mode - tiles are full image_size squares by "
+                             "construction, and the full view is batched with them")
+        return super().rectangular(False, max_graphs)
 
     def plans(self, shapes: Sequence[Sequence[int]]):
         """the tile plan of each (h, w); raises what a call with such images would raise"""
@@ -396,19 +487,21 @@ class TrackedDetector(Detector):
     The constructor is Detector's plus ByteTracker's keywords (its `agnostic` is `track_agnostic` here: `agnostic` is the
     NMS's).  conf_thres is the NMS threshold and defaults to low_thresh: the
     second association needs the boxes below track_thresh, so a conf_thres above track_thresh is refused.  max_det rows per
-    frame reach the tracker."""
+    frame reach the tracker.  rect=True (`Detector.rectangular`) never reorders here: stream s stays at index s and a clip's frames stay in
+    time order; the frames of one video have one size and so share one canvas, one engine shape and one captured graph."""
 
     def __init__(self, net, anchor_info, image_size: int = 640, batch_size: int = 16, conf_thres: Optional[float] = None,
                  iou_thres: float = 0.45, classes=None, agnostic: bool = False, multi_label: bool = False, max_det: int = 300,
                  graphed: bool = False, eval_fused: Optional[bool] = None, streams: int = 1, capacity: int = 256,
                  track_thresh: float = 0.5, low_thresh: float = 0.1, new_thresh: Optional[float] = None, match_thresh: float = 0.8,
                  match_thresh_low: float = 0.5, match_thresh_new: float = 0.7, fuse_score: bool = True, track_agnostic: bool = True,
-                 track_buffer: int = 30):
+                 track_buffer: int = 30, rect: bool = False, max_graphs: int = 8):
         conf = float(low_thresh) if conf_thres is None else float(conf_thres)
         if conf > float(track_thresh):
             raise ValueError(f"conf_thres {conf} above track_thresh {track_thresh}: no detection would reach the first association")
         super().__init__(net, anchor_info, image_size, batch_size, conf, iou_thres, classes, agnostic, multi_label, max_det, graphed,
                          eval_fused)
+        self.rectangular(rect, max_graphs)
         self.tracker = ByteTracker(streams, capacity, track_thresh, low_thresh, new_thresh, match_thresh, match_thresh_low,
                                    match_thresh_new, fuse_score, track_agnostic, track_buffer, device=self.device)
         self.streams = self.tracker.streams

@@ -48,7 +48,11 @@ class DefaultYolov5Experiment:
     lr_scheduler default to the reference's configs (configs/nn/optimizers/smart_sgd.yaml, schedulers/linear.yaml).
     val_augment=True: validation_step runs YOLOv5's test-time augmentation (val.py --augment) - three views of the batch, one
     NMS over the merged predictions.  The merged tensor has 45147 rows at 640 px against 25200, so the NMS key workspace
-    roughly doubles: at nc = 80, 45147 * 80 keys need a 4 Mi-key capacity per image, against 2 Mi without it."""
+    roughly doubles: at nc = 80, 45147 * 80 keys need a 4 Mi-key capacity per image, against 2 Mi without it.
+    val_max_graphs: with graphed=True validation_step keeps one captured forward per input shape, at most this many, least
+    recently used first (engine/graphed.GraphCache) - rectangular validation batches (DeviceValPipeline.rect_batches +
+    make_batch(canvas=...)) bring one shape per canvas; a shape beyond the bound costs a buffer-set allocation and a capture
+    again when it comes back."""
 
     def __init__(self, net, loss, anchor_info: LayerwiseAnchorInfo, smart_optimizer: Optional[SmartOptimizer] = None,
                  lr_scheduler: Optional[Callable] = None,
@@ -57,7 +61,8 @@ class DefaultYolov5Experiment:
                  graphed: bool = False, max_targets: int = 4096, world_size: int = 1,
                  gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
                  eval_fused: Optional[bool] = None, val_confusion: bool = False, val_confusion_conf: float = 0.25,
-                 val_confusion_iou: float = 0.45, val_augment: bool = False, val_metrics: bool = False):
+                 val_confusion_iou: float = 0.45, val_augment: bool = False, val_metrics: bool = False,
+                 val_max_graphs: int = 8):
         if gradient_clip_algorithm not in CLIP_ALGORITHMS:
             raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected one of {CLIP_ALGORITHMS}")
         # Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm): handed to the FusedSGD / the captured step
@@ -78,7 +83,10 @@ class DefaultYolov5Experiment:
         # graphed=True: the optimisation step is captured once as a hipGraph (engine/graphed.py) and replayed - same
         # arithmetic, no per-launch Python; batches must keep one shape and at most max_targets boxes
         self.graphed, self.max_targets, self._gstep = graphed, max_targets, None
-        self._geval = {}              # input shape -> GraphedEvalForward
+        # input shape -> GraphedEvalForward, at most val_max_graphs of them, least recently used first (rectangular
+        # validation batches bring one shape per canvas; a shape beyond the bound is captured again when it comes back)
+        from ....engine.graphed import GraphCache
+        self._geval = GraphCache(val_max_graphs)
         # validation forwards with BatchNorm + activation in the conv epilogue (Yolov5Network.fuse_eval); None leaves the
         # engine's option (EngineOptions.eval_fused / KODHIP_EVAL_FUSED) alone
         self.eval_fused = eval_fused
@@ -152,10 +160,9 @@ class DefaultYolov5Experiment:
         if self.graphed:          # eval forward + decode replayed as one hipGraph per input shape (engine/graphed.py)
             from ....engine.graphed import GraphedAugmentedForward, GraphedEvalForward
             key = tuple(images.shape)
-            if key not in self._geval:
-                cls = GraphedAugmentedForward if self.val_augment else GraphedEvalForward
-                self._geval[key] = cls(self.net, self.anchor_info, key[0], key[2], key[3])
-            det = self._geval[key](images if images.dtype == torch.float32 else images.float())
+            cls = GraphedAugmentedForward if self.val_augment else GraphedEvalForward
+            gf = self._geval.forward(key, lambda: cls(self.net, self.anchor_info, key[0], key[2], key[3]))
+            det = gf(images if images.dtype == torch.float32 else images.float())
             return targets, non_max_suppression(det, self.val_nms_conf_threshold, self.val_nms_iou_threshold)
         if self.val_augment:      # (the engine's eval forward, called directly: no module mode is touched)
             x = (images if images.dtype == torch.float32 else images.float()).contiguous()
