@@ -395,6 +395,20 @@ int kodhip_val_prep_batch(const void* pool, const void* descs /* device [B] */, 
  * (ImagePool leaves 8).  With H = W = S the outputs are kodhip_val_prep_batch's. */
 int kodhip_letterbox_batch(const void* pool, const void* descs /* device [B] */, float* out_f32 /* or NULL */,
                            void* out_pairs /* or NULL */, int B, int H, int W, kodStream_t stream);
+/* kodhip_letterbox_frames: kodhip_letterbox_batch for video frames that are read WHERE THEY LIE (csrc/video.hip): no pool, no
+ * intermediate RGB image.  descs: device [B] records of kodhip_frame_desc_bytes() bytes (data/frames.py FRAME_DESC): three
+ * plane addresses (64-bit device addresses), pitch of plane 0 and of planes 1 / 2 in bytes (any value >= the row's bytes),
+ * format (0 RGB24, 1 BGR24: packed, 3 B / pixel; 2 NV12: Y plane + interleaved UV plane; 3 I420: Y, U, V planes; 4:2:0 frames
+ * have even h and w), then h, w, nh, nw, top, left, scale_x, scale_y as in kodhip_letterbox_batch's records, then six ints
+ * yoff, CY, CVR, CVG, CUG, CUB: OpenCV's 20-bit fixed-point 4:2:0 conversion, y = max(0, Y - yoff) * CY + 2^19,
+ * R = sat8((y + CVR (V-128)) >> 20), G = sat8((y + CVG (V-128) + CUG (U-128)) >> 20), B = sat8((y + CUB (U-128)) >> 20), chroma
+ * sample (r >> 1, c >> 1) for pixel (r, c).  Every bilinear tap is converted to u8 RGB first, so both outputs equal, bit for
+ * bit, kodhip_letterbox_batch's on the RGB image the conversion of the whole frame gives.  Only bytes inside a frame's rows are
+ * read (byte / 2-byte loads; nothing depends on the alignment of an address or a pitch).  B <= 65535, W even, H * W <= 2^30,
+ * out_f32 8-byte and out_pairs 16-byte aligned; the arguments are checked before the launch. */
+int kodhip_frame_desc_bytes(void);
+int kodhip_letterbox_frames(const void* descs /* device [B] */, float* out_f32 /* [B,3,H,W] or NULL */,
+                            void* out_pairs /* bf16 [B,H,W/2,8] or NULL */, int B, int H, int W, kodStream_t stream);
 
 /* ---- evaluation post-process (kod/lightning/experiments/yv5_baseline/layers.py:55-155, exp.py:70-102;
  *      kod/core/nms.py:9-75 + torchvision.ops.nms) -------------------------------------------------- */

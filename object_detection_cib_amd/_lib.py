@@ -125,6 +125,8 @@ SIGNATURES = {
     "kodhip_val_prep_desc_bytes": (i32, []),
     "kodhip_val_prep_batch": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "kodhip_letterbox_batch": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    "kodhip_frame_desc_bytes": (i32, []),
+    "kodhip_letterbox_frames": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "kodhip_decode": (i32, [C.POINTER(KodDecodeLevel), vp, i32, i32, i32, vp]),
     "kodhip_nms": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, f32, vp]),
     "kodhip_tta_view": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]),

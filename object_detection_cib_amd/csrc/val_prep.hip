@@ -9,7 +9,7 @@
 // weights, intermediate rows in int32, dst = ((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2.  The geometry (new
 // size, pads, the two double-precision scales) is computed on the host exactly as the libraries do
 // (data/device_pipeline.py) and passed per sample.
-#include "kodhip_common.h"
+#include "kodhip_resize.h"      // sat16, lin_coeff (shared with video.hip)
 
 namespace {
 
@@ -20,24 +20,6 @@ struct ValDesc {
   int top, left;            // PadIfNeeded offsets
   double scale_x, scale_y;  // source / destination (1 / inv_scale as OpenCV computes it)
 };
-
-__device__ __forceinline__ int sat16(float v) {
-  int r = __float2int_rn(v);
-  return r < -32768 ? -32768 : (r > 32767 ? 32767 : r);
-}
-
-// left source index + 11-bit weights of destination index d (resize.cpp, INTER_LINEAR)
-__device__ __forceinline__ void lin_coeff(int d, double scale, int n_src, bool clamp_edges, int& s, int& w0, int& w1) {
-  float f = (float)(((double)d + 0.5) * scale - 0.5);
-  s = (int)floorf(f);
-  f -= (float)s;
-  if (clamp_edges) {        // horizontal: x < 0 and x >= width-1 collapse to one tap; vertical clamps the two rows instead
-    if (s < 0) { s = 0; f = 0.f; }
-    if (s >= n_src - 1) { s = n_src - 1; f = 0.f; }
-  }
-  w0 = sat16((1.f - f) * 2048.f);
-  w1 = sat16(f * 2048.f);
-}
 
 // grid: (ceil(S*S/256), B)
 __global__ __launch_bounds__(256) void val_prep_kernel(const unsigned char* pool, const ValDesc* descs, float* out_f32,

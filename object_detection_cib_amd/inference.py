@@ -14,6 +14,9 @@ whole image go through the network and kodhip_nms_ex, and one kodhip_merge_detec
 Rectangular mode (`Detector.rectangular()`, also AugmentedDetector's; `rect=True` on EnsembleDetector and TrackedDetector)
 letterboxes every chunk onto the smallest canvas of multiples of 32 that holds its images instead of the image_size square
 (engine/rect.py, kodhip_letterbox_batch).
+Every front end but TiledDetector also takes `Frame` items (data/frames.py): video frames that are already on the device - packed
+RGB / BGR with a row pitch, NV12 surfaces, I420 planes - or host NV12 / I420 arrays; a call that holds one goes through
+kodhip_letterbox_frames (csrc/video.hip), which reads the frames where they lie.  A call of numpy images only is untouched.
 """
 from __future__ import annotations
 
@@ -27,15 +30,24 @@ from .core.nms import _key_cap, _workspace, fuse_detections, merge_detections, n
 from .core.tracking import ByteTracker, Tracks
 from .core.types import FeatureShape
 from .data.device_pipeline import VAL_DESC, ImagePool, _Stager, letterbox_geometry
+from .data.frames import FRAME_DESC, Frame, frame_table, upload_frames, wrap_frames
 from .engine.graphed import GraphCache
 from .engine.rect import rect_canvas, rect_geometry, rect_order
 from .engine.tiles import tile_plan
 
 
-def _check_images(images):
+def _check_images(images, device=None):
+    """every item a numpy HWC uint8 image or a `Frame` (data/frames.py: checked by itself; its planes in host memory or on
+    `device`)"""
     for i, im in enumerate(images):
-        if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
+        if isinstance(im, Frame):
+            im.check(i, device)
+        elif not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
             raise ValueError(f"image {i}: expected an HWC uint8 array with 3 channels")
+
+
+def _has_frames(images) -> bool:
+    return any(isinstance(im, Frame) for im in images)
 
 
 def _chunk_tables(shapes, image_size: int, batch_size: int, rect: bool):
@@ -83,8 +95,9 @@ def letterbox_table(shapes: Sequence[Sequence[int]], image_size: int, first_inde
 class Detector:
     """det = Detector(net, anchor_info, image_size=640, ...); results = det(images)
 
-    images: a sequence of HWC uint8 arrays (3 channels) of any sizes.  results: one [n, 6] tensor per image, (x1, y1, x2, y2,
-    score, class) in that image's own pixels, n <= max_det, best score first.  conf_thres / iou_thres / classes / agnostic
+    images: a sequence of HWC uint8 arrays (3 channels) of any sizes, or of `Frame`s (data/frames.py: frames on the device in
+    RGB / BGR / NV12 / I420, host NV12 / I420), or a mix - one Frame sends the whole call through kodhip_letterbox_frames.
+    results: one [n, 6] tensor per image, (x1, y1, x2, y2, score, class) in that image's own pixels, n <= max_det, best score first.  conf_thres / iou_thres / classes / agnostic
     / multi_label / max_det are detect.py's arguments (non_max_suppression's keywords).  graphed=True replays the eval
     forward + decode as a hipGraph (GraphedEvalForward); eval_fused is handed to `net.fuse_eval` (None: left alone).
     Images are processed in chunks of `batch_size`; a final partial chunk is padded by repeating its last image, so one
@@ -104,6 +117,7 @@ class Detector:
 
     augment = False
     rect = False                  # set by rectangular()
+    _frame_stager = None          # pinned ring for the planes of host Frames, made on first use
 
     def __init__(self, net, anchor_info, image_size: int = 640, batch_size: int = 16, conf_thres: float = 0.25,
                  iou_thres: float = 0.45, classes=None, agnostic: bool = False, multi_label: bool = False, max_det: int = 300,
@@ -164,9 +178,11 @@ class Detector:
         """images in chunks of batch_size through letterbox, forward and NMS -> (real images of the chunk, the padded chunk's
         PackedDetections), chunk after chunk"""
         images = list(images)
-        _check_images(images)
+        _check_images(images, self.device)
         # (all geometry first: a bad image raises before anything is uploaded or launched)
         tables = _chunk_tables([im.shape[:2] for im in images], self.S, self.B, self.rect)
+        if _has_frames(images):            # one Frame sends the whole call through kodhip_letterbox_frames
+            images = wrap_frames(images)
         if self.eval_fused is not None:
             self.net.fuse_eval(self.eval_fused)
         for c, (canvas, descs, boxes) in enumerate(tables):
@@ -180,6 +196,8 @@ class Detector:
     def _letterbox(self, chunk, canvas, descs, boxes):
         """one chunk on the device: the upload of its images and the letterbox launch -> (x fp32 [B, 3, H, W] on `canvas`,
         the KodLetterbox rows of the padded chunk)"""
+        if isinstance(chunk[0], Frame):
+            return self._letterbox_frames(chunk, canvas, boxes)
         B, (H, W), n = self.B, canvas, len(chunk)
         pool = ImagePool(chunk, self.device)
         descs["off"] = pool.offsets
@@ -197,12 +215,31 @@ class Detector:
                        "val_prep_batch")
         return x, boxes
 
+    def _letterbox_frames(self, chunk, canvas, boxes):
+        """`_letterbox` for a chunk of Frames: planes in host memory go up in one pinned upload, the others are read where
+        they lie; one kodhip_letterbox_frames launch on either canvas"""
+        B, (H, W), n = self.B, canvas, len(chunk)
+        assert _lib.lib().kodhip_frame_desc_bytes() == FRAME_DESC.itemsize
+        if self._frame_stager is None:
+            self._frame_stager = _Stager(self.device, depth=2)
+        frames = upload_frames(chunk, self.device, self._frame_stager)
+        descs, rows = frame_table(frames, self.S, 0, canvas if self.rect else None)
+        assert np.array_equal(rows, boxes[:n])
+        if n < B:              # pad with the last record, as `_letterbox` does
+            descs = np.concatenate((descs, np.repeat(descs[-1:], B - n)))
+            boxes = np.concatenate((boxes, np.repeat(boxes[-1:], B - n, axis=0)))
+        d_dev = self._stager.upload(descs)
+        x = torch.empty((B, 3, H, W), dtype=torch.float32, device=self.device)
+        _lib.check(_lib.lib().kodhip_letterbox_frames(d_dev.data_ptr(), x.data_ptr(), None, B, H, W,
+                                                      torch.cuda.current_stream().cuda_stream), "letterbox_frames")
+        return x, boxes
+
     def _order(self, images):
         """rect: the images' positions sorted by aspect ratio (every chunk then holds alike shapes), after the checks a call
         in the caller's order would make; otherwise None"""
         if not self.rect or len(images) < 2:
             return None
-        _check_images(images)
+        _check_images(images, self.device)
         shapes = [im.shape[:2] for im in images]
         letterbox_table(shapes, self.S)                       # (its ValueErrors name the caller's index)
         return rect_order(shapes).tolist()
@@ -298,12 +335,14 @@ class EnsembleDetector:
     @torch.no_grad()
     def __call__(self, images: Sequence[np.ndarray]) -> List[torch.Tensor]:
         images = list(images)
-        _check_images(images)
+        _check_images(images, self.device)
         first = self.members[0]
         order = first._order(images)                        # rect: sorted by aspect ratio, as Detector does
         if order is not None:
             images = [images[k] for k in order]
         tables = _chunk_tables([im.shape[:2] for im in images], self.S, self.B, self.rect)
+        if _has_frames(images):
+            images = wrap_frames(images)
         if self.eval_fused is not None:
             for m in self.members:
                 m.net.fuse_eval(self.eval_fused)
@@ -413,6 +452,9 @@ class TiledDetector(Detector):
     def __call__(self, images: Sequence[np.ndarray]) -> List[torch.Tensor]:
         images = list(images)
         for i, im in enumerate(images):
+            if isinstance(im, Frame):
+                raise ValueError(f"image {i}: TiledDetector takes numpy images only - its tile cutter reads the image pool, "
+                                 f"not a Frame's planes")
             if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
                 raise ValueError(f"image {i}: expected an HWC uint8 array with 3 channels")
         plans = self.plans([im.shape[:2] for im in images])                    # (all geometry first, as Detector)
