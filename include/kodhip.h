@@ -447,6 +447,30 @@ int kodhip_tta_view(const float* x, void* out_pairs, float* out_f32 /* or NULL *
 int kodhip_decode_view(const KodDecodeLevel* levels /* host[3] */, float* det, int B, int A, int nc, float scale,
                        int flip_lr, float full_width, int level_mask, int row_offset, int rows_total, kodStream_t stream);
 
+/* ---- multi-scale training (YOLOv5 train.py --multi-scale: F.interpolate(imgs, size, mode="bilinear", align_corners=False)
+ *      on every batch, to a random multiple of 32 between 0.5 and 1.5 of the training size).
+ *
+ * kodhip_multiscale_batch: one launch resizes a base-size batch that is already on the device to h x w - up or down, each
+ * axis on its own - and scales the batch's boxes with it.  Exactly one source is given: x_f32 [B][3][H][W] fp32, or x_pairs
+ * bf16 [B][H][W/2][8] (the network's input layout; read as bf16 -> fp32, which is exact).  out_pairs: bf16 [B][h][w/2][8]
+ * (channels 3 and 7 are 0, the fp32 -> bf16 rounding of kodhip_nchw_to_nhwc4); out_f32 [B][3][h][w] or NULL: the same fp32
+ * values before that rounding.  The image arithmetic is kodhip_tta_view's, fp32, every operation rounded on its own (no
+ * FMA), per axis with n_in source and n_out destination samples:
+ *     scale = fp32(n_in) / fp32(n_out)
+ *     src   = max(fp32(fp32(dst + 0.5f) * scale) - 0.5f, 0)
+ *     i0 = (int)src (at most n_in - 1), i1 = i0 + (i0 < n_in - 1), l1 = src - i0, l0 = 1 - l1
+ *     out   = hy0 * (wx0 * a + wx1 * b) + hy1 * (wx0 * c + wx1 * d)       a, b on row y0; c, d on row y1
+ * h = H and w = W give l1 = 0 everywhere: the pixels themselves (rounded to bf16 in out_pairs).
+ * Boxes: boxes_in [n][4] fp64 xyxy pixels of the base size -> boxes_out, x' = x * (fp64(w) / fp64(W)), y' = y * (fp64(h) /
+ * fp64(H)), one rounded fp64 multiply each; rows of zeros stay zeros; boxes_out == boxes_in is allowed; n == 0 or NULL
+ * boxes_in: pixels only.  One thread per output pixel pair, the boxes in extra blocks of the same launch.
+ * Refused before any launch: both or neither source, a null out_pairs, odd W or w, non-positive sizes, B * h * w or B * H * W
+ * of 2^33 and more, n < 0, misaligned buffers (pairs 16 bytes, out_f32 8), an output that overlaps the source, boxes_out
+ * partly overlapping boxes_in. */
+int kodhip_multiscale_batch(const float* x_f32 /* or NULL */, const void* x_pairs /* or NULL */, void* out_pairs,
+                            float* out_f32 /* or NULL */, int B, int H, int W, int h, int w,
+                            const double* boxes_in /* or NULL */, double* boxes_out, int n, kodStream_t stream);
+
 /* kodhip_nms with the deployment options of YOLOv5's detect.py.  With best_class = 0, class_keep = NULL and
  * letterbox = NULL it is kodhip_nms: the same launches, the same bits.
  *   best_class = 1  (multi_label=False) one candidate per row: score = max over c of fp32(cls_c * obj), the LOWEST class

@@ -130,6 +130,7 @@ SIGNATURES = {
     "kodhip_decode": (i32, [C.POINTER(KodDecodeLevel), vp, i32, i32, i32, vp]),
     "kodhip_nms": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, f32, vp]),
     "kodhip_tta_view": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]),
+    "kodhip_multiscale_batch": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp]),
     "kodhip_decode_view": (i32, [C.POINTER(KodDecodeLevel), vp, i32, i32, i32, f32, i32, f32, i32, i32, i32, vp]),
     "kodhip_letterbox_bytes": (i32, []),
     "kodhip_nms_ex": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, f32, i32, vp, vp, vp]),

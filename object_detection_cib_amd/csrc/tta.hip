@@ -12,7 +12,7 @@
 //                                                                    the sum; then the outer products, then the outer sum
 // The flip comes first (the view is the resize of x[..., ::-1]); it is folded into the column index of the reads.
 // h = H, w = W gives l1 = 0 on both axes and reproduces the (flipped) pixels.
-#include "kodhip_common.h"
+#include "kodhip_bilinear.h"
 
 namespace {
 
@@ -23,16 +23,6 @@ struct TtaViewArgs {
   int B, H, W, h, w, Hp, Wp, flip;
   float pad, scale_y, scale_x;
 };
-
-// source index pair and weights of destination index `dst` along an axis of n_in source samples
-__device__ __forceinline__ void tta_axis(int dst, float scale, int n_in, int& i0, int& i1, float& l0, float& l1) {
-  const float src = fmaxf(__fsub_rn(__fmul_rn(__fadd_rn((float)dst, 0.5f), scale), 0.5f), 0.f);
-  i0 = (int)src;
-  l1 = __fsub_rn(src, (float)i0);
-  l0 = __fsub_rn(1.f, l1);
-  i0 = min(i0, n_in - 1);          // (src <= n_in - 1 for every dst < n_out <= n_in: never taken, keeps the reads in bounds)
-  i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-}
 
 // one thread per output pixel pair: 2 x 3 channels, one 16-byte store
 __global__ __launch_bounds__(256) void tta_view_kernel(TtaViewArgs a) {
@@ -50,23 +40,21 @@ __global__ __launch_bounds__(256) void tta_view_kernel(TtaViewArgs a) {
   if (y < a.h) {
     int y0, y1;
     float hy0, hy1;
-    tta_axis(y, a.scale_y, a.H, y0, y1, hy0, hy1);
+    bilin_axis(y, a.scale_y, a.H, y0, y1, hy0, hy1);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int x = 2 * q + k;
       if (x >= a.w) continue;
       int x0, x1;
       float wx0, wx1;
-      tta_axis(x, a.scale_x, a.W, x0, x1, wx0, wx1);
+      bilin_axis(x, a.scale_x, a.W, x0, x1, wx0, wx1);
       if (a.flip) { x0 = a.W - 1 - x0; x1 = a.W - 1 - x1; }
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         const float* pl = a.x + (size_t)(b * 3 + c) * a.H * a.W;
         const float* r0 = pl + (size_t)y0 * a.W;
         const float* r1 = pl + (size_t)y1 * a.W;
-        const float top = __fadd_rn(__fmul_rn(wx0, r0[x0]), __fmul_rn(wx1, r0[x1]));
-        const float bot = __fadd_rn(__fmul_rn(wx0, r1[x0]), __fmul_rn(wx1, r1[x1]));
-        v[k][c] = __fadd_rn(__fmul_rn(hy0, top), __fmul_rn(hy1, bot));
+        v[k][c] = bilin_mix(wx0, wx1, hy0, hy1, r0[x0], r0[x1], r1[x0], r1[x1]);
       }
     }
   }

@@ -27,11 +27,85 @@ from ..core.types import FeatureShape
 _KEEP = object()          # __call__(gradient_clip_val=...) left out: keep the current value
 
 
+class TargetBlock:
+    """The targets of one batch padded to a fixed capacity: boxes f64 [cap, 4] | labels i64 [cap] | sample ids i32 [cap] as
+    views of ONE device block, and the ring of pinned host mirrors it is filled from.  Padding rows are zero-size boxes,
+    which the assigner never matches.  GraphedTrainStep owns one; the captured steps of a MultiScaleTrainStep share one."""
+
+    def __init__(self, max_targets: int, device, lib):
+        # a batch's targets arrive as one host -> device copy of the pinned mirror block (three copies + three fills cost
+        # 0.17 ms per step)
+        self.cap, self.lib = int(max_targets), lib
+        cap = self.cap
+        tbytes = (cap * 44 + 15) // 16 * 16            # (kodhip_pull_from_host moves 16-byte pieces)
+        self.block = torch.zeros(tbytes, dtype=torch.uint8, device=device)
+        self.boxes = self.block[:cap * 32].view(torch.float64).view(cap, 4)
+        self.labels = self.block[cap * 32:cap * 40].view(torch.int64)
+        self.samples = self.block[cap * 40:cap * 44].view(torch.int32)
+        self.targets = BatchedTargets(self.boxes, self.labels, self.samples, self.cap)
+        self._host = []
+        for _ in range(4):
+            blk = torch.zeros(tbytes, dtype=torch.uint8).pin_memory()
+            self._host.append((blk, blk[:cap * 32].view(torch.float64).view(cap, 4), blk[cap * 32:cap * 40].view(torch.int64),
+                               blk[cap * 40:cap * 44].view(torch.int32)))
+        self._events, self._slot, self._used = [None] * 4, 0, [0] * 4
+
+    def load(self, targets) -> int:
+        """Fill the device block from a batch's targets; -> the number of boxes (a host value in every form)."""
+        if isinstance(targets, BatchedTargets):
+            n = targets.n
+            if n > self.cap:
+                raise ValueError(f"{n} target boxes in the batch exceed the graph's capacity {self.cap}")
+            self.boxes.zero_(); self.labels.zero_(); self.samples.zero_()      # padding = zero-size boxes: never assigned
+            if n:
+                self.boxes[:n].copy_(targets.boxes)
+                self.labels[:n].copy_(targets.labels)
+                self.samples[:n].copy_(targets.samples)
+            return n
+        # host-side targets (tuple of DetectionTarget on the CPU, or the flat arrays of data.device_pipeline.PackedTargets):
+        # pack them into one pinned block and upload it without stalling the host behind the previous step (a pageable
+        # copy would)
+        packed = hasattr(targets, "samples") and hasattr(targets, "counts")
+        lens = None if packed else [int(t.boxes.shape[0]) for t in targets]
+        n = int(len(targets.labels)) if packed else sum(lens)
+        if n > self.cap:
+            raise ValueError(f"{n} target boxes in the batch exceed the graph's capacity {self.cap}")
+        k = self._slot
+        self._slot = (self._slot + 1) % len(self._host)
+        if self._events[k] is not None:
+            self._events[k].synchronize()
+        blk, hb, hl, hs = self._host[k]
+        m_old = self._used[k]                  # padding = zero-size boxes: only what the slot's previous batch filled needs clearing
+        if m_old > n:
+            hb[n:m_old].zero_(); hl[n:m_old].zero_(); hs[n:m_old].zero_()
+        self._used[k] = n
+        if packed:
+            if n:
+                hb.numpy()[:n] = targets.boxes
+                hl.numpy()[:n] = targets.labels
+                hs.numpy()[:n] = targets.samples
+            targets = ()
+        o = 0
+        for i, t in enumerate(targets):
+            m = lens[i]
+            if m:
+                hb[o:o + m] = t.boxes.reshape(-1, 4).to(torch.float64)
+                hl[o:o + m] = t.labels.reshape(-1).to(torch.int64)
+                hs[o:o + m] = i
+                o += m
+        _lib.check(self.lib.kodhip_pull_from_host(self.block.data_ptr(), blk.data_ptr(), blk.numel(),
+                                                  torch.cuda.current_stream().cuda_stream), "pull_from_host")
+        ev = torch.cuda.Event()
+        ev.record()
+        self._events[k] = ev
+        return n
+
+
 class GraphedTrainStep:
     def __init__(self, net, loss, batch_size: int, height: int, width: int, max_targets: int = 4096,
                  loss_scale: Optional[float] = None, input_pairs: bool = False,
                  gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
-                 skip_nonfinite: bool = False, track_grad_norm: bool = False):
+                 skip_nonfinite: bool = False, track_grad_norm: bool = False, target_block: Optional["TargetBlock"] = None):
         """input_pairs: batches arrive as bf16 pixel pairs [B, H, W/2, 8] (DeviceTrainPipeline.make_batch(out_pairs=True)) and
         are copied straight into the network's input buffer - no fp32 NCHW batch, no layout-change pass in the step.
         gradient_clip_val / gradient_clip_algorithm ("norm" | "value"): Lightning's Trainer arguments; the clipping runs
@@ -39,7 +113,8 @@ class GraphedTrainStep:
         algorithm and on / off may not).  skip_nonfinite: a step whose gradient norm is NaN / Inf leaves parameters and
         momentum untouched and is counted in `skipped_steps`.  track_grad_norm: run the norm reduction without clipping.
         `grad_norm` (total, bias, decay, norm-group norms before clipping) and `skipped_steps` are static device tensors:
-        reading them is the caller's synchronisation, the step has none."""
+        reading them is the caller's synchronisation, the step has none.  target_block: a TargetBlock to read the targets from
+        instead of one of its own (MultiScaleTrainStep: one block for the steps of all its sizes)."""
         if gradient_clip_algorithm not in ("norm", "value"):
             raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected 'norm' or 'value'")
         self.gradient_clip_val = None if gradient_clip_val is None else float(gradient_clip_val)
@@ -54,15 +129,11 @@ class GraphedTrainStep:
         self.cap = int(max_targets)
         self.scale = float(batch_size if loss_scale is None else loss_scale)     # exp.py:104-138: total = B * sum
         self.x = torch.zeros((batch_size, 3, height, width), dtype=torch.float32, device=dev)
-        # boxes f64 [cap, 4] | labels i64 [cap] | sample ids i32 [cap] as views of ONE device block: a batch's targets arrive
-        # as one host -> device copy of the pinned mirror block (three copies + three fills cost 0.17 ms per step)
-        cap = self.cap
-        tbytes = (cap * 44 + 15) // 16 * 16            # (kodhip_pull_from_host moves 16-byte pieces)
-        self._tblock = torch.zeros(tbytes, dtype=torch.uint8, device=dev)
-        self.boxes = self._tblock[:cap * 32].view(torch.float64).view(cap, 4)
-        self.labels = self._tblock[cap * 32:cap * 40].view(torch.int64)
-        self.samples = self._tblock[cap * 40:cap * 44].view(torch.int32)
-        self.targets = BatchedTargets(self.boxes, self.labels, self.samples, self.cap)
+        # boxes f64 [cap, 4] | labels i64 [cap] | sample ids i32 [cap] as views of ONE device block (TargetBlock)
+        self._tb = target_block if target_block is not None else TargetBlock(max_targets, dev, self.eng.lib)
+        assert self._tb.cap == self.cap
+        self._tblock, self.boxes, self.labels, self.samples = self._tb.block, self._tb.boxes, self._tb.labels, self._tb.samples
+        self.targets = self._tb.targets
         self.shape = FeatureShape(width=width, height=height)
         self.params = list(net.parameters())
         self.graph = None
@@ -70,12 +141,7 @@ class GraphedTrainStep:
         self._bn_flags = None
         self.total = None
         self.parts = None
-        self._host = []
-        for _ in range(4):
-            blk = torch.zeros(tbytes, dtype=torch.uint8).pin_memory()
-            self._host.append((blk, blk[:cap * 32].view(torch.float64).view(cap, 4), blk[cap * 32:cap * 40].view(torch.int64),
-                               blk[cap * 40:cap * 44].view(torch.int32)))
-        self._events, self._slot, self._used = [None] * 4, 0, [0] * 4
+        self._pins = 0                    # pins capture() took on this shape, given back by release()
 
     def input_buffer(self) -> torch.Tensor:
         """input_pairs=True: the network's own input buffer (bf16 pixel pairs [B, H, W/2, 8]).  A data pipeline that runs on
@@ -117,52 +183,8 @@ class GraphedTrainStep:
         else:
             assert tuple(images.shape) == tuple(self.x.shape), (images.shape, self.x.shape)
             self.x.copy_(images, non_blocking=True)
-        if isinstance(targets, BatchedTargets):
-            n = targets.n
-            if n > self.cap:
-                raise ValueError(f"{n} target boxes in the batch exceed the graph's capacity {self.cap}")
-            self.boxes.zero_(); self.labels.zero_(); self.samples.zero_()      # padding = zero-size boxes: never assigned
-            if n:
-                self.boxes[:n].copy_(targets.boxes)
-                self.labels[:n].copy_(targets.labels)
-                self.samples[:n].copy_(targets.samples)
-            return
-        # host-side targets (tuple of DetectionTarget on the CPU, or the flat arrays of data.device_pipeline.PackedTargets):
-        # pack them into one pinned block and upload it without stalling the host behind the previous step (a pageable
-        # copy would)
-        packed = hasattr(targets, "samples") and hasattr(targets, "counts")
-        lens = None if packed else [int(t.boxes.shape[0]) for t in targets]
-        n = int(len(targets.labels)) if packed else sum(lens)
-        if n > self.cap:
-            raise ValueError(f"{n} target boxes in the batch exceed the graph's capacity {self.cap}")
-        k = self._slot
-        self._slot = (self._slot + 1) % len(self._host)
-        if self._events[k] is not None:
-            self._events[k].synchronize()
-        blk, hb, hl, hs = self._host[k]
-        m_old = self._used[k]                  # padding = zero-size boxes: only what the slot's previous batch filled needs clearing
-        if m_old > n:
-            hb[n:m_old].zero_(); hl[n:m_old].zero_(); hs[n:m_old].zero_()
-        self._used[k] = n
-        if packed:
-            if n:
-                hb.numpy()[:n] = targets.boxes
-                hl.numpy()[:n] = targets.labels
-                hs.numpy()[:n] = targets.samples
-            targets = ()
-        o = 0
-        for i, t in enumerate(targets):
-            m = lens[i]
-            if m:
-                hb[o:o + m] = t.boxes.reshape(-1, 4).to(torch.float64)
-                hl[o:o + m] = t.labels.reshape(-1).to(torch.int64)
-                hs[o:o + m] = i
-                o += m
-        _lib.check(self.eng.lib.kodhip_pull_from_host(self._tblock.data_ptr(), blk.data_ptr(), blk.numel(),
-                                                      torch.cuda.current_stream().cuda_stream), "pull_from_host")
-        ev = torch.cuda.Event()
-        ev.record()
-        self._events[k] = ev
+        if targets is not None:            # (None: a MultiScaleTrainStep has filled the shared block already)
+            self._tb.load(targets)
 
     def capture(self, images: torch.Tensor, targets, warmup: int = 2, preserve_state: bool = True):
         """Runs `warmup` eager steps on this batch (allocations, lazy initialisation), then captures the step.
@@ -170,6 +192,7 @@ class GraphedTrainStep:
         does not move the training trajectory."""
         eng = self.eng
         eng.pin_shape(self.B, self.H, self.W)      # the graph bakes this shape's buffer addresses in (Engine.allocate)
+        self._pins += 1
         self._load(images, targets)
         self._clip_cfg = self._clip_config()
         eng.set_clip(self.gradient_clip_val)
@@ -200,31 +223,51 @@ class GraphedTrainStep:
                  grad_scale: float = 1.0, gradient_clip_val=_KEEP, gradient_clip_algorithm: Optional[str] = None):
         """One replayed step on a new batch.  Returns (total, (box, obj, cls)) - static tensors that the next call
         overwrites (clone to keep).  gradient_clip_val: a new max_norm / clamp value from this step on."""
-        if self.graph is None:
-            raise RuntimeError("call capture() first")
-        if self.eng.freeze_flags() != self._freeze_flags:
+        self._prepare(lr, momentum, weight_decay, grad_scale, gradient_clip_val, gradient_clip_algorithm)
+        if self.eng.peer is not None:
+            self.eng.peer.check()             # a failed SyncBN exchange of an earlier replay: raise, do not train on NaN
+        self._load(images, targets)
+        return self._replay()
+
+    def release(self):
+        """Drop the captured graph and give back the pins capture() took on the shape (Engine.unpin_shape): the buffer set
+        becomes an ordinary one that the engine may drop.  The caller makes sure that no replay is still running; a later
+        capture() captures again."""
+        self.graph, self.total, self.parts = None, None, None
+        while self._pins:
+            self.eng.unpin_shape(self.B, self.H, self.W)
+            self._pins -= 1
+
+    def _guard(self, freeze_flags, bn_flags, clip_cfg):
+        """what the graph was captured with against what holds now (MultiScaleTrainStep checks every held step per call)"""
+        if freeze_flags != self._freeze_flags:
             # the graph replays the backward program of the freeze set it was captured with
             raise RuntimeError("requires_grad changed after capture(): the captured step would train the old freeze set; "
                                "build a new GraphedTrainStep and capture() again")
-        if self.eng.bn_mode_flags() != self._bn_flags:
+        if bn_flags != self._bn_flags:
             # the graph replays the forward / backward program of the BatchNorm modes it was captured with
             raise RuntimeError("a BatchNorm module changed mode (train / eval) after capture(): the captured step would "
                                "normalise with the old modes; build a new GraphedTrainStep and capture() again")
-        if gradient_clip_val is not _KEEP:
-            self.gradient_clip_val = None if gradient_clip_val is None else float(gradient_clip_val)
-        if gradient_clip_algorithm is not None:
-            self.gradient_clip_algorithm = gradient_clip_algorithm
-        if self._clip_config() != self._clip_cfg:
+        if clip_cfg != self._clip_cfg:
             # the graph replays the launches of the clipping mode it was captured with; only the value is device data
             raise RuntimeError("the gradient clipping algorithm (or clipping on / off, skip_nonfinite, track_grad_norm) changed "
                                "after capture(): the captured step holds the old launches; build a new GraphedTrainStep and "
                                "capture() again (gradient_clip_val itself may change per step)")
+
+    def _prepare(self, lr, momentum, weight_decay, grad_scale, gradient_clip_val, gradient_clip_algorithm):
+        """everything of a call before the batch is loaded: the guards, the clip value and the hyper-parameters"""
+        if self.graph is None:
+            raise RuntimeError("call capture() first")
+        if gradient_clip_val is not _KEEP:
+            self.gradient_clip_val = None if gradient_clip_val is None else float(gradient_clip_val)
+        if gradient_clip_algorithm is not None:
+            self.gradient_clip_algorithm = gradient_clip_algorithm
+        self._guard(self.eng.freeze_flags(), self.eng.bn_mode_flags(), self._clip_config())
         self.eng.set_clip(self.gradient_clip_val)
         if lr is not None:
             self.eng.set_hyper(lr, momentum, weight_decay, grad_scale)
-        if self.eng.peer is not None:
-            self.eng.peer.check()             # a failed SyncBN exchange of an earlier replay: raise, do not train on NaN
-        self._load(images, targets)
+
+    def _replay(self):
         self.graph.replay()
         self.eng.param_version += 1           # the replayed SGD changed the parameters
         self.eng.note_sgd_step()

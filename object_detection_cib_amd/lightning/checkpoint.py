@@ -95,8 +95,14 @@ def load_optimizer_state_dict(net, optimizer, sd: Dict):
     return loaded
 
 
+MULTI_SCALE_KEY = "multi_scale_schedule"
+
+
 def save_checkpoint(path: str, net, optimizer=None, epoch: int = 0, global_step: int = 0,
-                    lr_scheduler_state: Optional[Dict] = None, extra: Optional[Dict] = None) -> Dict:
+                    lr_scheduler_state: Optional[Dict] = None, extra: Optional[Dict] = None,
+                    multi_scale_state: Optional[Dict] = None) -> Dict:
+    """multi_scale_state: the multi-scale size schedule's state_dict (MultiScaleSchedule / MultiScaleTrainStep /
+    DefaultYolov5Experiment.multi_scale_state_dict), stored under MULTI_SCALE_KEY; left out, the file has no such key."""
     ckpt = {
         "epoch": int(epoch), "global_step": int(global_step), "pytorch-lightning_version": LIGHTNING_VERSION,
         "state_dict": {NET_PREFIX + k: v.detach().clone().cpu() for k, v in net.state_dict().items()},
@@ -104,15 +110,23 @@ def save_checkpoint(path: str, net, optimizer=None, epoch: int = 0, global_step:
         "optimizer_states": [optimizer_state_dict(net, optimizer)] if optimizer is not None else [],
         "lr_schedulers": [lr_scheduler_state] if lr_scheduler_state is not None else [],
     }
+    if multi_scale_state is not None:
+        ckpt[MULTI_SCALE_KEY] = dict(multi_scale_state)
     if extra:
         ckpt.update(extra)
     torch.save(ckpt, path)
     return ckpt
 
 
-def load_checkpoint(path: str, net, optimizer=None, strict: bool = True) -> Dict:
-    """Loads the network (and optimizer) from a reference-layout `.ckpt`; returns the remaining entries."""
+def load_checkpoint(path: str, net, optimizer=None, strict: bool = True, multi_scale=None) -> Dict:
+    """Loads the network (and optimizer) from a reference-layout `.ckpt`; returns the remaining entries.
+    multi_scale: an object with load_state_dict (MultiScaleSchedule, MultiScaleTrainStep) or a DefaultYolov5Experiment
+    (load_multi_scale_state_dict) that takes the size schedule's state when the file carries one; a file without the key
+    loads as before and leaves it untouched."""
     ckpt = torch.load(path, map_location="cpu", weights_only=False)
+    if multi_scale is not None and ckpt.get(MULTI_SCALE_KEY) is not None:
+        load = getattr(multi_scale, "load_multi_scale_state_dict", None) or multi_scale.load_state_dict
+        load(ckpt[MULTI_SCALE_KEY])
     sd = ckpt["state_dict"]
     net_sd = {k[len(NET_PREFIX):]: v for k, v in sd.items() if k.startswith(NET_PREFIX)}
     if not net_sd:                      # a bare network state_dict (README-style weight files)

@@ -52,7 +52,14 @@ class DefaultYolov5Experiment:
     val_max_graphs: with graphed=True validation_step keeps one captured forward per input shape, at most this many, least
     recently used first (engine/graphed.GraphCache) - rectangular validation batches (DeviceValPipeline.rect_batches +
     make_batch(canvas=...)) bring one shape per canvas; a shape beyond the bound costs a buffer-set allocation and a capture
-    again when it comes back."""
+    again when it comes back.
+    multi_scale=True: YOLOv5's train.py --multi-scale - every training batch is resized on the device to a random multiple of
+    32 between multi_scale_range[0] and [1] times its size, a new size every multi_scale_interval steps, boxes scaled with it
+    (engine/multiscale.py, one kodhip_multiscale_batch launch per step); validation stays at the size of its batches.
+    graphed=True keeps one captured step and one engine buffer set per size, at most multi_scale_max_graphs (None: all),
+    least recently used first: when the 21 sizes of a 640 px plan do not fit in device memory, narrow multi_scale_range,
+    bound multi_scale_max_graphs, and raise multi_scale_interval so that re-captures come less often.  Data parallel: every
+    rank must use the same multi_scale_seed (the ranks then draw the same sizes, which SyncBN needs)."""
 
     def __init__(self, net, loss, anchor_info: LayerwiseAnchorInfo, smart_optimizer: Optional[SmartOptimizer] = None,
                  lr_scheduler: Optional[Callable] = None,
@@ -62,7 +69,8 @@ class DefaultYolov5Experiment:
                  gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
                  eval_fused: Optional[bool] = None, val_confusion: bool = False, val_confusion_conf: float = 0.25,
                  val_confusion_iou: float = 0.45, val_augment: bool = False, val_metrics: bool = False,
-                 val_max_graphs: int = 8):
+                 val_max_graphs: int = 8, multi_scale: bool = False, multi_scale_range=(0.5, 1.5),
+                 multi_scale_interval: int = 1, multi_scale_max_graphs: Optional[int] = None, multi_scale_seed: int = 0):
         if gradient_clip_algorithm not in CLIP_ALGORITHMS:
             raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected one of {CLIP_ALGORITHMS}")
         # Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm): handed to the FusedSGD / the captured step
@@ -111,6 +119,12 @@ class DefaultYolov5Experiment:
         # records are GATHERED (the whole validation set's values), whatever val_sync says.
         self.val_metrics = bool(val_metrics)
         self.metrics = None
+        # multi_scale: the size schedule lives in the captured wrapper (graphed) or in `_ms_schedule` (eager), both built
+        # with the first batch; a state loaded before that waits in `_ms_pending`
+        self.multi_scale = bool(multi_scale)
+        self.multi_scale_range, self.multi_scale_interval = tuple(multi_scale_range), int(multi_scale_interval)
+        self.multi_scale_max_graphs, self.multi_scale_seed = multi_scale_max_graphs, int(multi_scale_seed)
+        self._ms_schedule, self._ms_pending, self._ms_pairs = None, None, {}
 
     # exp.py:156-162
     def configure_optimizers(self):
@@ -184,6 +198,8 @@ class DefaultYolov5Experiment:
         self.configure_optimizers()
         if self.graphed:
             return self._optimize_graphed(batch, num_training_batches)
+        if self.multi_scale:
+            batch = self._multi_scale_batch(batch)
         self.optimizer.zero_grad(set_to_none=True)
         total = self.training_step(batch)
         total.backward()
@@ -207,6 +223,49 @@ class DefaultYolov5Experiment:
         self.global_step += 1
         return total
 
+    # ------------------------------------------------------------------ multi-scale
+    def _multi_scale_holder(self):
+        return self._gstep if (self.graphed and self._gstep is not None) else self._ms_schedule
+
+    def multi_scale_state_dict(self) -> dict:
+        """the size schedule's state (save_checkpoint(multi_scale_state=...))"""
+        h = self._multi_scale_holder()
+        if h is not None:
+            return h.state_dict()
+        return dict(self._ms_pending) if self._ms_pending is not None else {"seed": self.multi_scale_seed, "draws": 0, "steps": 0}
+
+    def load_multi_scale_state_dict(self, state: dict):
+        h = self._multi_scale_holder()
+        if h is not None:
+            h.load_state_dict(state)
+        else:
+            self._ms_pending = dict(state)
+
+    def _multi_scale_batch(self, batch):
+        """the eager route: the batch resized by kodhip_multiscale_batch to the drawn size (fp32 NCHW for the module's
+        forward) and its boxes, scaled by the same launch, as BatchedTargets"""
+        from ....core.label_assignment.yv5 import BatchedTargets
+        from ....engine.multiscale import MultiScaleSchedule, resize_batch
+        images, targets, rest = batch
+        B, _, H, W = images.shape
+        eng = self.net.engine()
+        if self._ms_schedule is None:
+            self._ms_schedule = MultiScaleSchedule(H, W, self.multi_scale_seed, self.multi_scale_range,
+                                                   max(b.stride for b in eng.g.bufs), self.multi_scale_interval)
+            if self._ms_pending is not None:
+                self._ms_schedule.load_state_dict(self._ms_pending)
+                self._ms_pending = None
+        h, w = self._ms_schedule.next()
+        x = (images if images.dtype == torch.float32 else images.float()).contiguous()
+        bt = targets if isinstance(targets, BatchedTargets) else BatchedTargets.from_targets(targets, x.device)
+        out = torch.empty((B, 3, h, w), dtype=torch.float32, device=x.device)
+        pairs = self._ms_pairs.get((B, h, w))
+        if pairs is None:
+            pairs = self._ms_pairs[(B, h, w)] = torch.empty((B, h, w // 2, 8), dtype=torch.bfloat16, device=x.device)
+        boxes = torch.empty_like(bt.boxes)
+        resize_batch(eng.lib, x, pairs, h, w, out_f32=out, boxes_in=bt.boxes, boxes_out=boxes, n=bt.n)
+        return out, BatchedTargets(boxes, bt.labels, bt.samples, bt.n), rest
+
     def _warmup(self, num_training_batches: int):
         if self.optimizer_warmup_updater is not None:
             nw = max(round(num_training_batches * self.optimizer_warmup_updater.warmup_epochs), 100)
@@ -217,6 +276,19 @@ class DefaultYolov5Experiment:
     def _optimize_graphed(self, batch, num_training_batches: int):
         from ....engine.graphed import GraphedTrainStep
         images, targets, _ = batch
+        if self._gstep is None and self.multi_scale:
+            from ....engine.multiscale import MultiScaleTrainStep
+            B, _, H, W = images.shape
+            opt = self.optimizer
+            self._gstep = MultiScaleTrainStep(self.net, self.loss, B, H, W, self.max_targets,
+                                              gradient_clip_val=opt.gradient_clip_val,
+                                              gradient_clip_algorithm=opt.gradient_clip_algorithm,
+                                              skip_nonfinite=opt.skip_nonfinite, track_grad_norm=opt.track_grad_norm,
+                                              scale_range=self.multi_scale_range, interval=self.multi_scale_interval,
+                                              seed=self.multi_scale_seed, max_graphs=self.multi_scale_max_graphs)
+            if self._ms_pending is not None:
+                self._gstep.load_state_dict(self._ms_pending)
+                self._ms_pending = None
         if self._gstep is None:
             B, _, H, W = images.shape
             opt = self.optimizer
