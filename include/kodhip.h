@@ -319,6 +319,20 @@ int kodhip_sgd_nesterov_clipped(float* params, const float* grads, float* moment
 /* the gradients themselves, in place, over the counted elements: mode 0 g *= clip[4], mode 1 g = clamp(g, -clip[8], +clip[8]) */
 int kodhip_grad_clip_inplace(float* grads, const void* group_ids, const void* count_mask, long n, const float* clip,
                              int mode, kodStream_t stream);
+/* ---- weight EMA (YOLOv5 ModelEMA: `v *= d; v += (1 - d) * msd[k]`), beside the step, never inside it ----------------
+ * Up to 4 segments per launch; model_ptrs / shadow_ptrs / numels are HOST arrays of nseg entries (device pointers, element
+ * counts) that travel by value in the kernel arguments.  Per element, fp32, every operation rounded on its own:
+ *   shadow = fl( fl(shadow * d) + fl(omd * model) )
+ * with omd = float32(1.0 - d) formed in double by the caller (float32(1 - d) != 1 - float32(d)).  NaN, Inf and subnormals
+ * as IEEE fp32.  Bases 16-byte aligned: 16-byte accesses; any 4-byte aligned base and any numel >= 0 are correct; nothing
+ * at or beyond numel is touched; a segment with numel 0 is skipped (its pointers may be NULL).  Refused (< 0, nothing
+ * launched): nseg outside 1..4, a NULL table, a negative numel, a NULL or misaligned pointer with numel > 0, a model segment
+ * that overlaps a shadow segment, two written segments that overlap. */
+int kodhip_ema_update(const float* const* model_ptrs, float* const* shadow_ptrs, const long* numels, int nseg, float d, float omd,
+                      kodStream_t stream);
+/* exchanges the contents of the paired segments (numels in 32-bit words: a pure copy, NaN payloads included, so an int64
+ * buffer goes as two words per value); the same tables, rules and refusals as kodhip_ema_update */
+int kodhip_ema_swap(void* const* a_ptrs, void* const* b_ptrs, const long* numels, int nseg, kodStream_t stream);
 int kodhip_fill_u32(void* p, uint32_t value, long n, kodStream_t stream);
 /* dst (device) <- src (PINNED host memory), bytes % 16 == 0, both 16-byte aligned: a kernel pulling the bytes through the
  * host memory's device mapping - the small per-step tables of the data path (kod/data/detection.py's per-sample results)

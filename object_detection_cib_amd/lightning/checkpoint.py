@@ -96,13 +96,16 @@ def load_optimizer_state_dict(net, optimizer, sd: Dict):
 
 
 MULTI_SCALE_KEY = "multi_scale_schedule"
+EMA_KEY = "ema"
 
 
 def save_checkpoint(path: str, net, optimizer=None, epoch: int = 0, global_step: int = 0,
                     lr_scheduler_state: Optional[Dict] = None, extra: Optional[Dict] = None,
-                    multi_scale_state: Optional[Dict] = None) -> Dict:
+                    multi_scale_state: Optional[Dict] = None, ema_state: Optional[Dict] = None) -> Dict:
     """multi_scale_state: the multi-scale size schedule's state_dict (MultiScaleSchedule / MultiScaleTrainStep /
-    DefaultYolov5Experiment.multi_scale_state_dict), stored under MULTI_SCALE_KEY; left out, the file has no such key."""
+    DefaultYolov5Experiment.multi_scale_state_dict), stored under MULTI_SCALE_KEY; left out, the file has no such key.
+    ema_state: the weight EMA's state (ModelEMA.ema_state_dict / DefaultYolov5Experiment.ema_state_dict: updates, decay, tau and
+    the EMA's own state dict), stored under EMA_KEY; left out, the file has no such key."""
     ckpt = {
         "epoch": int(epoch), "global_step": int(global_step), "pytorch-lightning_version": LIGHTNING_VERSION,
         "state_dict": {NET_PREFIX + k: v.detach().clone().cpu() for k, v in net.state_dict().items()},
@@ -112,21 +115,27 @@ def save_checkpoint(path: str, net, optimizer=None, epoch: int = 0, global_step:
     }
     if multi_scale_state is not None:
         ckpt[MULTI_SCALE_KEY] = dict(multi_scale_state)
+    if ema_state is not None:
+        ckpt[EMA_KEY] = dict(ema_state)
     if extra:
         ckpt.update(extra)
     torch.save(ckpt, path)
     return ckpt
 
 
-def load_checkpoint(path: str, net, optimizer=None, strict: bool = True, multi_scale=None) -> Dict:
+def load_checkpoint(path: str, net, optimizer=None, strict: bool = True, multi_scale=None, ema=None) -> Dict:
     """Loads the network (and optimizer) from a reference-layout `.ckpt`; returns the remaining entries.
     multi_scale: an object with load_state_dict (MultiScaleSchedule, MultiScaleTrainStep) or a DefaultYolov5Experiment
     (load_multi_scale_state_dict) that takes the size schedule's state when the file carries one; a file without the key
-    loads as before and leaves it untouched."""
+    loads as before and leaves it untouched.
+    ema: a ModelEMA or a DefaultYolov5Experiment(ema=True) (both have load_ema_state_dict) that takes the weight EMA's state
+    when the file carries one; a file without the key leaves it untouched."""
     ckpt = torch.load(path, map_location="cpu", weights_only=False)
     if multi_scale is not None and ckpt.get(MULTI_SCALE_KEY) is not None:
         load = getattr(multi_scale, "load_multi_scale_state_dict", None) or multi_scale.load_state_dict
         load(ckpt[MULTI_SCALE_KEY])
+    if ema is not None and ckpt.get(EMA_KEY) is not None:
+        ema.load_ema_state_dict(ckpt[EMA_KEY])
     sd = ckpt["state_dict"]
     net_sd = {k[len(NET_PREFIX):]: v for k, v in sd.items() if k.startswith(NET_PREFIX)}
     if not net_sd:                      # a bare network state_dict (README-style weight files)

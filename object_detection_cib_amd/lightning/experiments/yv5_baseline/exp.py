@@ -59,7 +59,13 @@ class DefaultYolov5Experiment:
     graphed=True keeps one captured step and one engine buffer set per size, at most multi_scale_max_graphs (None: all),
     least recently used first: when the 21 sizes of a 640 px plan do not fit in device memory, narrow multi_scale_range,
     bound multi_scale_max_graphs, and raise multi_scale_interval so that re-captures come less often.  Data parallel: every
-    rank must use the same multi_scale_seed (the ranks then draw the same sizes, which SyncBN needs)."""
+    rank must use the same multi_scale_seed (the ranks then draw the same sizes, which SyncBN needs).
+    ema=True: YOLOv5's ModelEMA (engine/ema.py) - an exponential moving average of parameters and BatchNorm running statistics
+    with decay ema_decay * (1 - exp(-updates / ema_tau)), built with the optimizer and readable as `self.ema`.  optimize() calls
+    `ema.update()` after every optimizer step - one kodhip_ema_update launch behind the step, outside any captured graph - and
+    validate() runs under `ema.applied()`, i.e. reports the averaged model as train.py does; the network's own weights are
+    back, bit for bit, when it returns.  Data parallel: every rank forms the same parameter average without a collective;
+    without SyncBN the running statistics and their averages are per rank."""
 
     def __init__(self, net, loss, anchor_info: LayerwiseAnchorInfo, smart_optimizer: Optional[SmartOptimizer] = None,
                  lr_scheduler: Optional[Callable] = None,
@@ -70,7 +76,8 @@ class DefaultYolov5Experiment:
                  eval_fused: Optional[bool] = None, val_confusion: bool = False, val_confusion_conf: float = 0.25,
                  val_confusion_iou: float = 0.45, val_augment: bool = False, val_metrics: bool = False,
                  val_max_graphs: int = 8, multi_scale: bool = False, multi_scale_range=(0.5, 1.5),
-                 multi_scale_interval: int = 1, multi_scale_max_graphs: Optional[int] = None, multi_scale_seed: int = 0):
+                 multi_scale_interval: int = 1, multi_scale_max_graphs: Optional[int] = None, multi_scale_seed: int = 0,
+                 ema: bool = False, ema_decay: float = 0.9999, ema_tau: float = 2000.0):
         if gradient_clip_algorithm not in CLIP_ALGORITHMS:
             raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected one of {CLIP_ALGORITHMS}")
         # Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm): handed to the FusedSGD / the captured step
@@ -125,6 +132,9 @@ class DefaultYolov5Experiment:
         self.multi_scale_range, self.multi_scale_interval = tuple(multi_scale_range), int(multi_scale_interval)
         self.multi_scale_max_graphs, self.multi_scale_seed = multi_scale_max_graphs, int(multi_scale_seed)
         self._ms_schedule, self._ms_pending, self._ms_pairs = None, None, {}
+        # ema: the ModelEMA is built with the optimizer (configure_optimizers); a state loaded before that waits in `_ema_pending`
+        self._ema_on, self.ema_decay, self.ema_tau = bool(ema), float(ema_decay), float(ema_tau)
+        self.ema, self._ema_pending = None, None
 
     # exp.py:156-162
     def configure_optimizers(self):
@@ -141,6 +151,12 @@ class DefaultYolov5Experiment:
             elif self.gradient_clip_val is not None and self.graphed:
                 raise RuntimeError("gradient_clip_val with graphed=True needs the HIP network's FusedSGD")
             self.scheduler = self.lr_scheduler(optimizer=self.optimizer, max_epochs=self.max_epochs)
+            if self._ema_on:
+                from ....engine.ema import ModelEMA
+                self.ema = ModelEMA(self.net, self.ema_decay, self.ema_tau)
+                if self._ema_pending is not None:
+                    self.ema.load_ema_state_dict(self._ema_pending)
+                    self._ema_pending = None
         return [self.optimizer], [self.scheduler]
 
     @property
@@ -196,6 +212,9 @@ class DefaultYolov5Experiment:
     # exp.py:164-185 + Lightning automatic optimisation
     def optimize(self, batch, num_training_batches: int):
         self.configure_optimizers()
+        if self.ema is not None and self.ema.is_applied:
+            raise RuntimeError("optimize() while ema.applied(): the step would train the averaged weights; leave the applied() "
+                               "block first")
         if self.graphed:
             return self._optimize_graphed(batch, num_training_batches)
         if self.multi_scale:
@@ -220,8 +239,30 @@ class DefaultYolov5Experiment:
                 self.optimizer.step()
         else:
             self.optimizer.step()
+        if self.ema is not None:
+            self.ema.update()
         self.global_step += 1
         return total
+
+    # ------------------------------------------------------------------ weight EMA
+    def ema_state_dict(self) -> Optional[dict]:
+        """the EMA's state (save_checkpoint(ema_state=...)); None without ema=True"""
+        if self.ema is not None:
+            return self.ema.ema_state_dict()
+        if self._ema_pending is not None:
+            return dict(self._ema_pending)
+        if not self._ema_on:
+            return None
+        self.configure_optimizers()
+        return self.ema.ema_state_dict()
+
+    def load_ema_state_dict(self, state: dict):
+        if not self._ema_on:
+            raise RuntimeError("load_ema_state_dict: the experiment was built without ema=True")
+        if self.ema is not None:
+            self.ema.load_ema_state_dict(state)
+        else:
+            self._ema_pending = dict(state)
 
     # ------------------------------------------------------------------ multi-scale
     def _multi_scale_holder(self):
@@ -301,6 +342,8 @@ class DefaultYolov5Experiment:
         lr, mom, wd = self.optimizer.hyper()
         total, (box, obj, cls) = self._gstep(images, targets, lr, mom, wd, 1.0 / self.optimizer.world_size,
                                              gradient_clip_val=self.optimizer.gradient_clip_val)
+        if self.ema is not None:              # behind the replay, on the same stream, outside the captured graph
+            self.ema.update()
         self.optimizer.steps_taken += 1
         # the replayed graph contains the SGD update: tell torch's bookkeeping that a step happened (LambdaLR.step() checks
         # optimizer._step_count to warn about a scheduler stepped before the optimizer)
@@ -339,7 +382,10 @@ class DefaultYolov5Experiment:
         _lib.limit_host_threads()
         if self.eval_fused is not None:
             self.net.fuse_eval(self.eval_fused)
-        with _gc_paused():
+        if self._ema_on:
+            self.configure_optimizers()
+        # ema=True: the averaged weights are in the network while the batches run (train.py validates ema.ema)
+        with _gc_paused(), (self.ema.applied() if self.ema is not None else contextlib.nullcontext()):
             for b in batches:
                 targets, dets = self.validation_step(b)
                 if extra:                  # every consumer takes the batch's boxes as one device upload
