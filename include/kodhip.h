@@ -399,14 +399,17 @@ int kodhip_compose_color(const void* pool, const void* descs, const void* biline
 /* ---- validation pre-processing: SampleReader (LongestMaxSize + PadIfNeeded(114), kod/data/sample_reader.py:16-40,
  *      102-136) + ValidationSampleAugmentor (ToFloat(255) + CHW, kod/data/augmentations/albu.py:91-119) ------------ */
 int kodhip_val_prep_desc_bytes(void);
-int kodhip_val_prep_batch(const void* pool, const void* descs /* device [B] */, float* out_f32, void* out_pairs,
-                          int B, int S, kodStream_t stream);
-/* kodhip_letterbox_batch: the same records and the same arithmetic, bit for bit (OpenCV's fixed-point INTER_LINEAR, padding
- * 114, / 255.f, the copy path when nothing is resized), on an H x W canvas: a record's top / left are PadIfNeeded's centre
- * position on that canvas (engine/rect.py rect_geometry; nh <= H and nw <= W are the caller's to hold).  out_f32 [B,3,H,W]
- * (8-byte aligned) and / or out_pairs bf16 [B,H,W/2,8] (16-byte aligned), W even; the network takes multiples of 32.  One
- * thread per pixel pair; every tap is one 4-byte load, so the pool must stay readable 1 byte behind its last image
- * (ImagePool leaves 8).  With H = W = S the outputs are kodhip_val_prep_batch's. */
+/* kodhip_letterbox_batch: B records of kodhip_val_prep_desc_bytes() bytes (data/device_pipeline.py VAL_DESC) letterboxed onto an
+ * H x W canvas - OpenCV's fixed-point INTER_LINEAR, padding 114, / 255.f, a copy path when nothing is resized.  A record's top /
+ * left are PadIfNeeded's centre position on that canvas (engine/tiles.py letterbox_geometry; nh <= H and nw <= W are the
+ * caller's to hold).  out_f32 [B,3,H,W] (8-byte aligned) and / or out_pairs bf16 [B,H,W/2,8] (16-byte aligned), W even,
+ * B <= 65535; the network takes multiples of 32.  One thread per pixel pair; every tap is one 4-byte load, so the pool must
+ * stay readable 1 byte behind its last image (ImagePool leaves 8).
+ * kodhip_val_prep_batch is kodhip_letterbox_batch with H = W = S: the same kernel under the same contract (since version 114:
+ * the readable byte behind the pool, the two alignments, B <= 65535, checked before the launch with errors that name
+ * val_prep_batch; before, it ran a kernel of its own that needed none of them). */
+int kodhip_val_prep_batch(const void* pool, const void* descs /* device [B] */, float* out_f32 /* or NULL */,
+                          void* out_pairs /* or NULL */, int B, int S, kodStream_t stream);
 int kodhip_letterbox_batch(const void* pool, const void* descs /* device [B] */, float* out_f32 /* or NULL */,
                            void* out_pairs /* or NULL */, int B, int H, int W, kodStream_t stream);
 /* kodhip_letterbox_frames: kodhip_letterbox_batch for video frames that are read WHERE THEY LIE (csrc/video.hip): no pool, no

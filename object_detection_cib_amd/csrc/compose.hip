@@ -186,17 +186,7 @@ __global__ __launch_bounds__(256) void compose_kernel(const unsigned char* pool,
       for (int c = 0; c < 3; ++c) v[k][c] = v[k][c] * r + ((float)q[c] / 255.f) * r1;
     }
   }
-  if (out_f32) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float2 o = {v[0][c], v[1][c]};
-      *reinterpret_cast<float2*>(out_f32 + ((size_t)(b * 3 + c) * S + y) * S + x0) = o;
-    }
-  }
-  if (out_pairs) {   // network input layout [B][S][S/2][8] = pixel pairs x 4 channels
-    bf16x8 o = {(bf16_t)v[0][0], (bf16_t)v[0][1], (bf16_t)v[0][2], (bf16_t)0.f, (bf16_t)v[1][0], (bf16_t)v[1][1], (bf16_t)v[1][2], (bf16_t)0.f};
-    *reinterpret_cast<bf16x8*>(out_pairs + ((size_t)(b * S + y) * S + x0) * 4) = o;
-  }
+  kod_store_input_pair(out_f32, out_pairs, b, y, x0 >> 1, S, S, v);
 }
 
 // ------------------------------------------------------------------ image_color_transforms (rare path, see the header)

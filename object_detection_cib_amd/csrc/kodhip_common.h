@@ -48,6 +48,24 @@ template <typename V> __device__ __forceinline__ V kod_load_once(const void* p) 
 __device__ __forceinline__ float bf2f(bf16_t v) { return (float)v; }
 __device__ __forceinline__ bf16_t f2bf(float v) { return (bf16_t)v; }
 
+// The network-input store of every front end (letterbox, frames, TTA views, multi-scale, compose): a thread's two pixels
+// x 3 channels at pair q of row y of image b on an H x W canvas (W even) - one float2 per fp32 plane [B][3][H][W] (8-byte
+// aligned) and / or one bf16x8 with zeroed 4th channels into the pair layout [B][H][W/2][8] (16-byte aligned); a null
+// pointer skips that output.
+__device__ __forceinline__ void kod_store_input_pair(float* out_f32, bf16_t* out_pairs, int b, int y, int q, int H, int W,
+                                                     const float v[2][3]) {
+  if (out_f32) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      *reinterpret_cast<float2*>(out_f32 + ((size_t)(b * 3 + c) * H + y) * W + 2 * q) = make_float2(v[0][c], v[1][c]);
+  }
+  if (out_pairs) {
+    bf16x8 o = {(bf16_t)v[0][0], (bf16_t)v[0][1], (bf16_t)v[0][2], (bf16_t)0.f,
+                (bf16_t)v[1][0], (bf16_t)v[1][1], (bf16_t)v[1][2], (bf16_t)0.f};
+    *reinterpret_cast<bf16x8*>(out_pairs + (((size_t)b * H + y) * (W >> 1) + q) * 8) = o;
+  }
+}
+
 __device__ __forceinline__ float silu_f(float z) { return z / (1.0f + __expf(-z)); }
 __device__ __forceinline__ float sigmoid_f(float z) { return 1.0f / (1.0f + __expf(-z)); }
 

@@ -1,5 +1,6 @@
-// OpenCV's fixed-point INTER_LINEAR coefficients (resize.cpp, 8-bit images), shared by the letterbox kernels of val_prep.hip
-// (images in the pool) and video.hip (frames where they lie): both must produce the same bits.
+// The validation letterbox (OpenCV's fixed-point INTER_LINEAR on 8-bit images, padding 114, / 255.f, a copy path when nothing
+// is resized) as ONE kernel body for the letterbox kernels of val_prep.hip (images in the pool) and video.hip (frames where
+// they lie): a kernel supplies its record type and how a source pixel is fetched, everything else is here.
 #pragma once
 #include "kodhip_common.h"
 
@@ -19,4 +20,68 @@ __device__ __forceinline__ void lin_coeff(int d, double scale, int n_src, bool c
   }
   w0 = sat16((1.f - f) * 2048.f);
   w1 = sat16(f * 2048.f);
+}
+
+// The two pixels of output pair xp of row dy of the resized image (d.nh x d.nw, `left` columns into the canvas); px keeps
+// what it holds (the pad) where the image does not reach.  Desc: a record with h, w, nh, nw, left, scale_x, scale_y (ValDesc,
+// KodFrameDesc).  Src: the source image - src.rows(r0, r1) names the two source rows of this thread (both in [0, h)), then
+// src.px(i, c) is pixel (row i = 0 | 1, column c in [0, w)) as u8 r | g << 8 | b << 16 (higher bits are ignored).
+template <typename Desc, typename Src>
+__device__ __forceinline__ void letterbox_pair(const Desc& d, int dy, int xp, Src src, int px[2][3]) {
+  const bool copy = d.nh == d.h && d.nw == d.w;
+  int r0 = dy, r1 = dy, b0 = 0, b1 = 0;
+  if (!copy) {
+    int sy;
+    lin_coeff(dy, d.scale_y, d.h, false, sy, b0, b1);
+    r0 = min(max(sy, 0), d.h - 1);
+    r1 = min(max(sy + 1, 0), d.h - 1);
+  }
+  src.rows(r0, r1);
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {             // (`left` may be odd: each pixel of the pair decides for itself)
+    const int dx = 2 * xp + k - d.left;
+    if (dx < 0 || dx >= d.nw) continue;
+    if (copy) {
+      const unsigned p = src.px(0, dx);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) px[k][c] = (p >> (8 * c)) & 255;
+    } else {
+      int sx, a0, a1;
+      lin_coeff(dx, d.scale_x, d.w, true, sx, a0, a1);
+      const int sx1 = min(sx + 1, d.w - 1);
+      const unsigned p00 = src.px(0, sx), p01 = src.px(0, sx1);
+      const unsigned p10 = src.px(1, sx), p11 = src.px(1, sx1);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int S0 = (int)((p00 >> (8 * c)) & 255) * a0 + (int)((p01 >> (8 * c)) & 255) * a1;
+        const int S1 = (int)((p10 >> (8 * c)) & 255) * a0 + (int)((p11 >> (8 * c)) & 255) * a1;
+        const int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
+        px[k][c] = min(max(v, 0), 255);
+      }
+    }
+  }
+}
+
+// One thread of a letterbox launch, grid (ceil(H * W/2 / 256), B): one pixel PAIR of a canvas row.  The index is flat over
+// H * W/2, so a 64-wide canvas still fills its blocks; the record is uniform over a block.  fill(d, dy, xp, px) is called for
+// the rows the image reaches and hands `letterbox_pair` its source; the pair leaves as u8 / 255.f through
+// kod_store_input_pair (one 16-byte store into the pair layout, one 8-byte store per fp32 plane).
+template <typename Desc, typename Fill>
+__device__ __forceinline__ void letterbox_thread(const Desc* __restrict__ descs, float* __restrict__ out_f32,
+                                                 bf16_t* __restrict__ out_pairs, int H, int W, Fill&& fill) {
+  const int b = blockIdx.y;
+  const int Wp = W >> 1;
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= H * Wp) return;
+  const int y = q / Wp, xp = q - y * Wp;
+  const Desc d = descs[b];
+  int px[2][3] = {{114, 114, 114}, {114, 114, 114}};
+  const int dy = y - d.top;
+  if (dy >= 0 && dy < d.nh) fill(d, dy, xp, px);
+  float v[2][3];
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[k][c] = (float)px[k][c] / 255.f;
+  kod_store_input_pair(out_f32, out_pairs, b, y, xp, H, W, v);
 }

@@ -4,7 +4,7 @@
 //
 //   tile_batch       : slot t = the S x S window of a u8 HWC pool image with its corner at (x0, y0), as fp32 [T][3][S][S]
 //                      and / or as the network's bf16 pixel pairs [T][S][S/2][8].  A pixel inside the image is (float)u8 / 255.f,
-//                      a pixel outside it 114 / 255.f - the values of val_prep_kernel (val_prep.hip), so a tile is
+//                      a pixel outside it 114 / 255.f - the values of the letterbox (kodhip_resize.h), so a tile is
 //                      bit-identical to a letterbox at scale 1.
 //   merge_detections : one greedy pass per image over the rows kodhip_nms_ex kept in each of its views (already in image
 //                      pixels).  Classes are compared directly - there is no class offset, which in fp32 costs ulps that

@@ -58,19 +58,7 @@ __global__ __launch_bounds__(256) void tta_view_kernel(TtaViewArgs a) {
       }
     }
   }
-  bf16x8 o;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) o[4 * k + c] = (bf16_t)v[k][c];
-    o[4 * k + 3] = (bf16_t)0.f;
-  }
-  *reinterpret_cast<bf16x8*>(a.pairs + (size_t)i * 8) = o;
-  if (a.f32) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      *reinterpret_cast<float2*>(a.f32 + ((size_t)(b * 3 + c) * a.Hp + y) * a.Wp + 2 * q) = make_float2(v[0][c], v[1][c]);
-  }
+  kod_store_input_pair(a.f32, a.pairs, b, y, q, a.Hp, a.Wp, v);    // (a.pairs is never null: the launcher checks)
 }
 
 }  // namespace

@@ -23,7 +23,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..engine.rect import rect_batches, rect_geometry
+from ..engine.rect import rect_batches
+from ..engine.tiles import letterbox_geometry                   # noqa: F401  (the one geometry; imported from here as well)
 from .detection import DetectionTarget
 
 
@@ -229,21 +230,29 @@ VAL_DESC = np.dtype([("off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("nh", "<i4"), 
                      ("left", "<i4"), ("scale_x", "<f8"), ("scale_y", "<f8")], align=True)
 
 
-def _py3round(v: float) -> int:
-    """albumentations' py3round (geometric/functional.py): exact halves round away from zero."""
-    if abs(round(v) - v) == 0.5:
-        return int(2.0 * round(v / 2.0))
-    return int(round(v))
-
-
-def letterbox_geometry(h: int, w: int, S: int):
-    """(new_h, new_w, pad_top, pad_left) of A.LongestMaxSize(S) followed by A.PadIfNeeded(S, S), centre position
-    (kod/data/sample_reader.py:16-40)."""
-    scale = S / float(max(w, h))
-    nh, nw = (_py3round(h * scale), _py3round(w * scale)) if scale != 1.0 else (h, w)
-    top = int((S - nh) / 2.0) if nh < S else 0
-    left = int((S - nw) / 2.0) if nw < S else 0
-    return nh, nw, top, left
+def letterbox_table(shapes: Sequence[Sequence[int]], image_size: int, first_index=0, canvas=None):
+    """(h, w) per image -> (VAL_DESC records without pool offsets, KodLetterbox rows float32 [n, 6]): the geometry of the
+    validation letterbox and its inverse - left, top, fp32(w / nw), fp32(h / nh), w, h, the quotients formed in double.
+    canvas (H, W): the same resize centred on an H x W canvas (engine/rect.py), top / left relative to it; None: the
+    image_size square.  A ValueError names image k as first_index + k (first_index a sequence: as first_index[k])."""
+    H, W = (None, None) if canvas is None else (int(canvas[0]), int(canvas[1]))
+    number = (lambda k: first_index + k) if isinstance(first_index, (int, np.integer)) else (lambda k: first_index[k])
+    descs = np.zeros(len(shapes), dtype=VAL_DESC)
+    boxes = np.zeros((len(shapes), 6), dtype=np.float32)
+    for k, (h, w) in enumerate(shapes):
+        h, w = int(h), int(w)
+        if h < 1 or w < 1:
+            raise ValueError(f"image {number(k)}: empty ({h} x {w})")
+        nh, nw, top, left = letterbox_geometry(h, w, image_size, H, W)
+        if canvas is not None and (nh > H or nw > W):
+            raise ValueError(f"image {number(k)}: {h} x {w} letterboxes to {nh} x {nw}, larger than the canvas {H} x {W}")
+        if nh < 1 or nw < 1:
+            raise ValueError(f"image {number(k)}: {h} x {w} letterboxes to {nh} x {nw} at image_size {image_size}")
+        d = descs[k]
+        d["h"], d["w"], d["nh"], d["nw"], d["top"], d["left"] = h, w, nh, nw, top, left
+        d["scale_x"], d["scale_y"] = 1.0 / (nw / float(w)), 1.0 / (nh / float(h))     # OpenCV: 1 / inv_scale
+        boxes[k] = (left, top, np.float32(w / float(nw)), np.float32(h / float(nh)), w, h)
+    return descs, boxes
 
 
 class DeviceValPipeline:
@@ -274,16 +283,12 @@ class DeviceValPipeline:
         its own to the network: a buffer set, and a capture where the validation forward is graphed."""
         B, S = len(batch_indices), self.S
         H, W = (S, S) if canvas is None else (int(canvas[0]), int(canvas[1]))
-        descs = np.zeros(B, dtype=VAL_DESC)
+        batch_indices = [int(i) for i in batch_indices]
+        descs, _ = letterbox_table([self.pool.shapes[i] for i in batch_indices], S, batch_indices, canvas)
+        descs["off"] = self.pool.offsets[np.asarray(batch_indices, dtype=np.int64)]
         targets = []
-        for k, i in enumerate(batch_indices):
-            h, w = self.pool.shapes[i]
-            nh, nw, top, left = letterbox_geometry(h, w, S) if canvas is None else rect_geometry(h, w, S, H, W)
-            if nh > H or nw > W:
-                raise ValueError(f"image {i}: {h} x {w} letterboxes to {nh} x {nw}, larger than the canvas {H} x {W}")
-            d = descs[k]
-            d["off"], d["h"], d["w"], d["nh"], d["nw"], d["top"], d["left"] = self.pool.offsets[i], h, w, nh, nw, top, left
-            d["scale_x"], d["scale_y"] = 1.0 / (nw / float(w)), 1.0 / (nh / float(h))     # OpenCV: 1 / inv_scale
+        for d, i in zip(descs, batch_indices):
+            h, w, nh, nw, top, left = (int(d[f]) for f in ("h", "w", "nh", "nw", "top", "left"))
             bb = np.asarray(self.boxes[i], dtype=np.float64).reshape(-1, 4).copy()
             if bb.size:          # albumentations keeps boxes normalised through the resize; the pad shifts pixels
                 bb[:, [0, 2]] = bb[:, [0, 2]] / w * nw + left
@@ -292,12 +297,8 @@ class DeviceValPipeline:
         d_dev = self._stager.upload(descs)
         img = torch.empty((B, 3, H, W), dtype=torch.float32, device=self.device) if out_f32 else None
         pairs = torch.empty((B, H, W // 2, 8), dtype=torch.bfloat16, device=self.device) if out_pairs else None
-        args = (self.pool.data.data_ptr(), d_dev.data_ptr(), img.data_ptr() if out_f32 else None,
-                pairs.data_ptr() if out_pairs else None, B)
-        stream = torch.cuda.current_stream().cuda_stream
-        if canvas is None:
-            _lib.check(_lib.lib().kodhip_val_prep_batch(*args, S, stream), "val_prep_batch")
-        else:
-            _lib.check(_lib.lib().kodhip_letterbox_batch(*args, H, W, stream), "letterbox_batch")
+        _lib.check(_lib.lib().kodhip_letterbox_batch(self.pool.data.data_ptr(), d_dev.data_ptr(), img.data_ptr() if out_f32 else None,
+                                                     pairs.data_ptr() if out_pairs else None, B, H, W,
+                                                     torch.cuda.current_stream().cuda_stream), "letterbox_batch")
         self._keep = d_dev
         return img, pairs, tuple(targets)

@@ -17,6 +17,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .device_pipeline import letterbox_table
+
 RGB24, BGR24, NV12, I420 = 0, 1, 2, 3
 FORMATS = {"rgb": RGB24, "bgr": BGR24, "nv12": NV12, "i420": I420}
 
@@ -256,7 +258,6 @@ def frame_table(frames: Sequence[Frame], image_size: int, first_index: int = 0, 
     """(FRAME_DESC records, KodLetterbox rows float32 [n, 6]) of frames letterboxed at image_size: `letterbox_table`'s geometry
     for their shapes (canvas None: the image_size square; (H, W): that canvas) plus each frame's plane addresses, pitches,
     format and matrix.  Host arithmetic only; raises ValueError("image <first_index + k>: ...") for a bad frame."""
-    from ..inference import letterbox_table                      # (inference imports this module)
     for k, f in enumerate(frames):
         f.check(first_index + k)
     geo, boxes = letterbox_table([(f.h, f.w) for f in frames], image_size, first_index, canvas)

@@ -17,7 +17,7 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
-from .tiles import GRID, _letterbox_geometry
+from .tiles import GRID, letterbox_geometry
 
 MIN_SIDE = 64                    # the smallest input side the network is tested at
 
@@ -34,18 +34,15 @@ def rect_canvas(shapes: Sequence[Sequence[int]], image_size: int, stride: int = 
     for h, w in shapes:
         if h < 1 or w < 1:
             raise ValueError(f"empty image ({h} x {w})")
-    sizes = [_letterbox_geometry(h, w, image_size)[:2] for h, w in shapes]
+    sizes = [letterbox_geometry(h, w, image_size)[:2] for h, w in shapes]
     side = lambda n: min(image_size, max(int(min_side), -(-n // stride) * stride))
     return side(max(nh for nh, _ in sizes)), side(max(nw for _, nw in sizes))
 
 
 def rect_geometry(h: int, w: int, image_size: int, H: int, W: int) -> Tuple[int, int, int, int]:
     """(new_h, new_w, pad_top, pad_left) of A.LongestMaxSize(image_size) followed by A.PadIfNeeded(H, W), centre position;
-    with H = W = image_size it is `letterbox_geometry`"""
-    nh, nw, _, _ = _letterbox_geometry(int(h), int(w), int(image_size))
-    top = int((H - nh) / 2.0) if nh < H else 0
-    left = int((W - nw) / 2.0) if nw < W else 0
-    return nh, nw, top, left
+    with H = W = image_size it is the square letterbox"""
+    return letterbox_geometry(h, w, image_size, H, W)
 
 
 def rect_order(shapes: Sequence[Sequence[int]]) -> np.ndarray:

@@ -14,7 +14,7 @@ their fp32 rounding happens where the table is built).
 """
 from __future__ import annotations
 
-from typing import List, NamedTuple, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 GRID = 32                                                        # the network's coarsest stride: the tile is a multiple
 
@@ -55,17 +55,28 @@ def axis_origins(n: int, tile: int, overlap_px: int) -> List[int]:
     return out
 
 
-def _letterbox_geometry(h: int, w: int, S: int):
-    # (data.device_pipeline.letterbox_geometry, which this module cannot import without torch; tests hold the two together)
-    def py3round(v):
-        if abs(round(v) - v) == 0.5:
-            return int(2.0 * round(v / 2.0))
-        return int(round(v))
+def _py3round(v: float) -> int:
+    """albumentations' py3round (geometric/functional.py): exact halves round away from zero."""
+    if abs(round(v) - v) == 0.5:
+        return int(2.0 * round(v / 2.0))
+    return int(round(v))
+
+
+def letterbox_geometry(h: int, w: int, S: int, H: Optional[int] = None, W: Optional[int] = None):
+    """(new_h, new_w, pad_top, pad_left) of A.LongestMaxSize(S) followed by A.PadIfNeeded(H, W), centre position
+    (kod/data/sample_reader.py:16-40); H, W None: the S x S square.  THE letterbox geometry of the package:
+    data.device_pipeline.letterbox_geometry and engine.rect.rect_geometry are this function (it lives here because this
+    module imports without torch)."""
+    h, w, S = int(h), int(w), int(S)
+    H, W = S if H is None else int(H), S if W is None else int(W)
     scale = S / float(max(w, h))
-    nh, nw = (py3round(h * scale), py3round(w * scale)) if scale != 1.0 else (h, w)
-    top = int((S - nh) / 2.0) if nh < S else 0
-    left = int((S - nw) / 2.0) if nw < S else 0
+    nh, nw = (_py3round(h * scale), _py3round(w * scale)) if scale != 1.0 else (h, w)
+    top = int((H - nh) / 2.0) if nh < H else 0
+    left = int((W - nw) / 2.0) if nw < W else 0
     return nh, nw, top, left
+
+
+_letterbox_geometry = letterbox_geometry
 
 
 def tile_plan(h: int, w: int, tile: int, overlap: float = 0.2, full_view: bool = True) -> TilePlan:
@@ -80,7 +91,7 @@ def tile_plan(h: int, w: int, tile: int, overlap: float = 0.2, full_view: bool =
     xs, ys = axis_origins(w, tile, o), axis_origins(h, tile, o)
     views = [TileView(False, x0, y0, (-x0, -y0, 1.0, 1.0, w, h)) for y0 in ys for x0 in xs]
     if full_view and not (len(views) == 1 and max(h, w) == tile):
-        nh, nw, top, left = _letterbox_geometry(h, w, tile)
+        nh, nw, top, left = letterbox_geometry(h, w, tile)
         if nh < 1 or nw < 1:
             raise ValueError(f"{h} x {w} letterboxes to {nh} x {nw} at {tile}")
         views.append(TileView(True, 0, 0, (left, top, w / float(nw), h / float(nh), w, h)))

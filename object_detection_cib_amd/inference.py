@@ -2,7 +2,7 @@
 coordinates out.
 
 Every stage runs on the device and is the one validation uses, so the network sees what it was trained and validated on:
-letterbox (`letterbox_geometry` + kodhip_val_prep_batch, csrc/val_prep.hip), the eval forward (eager, fused or replayed as
+letterbox (`letterbox_table` + kodhip_letterbox_batch, csrc/val_prep.hip), the eval forward (eager, fused or replayed as
 a hipGraph), the prediction decode (kodhip_decode) and the NMS in YOLOv5's detect.py form (kodhip_nms_ex: one label per box
 by default, optional class filter / class-agnostic suppression / smaller max_det), whose last launch maps the kept boxes
 from the letterboxed frame back into the source image.  `AugmentedDetector` is detect.py's `--augment`: the letterboxed batch
@@ -20,6 +20,7 @@ kodhip_letterbox_frames (csrc/video.hip), which reads the frames where they lie.
 """
 from __future__ import annotations
 
+import functools
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -29,10 +30,10 @@ from . import _lib
 from .core.nms import _key_cap, _workspace, fuse_detections, merge_detections, non_max_suppression
 from .core.tracking import ByteTracker, Tracks
 from .core.types import FeatureShape
-from .data.device_pipeline import VAL_DESC, ImagePool, _Stager, letterbox_geometry
+from .data.device_pipeline import VAL_DESC, ImagePool, _Stager, letterbox_table                 # noqa: F401  (re-exported)
 from .data.frames import FRAME_DESC, Frame, frame_table, upload_frames, wrap_frames
 from .engine.graphed import GraphCache
-from .engine.rect import rect_canvas, rect_geometry, rect_order
+from .engine.rect import rect_canvas, rect_order
 from .engine.tiles import tile_plan
 
 
@@ -65,31 +66,14 @@ def _chunk_tables(shapes, image_size: int, batch_size: int, rect: bool):
     return tables
 
 
-def letterbox_table(shapes: Sequence[Sequence[int]], image_size: int, first_index: int = 0, canvas=None):
-    """(h, w) per image -> (VAL_DESC records without pool offsets, KodLetterbox rows float32 [n, 6]): the geometry of the
-    validation letterbox and its inverse - left, top, fp32(w / nw), fp32(h / nh), w, h, the quotients formed in double.
-    canvas (H, W): the same resize centred on an H x W canvas (engine/rect.py), top / left relative to it; None: the
-    image_size square."""
-    descs = np.zeros(len(shapes), dtype=VAL_DESC)
-    boxes = np.zeros((len(shapes), 6), dtype=np.float32)
-    for k, (h, w) in enumerate(shapes):
-        h, w = int(h), int(w)
-        if h < 1 or w < 1:
-            raise ValueError(f"image {first_index + k}: empty ({h} x {w})")
-        if canvas is None:
-            nh, nw, top, left = letterbox_geometry(h, w, image_size)
-        else:
-            nh, nw, top, left = rect_geometry(h, w, image_size, int(canvas[0]), int(canvas[1]))
-            if nh > canvas[0] or nw > canvas[1]:
-                raise ValueError(f"image {first_index + k}: {h} x {w} letterboxes to {nh} x {nw}, larger than the canvas "
-                                 f"{int(canvas[0])} x {int(canvas[1])}")
-        if nh < 1 or nw < 1:
-            raise ValueError(f"image {first_index + k}: {h} x {w} letterboxes to {nh} x {nw} at image_size {image_size}")
-        d = descs[k]
-        d["h"], d["w"], d["nh"], d["nw"], d["top"], d["left"] = h, w, nh, nw, top, left
-        d["scale_x"], d["scale_y"] = 1.0 / (nw / float(w)), 1.0 / (nh / float(h))     # (as DeviceValPipeline.make_batch)
-        boxes[k] = (left, top, np.float32(w / float(nw)), np.float32(h / float(nh)), w, h)
-    return descs, boxes
+def _caller_order(order, results):
+    """results of images that were processed in `order` (None: as given), back in the caller's order"""
+    if order is None:
+        return results
+    back = [None] * len(results)
+    for k, r in zip(order, results):
+        back[k] = r
+    return back
 
 
 class Detector:
@@ -174,89 +158,71 @@ class Detector:
                 m.training = was
         return get_detections(FeatureShape(width=x.shape[3], height=x.shape[2]), res, self.anchor_info)
 
-    def _chunks(self, images):
-        """images in chunks of batch_size through letterbox, forward and NMS -> (real images of the chunk, the padded chunk's
-        PackedDetections), chunk after chunk"""
+    def _letterboxed(self, images, sort: bool = False):
+        """The input half of a call: checks, all geometry (a bad image raises here, before anything is uploaded or launched),
+        then chunk after chunk of batch_size images uploaded and letterboxed -> (order, iterator of (real images of the chunk,
+        x fp32 [B, 3, H, W], the padded chunk's KodLetterbox rows)).  sort: in rectangular mode the images are taken sorted by
+        aspect ratio (every chunk then holds alike shapes) and `order` holds their positions for `_caller_order`; otherwise
+        None."""
         images = list(images)
         _check_images(images, self.device)
-        # (all geometry first: a bad image raises before anything is uploaded or launched)
-        tables = _chunk_tables([im.shape[:2] for im in images], self.S, self.B, self.rect)
+        shapes = [im.shape[:2] for im in images]
+        order = None
+        if sort and self.rect and len(images) > 1:
+            letterbox_table(shapes, self.S)                       # (its ValueErrors name the caller's index)
+            order = rect_order(shapes).tolist()
+            images, shapes = [images[k] for k in order], [shapes[k] for k in order]
+        tables = _chunk_tables(shapes, self.S, self.B, self.rect)
         if _has_frames(images):            # one Frame sends the whole call through kodhip_letterbox_frames
             images = wrap_frames(images)
+        chunks = (images[c * self.B:(c + 1) * self.B] for c in range(len(tables)))
+        return order, ((len(chunk), *self._letterbox(chunk, *table)) for chunk, table in zip(chunks, tables))
+
+    def _detect(self, batches):
+        """`_letterboxed`'s chunks through forward and NMS -> (real images of the chunk, the padded chunk's PackedDetections),
+        chunk after chunk"""
         if self.eval_fused is not None:
             self.net.fuse_eval(self.eval_fused)
-        for c, (canvas, descs, boxes) in enumerate(tables):
-            chunk = images[c * self.B:(c + 1) * self.B]
-            x, boxes = self._letterbox(chunk, canvas, descs, boxes)
+        for n, x, boxes in batches:
             det = self._forward(x)
             out = non_max_suppression(det, self.conf_thres, self.iou_thres, self.classes, agnostic=self.agnostic,
                                       multi_label=self.multi_label, max_det=self.max_det, letterbox=boxes)
-            yield len(chunk), out
+            yield n, out
+
+    def _chunks(self, images):
+        """images, in the given order, in chunks of batch_size through letterbox, forward and NMS"""
+        return self._detect(self._letterboxed(images)[1])
 
     def _letterbox(self, chunk, canvas, descs, boxes):
         """one chunk on the device: the upload of its images and the letterbox launch -> (x fp32 [B, 3, H, W] on `canvas`,
-        the KodLetterbox rows of the padded chunk)"""
+        the KodLetterbox rows of the padded chunk).  Frames: planes in host memory go up in one pinned upload, the others are
+        read where they lie (kodhip_letterbox_frames); numpy images go into an ImagePool (kodhip_letterbox_batch)."""
+        B, (H, W), n = self.B, canvas, len(chunk)
+        lib = _lib.lib()
         if isinstance(chunk[0], Frame):
-            return self._letterbox_frames(chunk, canvas, boxes)
-        B, (H, W), n = self.B, canvas, len(chunk)
-        pool = ImagePool(chunk, self.device)
-        descs["off"] = pool.offsets
-        if n < B:              # pad with the last descriptor: the batch keeps its shape, the copies are dropped by the caller
-            descs = np.concatenate((descs, np.repeat(descs[-1:], B - n)))
-            boxes = np.concatenate((boxes, np.repeat(boxes[-1:], B - n, axis=0)))
-        d_dev = self._stager.upload(descs)
-        x = torch.empty((B, 3, H, W), dtype=torch.float32, device=self.device)
-        stream = torch.cuda.current_stream().cuda_stream
-        if self.rect:
-            _lib.check(_lib.lib().kodhip_letterbox_batch(pool.data.data_ptr(), d_dev.data_ptr(), x.data_ptr(), None, B, H, W, stream),
-                       "letterbox_batch")
+            assert lib.kodhip_frame_desc_bytes() == FRAME_DESC.itemsize
+            if self._frame_stager is None:
+                self._frame_stager = _Stager(self.device, depth=2)
+            src = upload_frames(chunk, self.device, self._frame_stager)          # (alive until the launch is queued)
+            descs, rows = frame_table(src, self.S, 0, canvas if self.rect else None)
+            assert np.array_equal(rows, boxes[:n])
+            launch, name = lib.kodhip_letterbox_frames, "letterbox_frames"
         else:
-            _lib.check(_lib.lib().kodhip_val_prep_batch(pool.data.data_ptr(), d_dev.data_ptr(), x.data_ptr(), None, B, H, stream),
-                       "val_prep_batch")
-        return x, boxes
-
-    def _letterbox_frames(self, chunk, canvas, boxes):
-        """`_letterbox` for a chunk of Frames: planes in host memory go up in one pinned upload, the others are read where
-        they lie; one kodhip_letterbox_frames launch on either canvas"""
-        B, (H, W), n = self.B, canvas, len(chunk)
-        assert _lib.lib().kodhip_frame_desc_bytes() == FRAME_DESC.itemsize
-        if self._frame_stager is None:
-            self._frame_stager = _Stager(self.device, depth=2)
-        frames = upload_frames(chunk, self.device, self._frame_stager)
-        descs, rows = frame_table(frames, self.S, 0, canvas if self.rect else None)
-        assert np.array_equal(rows, boxes[:n])
-        if n < B:              # pad with the last record, as `_letterbox` does
+            src = ImagePool(chunk, self.device)
+            descs["off"] = src.offsets
+            launch, name = functools.partial(lib.kodhip_letterbox_batch, src.data.data_ptr()), "letterbox_batch"
+        if n < B:              # pad with the last record: the batch keeps its shape, the copies are dropped by the caller
             descs = np.concatenate((descs, np.repeat(descs[-1:], B - n)))
             boxes = np.concatenate((boxes, np.repeat(boxes[-1:], B - n, axis=0)))
         d_dev = self._stager.upload(descs)
         x = torch.empty((B, 3, H, W), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib().kodhip_letterbox_frames(d_dev.data_ptr(), x.data_ptr(), None, B, H, W,
-                                                      torch.cuda.current_stream().cuda_stream), "letterbox_frames")
+        _lib.check(launch(d_dev.data_ptr(), x.data_ptr(), None, B, H, W, torch.cuda.current_stream().cuda_stream), name)
         return x, boxes
-
-    def _order(self, images):
-        """rect: the images' positions sorted by aspect ratio (every chunk then holds alike shapes), after the checks a call
-        in the caller's order would make; otherwise None"""
-        if not self.rect or len(images) < 2:
-            return None
-        _check_images(images, self.device)
-        shapes = [im.shape[:2] for im in images]
-        letterbox_table(shapes, self.S)                       # (its ValueErrors name the caller's index)
-        return rect_order(shapes).tolist()
 
     @torch.no_grad()
     def __call__(self, images: Sequence[np.ndarray]) -> List[torch.Tensor]:
-        images = list(images)
-        order = self._order(images)
-        results = []
-        for n, out in self._chunks(images if order is None else [images[k] for k in order]):
-            results.extend(out[:n])
-        if order is not None:
-            back = [None] * len(images)
-            for k, r in zip(order, results):
-                back[k] = r
-            results = back
-        return results
+        order, batches = self._letterboxed(images, sort=True)
+        return _caller_order(order, [r for n, out in self._detect(batches) for r in out[:n]])
 
 
 class AugmentedDetector(Detector):
@@ -334,25 +300,15 @@ class EnsembleDetector:
 
     @torch.no_grad()
     def __call__(self, images: Sequence[np.ndarray]) -> List[torch.Tensor]:
-        images = list(images)
-        _check_images(images, self.device)
-        first = self.members[0]
-        order = first._order(images)                        # rect: sorted by aspect ratio, as Detector does
-        if order is not None:
-            images = [images[k] for k in order]
-        tables = _chunk_tables([im.shape[:2] for im in images], self.S, self.B, self.rect)
-        if _has_frames(images):
-            images = wrap_frames(images)
+        # (checks, geometry, rect order, letterbox and chunk padding: Detector's, once for all members)
+        order, batches = self.members[0]._letterboxed(images, sort=True)
         if self.eval_fused is not None:
             for m in self.members:
                 m.net.fuse_eval(self.eval_fused)
         B, M = self.B, len(self.members)
         nms = dict(agnostic=self.agnostic, multi_label=self.multi_label, max_det=self.max_det)
         results = []
-        for c, (canvas, descs, boxes) in enumerate(tables):
-            chunk = images[c * B:(c + 1) * B]
-            n = len(chunk)
-            x, boxes = first._letterbox(chunk, canvas, descs, boxes)      # (padded with the last descriptor, as Detector does)
+        for n, x, boxes in batches:
             dets = [m._forward(x) for m in self.members]
             nc = {int(d.shape[2]) - 5 for d in dets}
             if len(nc) != 1:
@@ -371,12 +327,7 @@ class EnsembleDetector:
                     out = fuse_detections(rows, counts, np.arange(B + 1) * M, np.tile(self.weights, B), thres=self.fuse_thres,
                                           agnostic=self.agnostic, max_det=self.max_det)
             results.extend(out[:n])
-        if order is not None:
-            back = [None] * len(images)
-            for k, r in zip(order, results):
-                back[k] = r
-            results = back
-        return results
+        return _caller_order(order, results)
 
 
 TILE_DESC = np.dtype([("off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("x0", "<i4"), ("y0", "<i4")], align=True)
@@ -451,12 +402,11 @@ class TiledDetector(Detector):
     @torch.no_grad()
     def __call__(self, images: Sequence[np.ndarray]) -> List[torch.Tensor]:
         images = list(images)
-        for i, im in enumerate(images):
-            if isinstance(im, Frame):
-                raise ValueError(f"image {i}: TiledDetector takes numpy images only - its tile cutter reads the image pool, "
-                                 f"not a Frame's planes")
-            if not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
-                raise ValueError(f"image {i}: expected an HWC uint8 array with 3 channels")
+        i = next((i for i, im in enumerate(images) if isinstance(im, Frame)), len(images))
+        _check_images(images[:i])                                              # (the images before the first Frame)
+        if i < len(images):
+            raise ValueError(f"image {i}: TiledDetector takes numpy images only - its tile cutter reads the image pool, "
+                             f"not a Frame's planes")
         plans = self.plans([im.shape[:2] for im in images])                    # (all geometry first, as Detector)
         if not images:
             return []
@@ -494,8 +444,8 @@ class TiledDetector(Detector):
                 while e < c0 + B and slots[e][1].full == slots[k][1].full:
                     e += 1
                 if slots[k][1].full:
-                    _lib.check(lib.kodhip_val_prep_batch(pool.data.data_ptr(), v_dev.data_ptr() + k * VAL_DESC.itemsize,
-                                                         x[k - c0].data_ptr(), None, e - k, S, stream), "val_prep_batch")
+                    _lib.check(lib.kodhip_letterbox_batch(pool.data.data_ptr(), v_dev.data_ptr() + k * VAL_DESC.itemsize,
+                                                          x[k - c0].data_ptr(), None, e - k, S, S, stream), "letterbox_batch")
                 else:
                     _lib.check(lib.kodhip_tile_batch(pool.data.data_ptr(), t_dev.data_ptr() + k * TILE_DESC.itemsize,
                                                      x[k - c0].data_ptr(), None, e - k, S, stream), "tile_batch")

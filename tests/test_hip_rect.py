@@ -1,5 +1,5 @@
-"""Rectangular inference and validation on the device: kodhip_letterbox_batch (csrc/val_prep.hip) through the C ABI against
-`oracle.datapath.resize_linear_u8` pasted on a 114 canvas, and the front ends that use it - Detector / AugmentedDetector /
+"""Rectangular inference and validation on the device: kodhip_letterbox_batch and kodhip_val_prep_batch (the same launch on the
+square; csrc/val_prep.hip) through the C ABI against `oracle.datapath.resize_linear_u8` pasted on a 114 canvas, and the front ends that use it - Detector / AugmentedDetector /
 EnsembleDetector / TrackedDetector in rectangular mode (`rectangular()` / `rect=True`), the bounded graph cache,
 DeviceValPipeline.make_batch(canvas=...) and validate() over a rectangular plan - against "the long way round": the numpy batch on the chunk's canvas, the eval forward,
 `get_detections` and `non_max_suppression(letterbox=canvas table)`.
@@ -9,7 +9,7 @@ division, and both sides of every detector comparison run the same kernels on th
 are asserted (`pytest -s`).
 
 Measured on an MI355X: every comparison exact; the ten detector images form the canvases (64, 128), (128, 128), (128, 64) and keep
-28 - 247 rows each at conf 0.000445; the tracked clip emits 13 / 11 / 11 / 1 / 6 / 11 tracks; the 17 tests take 2.3 s.
+28 - 247 rows each at conf 0.000445; the tracked clip emits 13 / 11 / 11 / 1 / 6 / 11 tracks; the module takes under 3 s.
 """
 import numpy as np
 import pytest
@@ -148,6 +148,52 @@ def test_square_canvas_equals_val_prep_batch(size):
     b = _launch("kodhip_letterbox_batch", images, geo, (size, size))
     np.testing.assert_array_equal(_bits(a[0]), _bits(b[0]))
     np.testing.assert_array_equal(a[1], b[1])
+
+
+@pytest.mark.parametrize("size", [128, 160])
+def test_val_prep_batch_equals_numpy_bit_for_bit(size):
+    """kodhip_val_prep_batch on its own (it forwards to the letterbox launch, so the comparison above holds one kernel against
+    itself): against the numpy reference, both outputs together and each alone"""
+    images, geo = _kernel_case(size, size, seed=size)
+    want = np.stack([_paste(im, *g, size, size) for im, g in zip(images, geo)])
+    wp = _pairs_of(want)
+    x, p = _launch("kodhip_val_prep_batch", images, geo, (size,))
+    np.testing.assert_array_equal(_bits(x), _bits(want))
+    np.testing.assert_array_equal(p, wp)
+    np.testing.assert_array_equal(_bits(_launch("kodhip_val_prep_batch", images, geo, (size,), pairs=False)[0]), _bits(want))
+    np.testing.assert_array_equal(_launch("kodhip_val_prep_batch", images, geo, (size,), f32=False)[1], wp)
+
+
+# The smallest shape at which the flat index, the partial block and the odd-`left` pair logic can go wrong: a 6 x 10 canvas is 30
+# pairs in one partial block.  (h, w) of the source, (nh, nw, top, left): a copy; one pixel upscaled at odd top and left; a
+# downscale onto the whole canvas; a widened image at left = 1.  tests/test_hip_frames.py runs the same case through the frames.
+TINY_CANVAS = (6, 10)
+TINY_CASE = (((6, 10), (6, 10, 0, 0)), ((1, 1), (5, 5, 1, 3)), ((12, 20), (6, 10, 0, 0)), ((2, 4), (4, 8, 1, 1)))
+
+
+def test_tiny_canvas_equals_numpy_bit_for_bit():
+    H, W = TINY_CANVAS
+    rng = np.random.default_rng(6)
+    images = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for (h, w), _ in TINY_CASE]
+    geo = [g for _, g in TINY_CASE]
+    want = np.stack([_paste(im, *g, H, W) for im, g in zip(images, geo)])
+    wp = _pairs_of(want)
+    x, p = _launch("kodhip_letterbox_batch", images, geo, (H, W))
+    np.testing.assert_array_equal(_bits(x), _bits(want))
+    np.testing.assert_array_equal(p, wp)
+    np.testing.assert_array_equal(_bits(_launch("kodhip_letterbox_batch", images, geo, (H, W), pairs=False)[0]), _bits(want))
+    np.testing.assert_array_equal(_launch("kodhip_letterbox_batch", images, geo, (H, W), f32=False)[1], wp)
+
+
+def test_val_prep_batch_argument_checks_launch_nothing():
+    x = torch.full((1, 3, 64, 64), -7.0, device="cuda")
+    h = _lib.lib()
+    for args in ((None, 8, x.data_ptr(), None, 1, 64), (8, 8, None, None, 1, 64), (8, 8, x.data_ptr(), None, 0, 64),
+                 (8, 8, x.data_ptr(), None, 1, 63), (8, 8, x.data_ptr() + 4, None, 1, 64), (8, 8, None, x.data_ptr() + 8, 1, 64)):
+        assert h.kodhip_val_prep_batch(*args, stream()) < 0
+        assert b"val_prep_batch" in h.kodhip_last_error()
+    torch.cuda.synchronize()
+    assert bool((x == -7.0).all())
 
 
 def test_letterbox_batch_argument_checks_launch_nothing():

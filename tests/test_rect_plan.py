@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import predict_reference as R
-from object_detection_cib_amd.data.device_pipeline import letterbox_geometry
+from object_detection_cib_amd.data.device_pipeline import VAL_DESC, letterbox_geometry
 from object_detection_cib_amd.engine.rect import pixel_share, rect_batches, rect_canvas, rect_geometry, rect_order
 from object_detection_cib_amd.inference import letterbox_table
 
@@ -131,3 +131,35 @@ def test_table_on_a_canvas_and_back_to_image_pixels():
             assert np.abs(back - pts).max() <= tol, (h, w, np.abs(back - pts).max(), tol)
     with pytest.raises(ValueError, match="image 3"):
         letterbox_table([(640, 480)], S, first_index=3, canvas=(384, 640))
+
+
+def test_the_three_geometry_names_are_one_function():
+    """`letterbox_geometry` (data/device_pipeline.py), `rect_geometry` on the square (engine/rect.py) and
+    `tiles._letterbox_geometry` (engine/tiles.py) answer alike on a seeded set of shapes and on the exact halves"""
+    from object_detection_cib_amd.engine import tiles
+    rng = np.random.default_rng(11)
+    cases = [(int(h), int(w), S) for S in (64, 128, 640) for h, w in rng.integers(1, 2000, (120, 2))]
+    cases += [(h, w, S) for S in (64, 128, 640) for h, w in SHAPES]
+    assert len(cases) >= 400
+    for h, w, S in cases:
+        g = letterbox_geometry(h, w, S)
+        assert g == rect_geometry(h, w, S, S, S) == tiles._letterbox_geometry(h, w, S), (h, w, S)
+        assert all(type(v) is int for v in g)
+
+
+@pytest.mark.parametrize("canvas", [None, (384, 640)])
+def test_letterbox_table_records_are_the_geometry_field_by_field(canvas):
+    """what DeviceValPipeline.make_batch uploads (`letterbox_table`'s records plus the pool offsets): every field against
+    values formed here from the geometry, the two scales as OpenCV forms them (1 / inv_scale, in double)"""
+    S = 640
+    shapes = [(720, 1280), (360, 640), (63, 1280), (100, 300), (384, 640), (1, 9)]
+    descs, rows = letterbox_table(shapes, S, canvas=canvas)
+    assert descs.dtype == VAL_DESC and len(descs) == len(shapes) and not descs["off"].any()
+    for d, row, (h, w) in zip(descs, rows, shapes):
+        nh, nw, top, left = letterbox_geometry(h, w, S) if canvas is None else rect_geometry(h, w, S, *canvas)
+        assert (int(d["h"]), int(d["w"]), int(d["nh"]), int(d["nw"]), int(d["top"]), int(d["left"])) == (h, w, nh, nw, top, left)
+        assert float(d["scale_x"]) == 1.0 / (nw / float(w)) and float(d["scale_y"]) == 1.0 / (nh / float(h))
+        assert row.tolist() == [left, top, np.float32(w / float(nw)), np.float32(h / float(nh)), w, h]
+    # a sequence as first_index names each image by its own number (make_batch: the pool index)
+    with pytest.raises(ValueError, match="image 41: "):
+        letterbox_table([(360, 640), (1, 2000)], S, [40, 41], canvas)

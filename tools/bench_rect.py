@@ -7,9 +7,9 @@
 2. One replay of each detector's captured forward (GraphedEvalForward: eval forward + decode) on its canvas: device events around
    --reps replays per window, alternated.  This is the part the pixel share (0.75 for 4:3, 0.60 for 16:9) is about; the rest of a
    Detector call (the upload of the source images, the NMS) does not shrink with the canvas.
-3. kodhip_letterbox_batch against kodhip_val_prep_batch on the square canvas, same records, fp32 output as the Detector asks
-   for it and the bf16 pair output: device events around --reps launches per window, alternated; and the new kernel on the
-   rectangular canvas of the same images.
+3. kodhip_letterbox_batch (kodhip_val_prep_batch is the same launch with H = W = S) on the square canvas and on the rectangular
+   canvas of the same images, fp32 output as the Detector asks for it and the bf16 pair output: device events around --reps
+   launches per window, alternated.
 
 usage: python tools/bench_rect.py [--batch 16] [--size 640] [--nc 80] [--rounds 7] [--reps 50] [--images 128] [--calls 16] [--json PATH]"""
 import argparse, json, os, sys, time
@@ -61,7 +61,7 @@ def alternate(forms, measure):
 
 
 def kernel_forms(images, canvas):
-    """launches of the two letterbox kernels over one chunk's records -> {name: callable}; the buffers stay alive in `keep`"""
+    """launches of the letterbox kernel over one chunk's records on the two canvases -> {name: callable}; the buffers stay alive in `keep`"""
     lib, stream = _lib.lib(), torch.cuda.current_stream().cuda_stream
     pool = ImagePool(images, dev)
     shapes = [im.shape[:2] for im in images]
@@ -77,9 +77,6 @@ def kernel_forms(images, canvas):
             base = (pool.data.data_ptr(), d_dev.data_ptr(), xp, pp, B)
             forms[f"letterbox_batch {name} {H}x{W} {out}"] = lambda base=base, H=H, W=W: _lib.check(      # noqa: E731
                 lib.kodhip_letterbox_batch(*base, H, W, stream), "letterbox_batch")
-            if name == "square":
-                forms[f"val_prep_batch  {name} {H}x{W} {out}"] = lambda base=base: _lib.check(             # noqa: E731
-                    lib.kodhip_val_prep_batch(*base, S, stream), "val_prep_batch")
     return forms, keep
 
 
