@@ -319,6 +319,24 @@ int kodhip_sgd_nesterov_clipped(float* params, const float* grads, float* moment
 /* the gradients themselves, in place, over the counted elements: mode 0 g *= clip[4], mode 1 g = clamp(g, -clip[8], +clip[8]) */
 int kodhip_grad_clip_inplace(float* grads, const void* group_ids, const void* count_mask, long n, const float* clip,
                              int mode, kodStream_t stream);
+/* ---- Adam / AdamW (torch.optim.Adam, torch.optim.AdamW; single-tensor, non-capturable arithmetic) as one launch over the
+ * arenas, csrc/adam.hip.  hyper: device, kodhip_adam_hyper_floats() = 32 fp32, every per-group constant (3 groups: bias,
+ * decay, norm) formed by the caller in double as torch forms it and then rounded to fp32:
+ *   [0..2] nss = -(lr / (1 - beta1 ** step))   [3..5] beta2   [6..8] omb1 = 1 - beta1   [9] grad_scale (where
+ *   kodhip_grad_norm reads it)   [10] flags = 1 maximize + 2 decoupled weight decay (AdamW)   [11] spare
+ *   [12..14] omb2 = 1 - beta2   [15..17] bc2s = (1 - beta2 ** step) ** 0.5   [18..20] eps   [21..23] wd
+ *   [24..26] c_decay = 1 - lr * wd   [27..31] spare
+ * `step` is the caller's count: the block is rewritten before every step, also before every replay of a captured one.
+ * Per element, fp32, each operation rounded once:  gg = g * grad_scale; [clip]; maximize: gg = -gg;
+ *   Adam, wd != 0: gg = fma(p, wd, gg);  AdamW, wd != 0: p = p * c_decay;  m = fma(gg - m, omb1, m)  (torch's lerp_ for
+ *   beta1 >= 0.5);  v = fma(omb2 * gg, gg, v * beta2);  p = p + (nss * m) / (sqrt(v) / bc2s + eps).
+ * keep_mask (device, n bytes, may be NULL): 0 = element of a frozen tensor, untouched.  clip (may be NULL) with clip_mode
+ * 0: (g * grad_scale) * clip[4]; 1: clamp(g * grad_scale, -clip[8], +clip[8]) (a NaN stays a NaN); clip NULL needs
+ * clip_mode -1.  Refused before any launch (< 0, the text names adam_step): a NULL pointer, n <= 0 or n % 64 != 0, a clip
+ * mode without a clip block or the reverse, an unknown clip mode. */
+int kodhip_adam_hyper_floats(void);
+int kodhip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const void* group_ids,
+                     const void* keep_mask, long n, const float* hyper, const float* clip, int clip_mode, kodStream_t stream);
 /* ---- weight EMA (YOLOv5 ModelEMA: `v *= d; v += (1 - d) * msd[k]`), beside the step, never inside it ----------------
  * Up to 4 segments per launch; model_ptrs / shadow_ptrs / numels are HOST arrays of nseg entries (device pointers, element
  * counts) that travel by value in the kernel arguments.  Per element, fp32, every operation rounded on its own:

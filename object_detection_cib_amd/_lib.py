@@ -95,6 +95,8 @@ SIGNATURES = {
     "kodhip_grad_norm": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, i32, vp]),
     "kodhip_sgd_nesterov_clipped": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, vp]),
     "kodhip_grad_clip_inplace": (i32, [vp, vp, vp, i64, vp, i32, vp]),
+    "kodhip_adam_hyper_floats": (i32, []),
+    "kodhip_adam_step": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp]),
     "kodhip_ema_update": (i32, [vp, vp, vp, i32, f32, f32, vp]),
     "kodhip_ema_swap": (i32, [vp, vp, vp, i32, vp]),
     "kodhip_fill_u32": (i32, [vp, u32, i64, vp]),

@@ -1,5 +1,5 @@
 """Parameter side of the engine: flat fp32 arenas (masters, gradients x 2, momentum), BatchNorm statistic arenas, the
-bf16 MFMA operand packs and the fused SGD step.
+bf16 MFMA operand packs and the fused SGD and Adam / AdamW steps.
 
 Replaces what torch.optim.SGD's foreach kernels and autograd's .grad bookkeeping do for the reference
 (kod/nn/optim/smart.py:36-58, kod/lightning/experiments/yv5_baseline/exp.py:156-185): torch Parameters are views of ONE
@@ -21,6 +21,30 @@ from .graph import Graph, head_param
 
 def _pad(n: int, a: int = 64) -> int:
     return (n + a - 1) // a * a
+
+
+ADAM_HYPER_FLOATS = 32           # the device block of csrc/adam.hip; checked against kodhip_adam_hyper_floats() at allocation
+
+
+def adam_hyper_values(lr, betas, eps, weight_decay, step: int, grad_scale: float = 1.0, maximize: bool = False,
+                      decoupled: bool = False):
+    """The Adam hyper block (layout: include/kodhip.h, kodhip_adam_step) as Python doubles; the upload rounds them to fp32.
+    lr / eps / weight_decay: 3 values, betas: 3 pairs, for (bias_params, decay_params, norm_params); step: the 1-based
+    count of the step that will read the block.  Every constant is formed as torch's single-tensor, non-capturable Adam
+    forms it (torch/optim/adam.py): in doubles, from the host's step count."""
+    if step < 1:
+        raise ValueError(f"adam step {step}: the count of the step about to run, 1-based")
+    v = [0.0] * ADAM_HYPER_FLOATS
+    for k in range(3):
+        l, (b1, b2), e, wd = float(lr[k]), (float(betas[k][0]), float(betas[k][1])), float(eps[k]), float(weight_decay[k])
+        bias_correction1 = 1 - b1 ** step
+        bias_correction2 = 1 - b2 ** step
+        step_size = l / bias_correction1
+        v[k], v[3 + k], v[6 + k] = -step_size, b2, 1 - b1
+        v[12 + k], v[15 + k], v[18 + k], v[21 + k], v[24 + k] = 1 - b2, bias_correction2 ** 0.5, e, wd, 1 - l * wd
+    v[9] = float(grad_scale)
+    v[10] = (1.0 if maximize else 0.0) + (2.0 if decoupled else 0.0)
+    return tuple(v)
 
 
 def arena_layout(g: Graph, numel: Dict[str, int]):
@@ -225,6 +249,13 @@ class ArenaMixin:
         self._clip_ring = _StagingRing(4)
         self.clip[8] = float("inf")                    # input slot: max_norm / clamp value (set_clip); inf clips nothing
         self._clip_val = float("inf")
+        # Adam / AdamW (csrc/adam.hip): m_arena serves as exp_avg; exp_avg_sq and the hyper block exist once Adam is configured
+        # (configure_adam), never for SGD
+        self.v_arena = None
+        self.adam_hyper = None
+        self._adam_ring, self._adam_vals = None, None
+        self.adam_steps = 0               # Adam steps taken, as the optimizer counts them (set_adam_hyper)
+        self.adam_frozen = None           # frozenset of the names frozen at the first Adam step (they own no state)
 
     def _grad_view(self, name, arena=None):
         o, k = self.layout[name]
@@ -470,6 +501,78 @@ class ArenaMixin:
                                                            self.hyper.data_ptr(), self._stream()), "sgd_masked")
         self.param_version += 1
         self.note_sgd_step()
+
+    # ------------------------------------------------------------------ Adam / AdamW
+    def configure_adam(self):
+        """Allocate what Adam needs beside the SGD arenas, once: exp_avg_sq (the parameter arena's size) and the hyper block
+        with its staging ring.  exp_avg is m_arena."""
+        if self.v_arena is None:
+            n = self.lib.kodhip_adam_hyper_floats()
+            if n != ADAM_HYPER_FLOATS:
+                raise RuntimeError(f"libkodhip's Adam hyper block has {n} floats, the host lays out {ADAM_HYPER_FLOATS}")
+            self.v_arena = torch.zeros(self.n_arena, dtype=torch.float32, device=self.device)
+            self.adam_hyper = torch.zeros(n, dtype=torch.float32, device=self.device)
+            self._adam_ring = _StagingRing(n)
+
+    def set_adam_hyper(self, lr, betas, eps, weight_decay, step: int, grad_scale: float = 1.0, maximize: bool = False,
+                       decoupled: bool = False):
+        """Upload the Adam hyper block (adam_hyper_values) - outside any captured graph, like set_hyper.  step: the 1-based
+        count of the step about to run; the bias corrections are host values, so a replayed graph needs a new block before
+        every replay."""
+        self.configure_adam()
+        vals = adam_hyper_values(lr, betas, eps, weight_decay, step, grad_scale, maximize, decoupled)
+        self.adam_steps = int(step) - 1
+        if vals != self._adam_vals:
+            self._adam_ring.upload(self.adam_hyper, vals)
+            self._adam_vals = vals
+
+    def adam_step(self, lr, betas, eps, weight_decay, step: int, grad_scale: float = 1.0, maximize: bool = False,
+                  decoupled: bool = False):
+        """The eager route: wait for the gradients, upload the block, launch."""
+        self.wait_grads()
+        self.set_adam_hyper(lr, betas, eps, weight_decay, step, grad_scale, maximize, decoupled)
+        self.adam_step_device()
+
+    def _frozen_now(self):
+        fz = self.freeze_active()
+        return frozenset() if fz is None else frozenset(fz.frozen)
+
+    def check_adam_freeze(self):
+        """One host step count serves every tensor, so the freeze set is fixed by the first Adam step: a tensor that joins or
+        leaves later would need a count of its own (torch keeps one per tensor)."""
+        if self.adam_steps > 0 and self.adam_frozen is not None and self._frozen_now() != self.adam_frozen:
+            raise RuntimeError("the freeze set (requires_grad) changed after the first Adam step: the fused Adam keeps one step "
+                               "count for all tensors, so the set of frozen parameters must stay what it was at the first step "
+                               "(frozen from the start is supported); build a new optimizer to change it")
+
+    def adam_step_device(self):
+        """Adam / AdamW with whatever is in self.adam_hyper (device) - the graph-capturable form, with the same launches in
+        front as sgd_step_device(): the norm reduction when clipping by norm or tracking the norm, then ONE kodhip_adam_step
+        that consumes the clip block.  skip_nonfinite is refused: a step skipped on the device would not hold the host's step
+        count back."""
+        if self.clip_skip_nonfinite:
+            raise ValueError("skip_nonfinite with Adam is not supported: the bias corrections come from the host's step count, "
+                             "which a step skipped on the device would not hold back")
+        if self.v_arena is None:
+            raise RuntimeError("adam_step_device() before set_adam_hyper()")
+        self.check_adam_freeze()
+        algo = self.clip_algorithm
+        if algo == "norm" or self.track_grad_norm:
+            self.grad_norm_device(self.adam_hyper)
+        fz = self.freeze_active()
+        _lib.check(self.lib.kodhip_adam_step(
+            self.p_arena.data_ptr(), self.current_grad_arena().data_ptr(), self.m_arena.data_ptr(), self.v_arena.data_ptr(),
+            self.gid.data_ptr(), None if fz is None else self.keep_mask.data_ptr(), self.n_arena, self.adam_hyper.data_ptr(),
+            None if algo is None else self.clip.data_ptr(), -1 if algo is None else self.CLIP_MODES[algo], self._stream()),
+            "adam_step")
+        self.param_version += 1
+        self.note_adam_step()
+
+    def note_adam_step(self):
+        """one Adam step has run (eagerly, or inside a replayed graph)"""
+        if self.adam_steps == 0:
+            self.adam_frozen = self._frozen_now()
+        self.adam_steps += 1
 
     def note_sgd_step(self):
         """one optimizer step has run (eagerly, or inside a replayed graph): with dampening the first step's flag must leave

@@ -105,7 +105,8 @@ class GraphedTrainStep:
     def __init__(self, net, loss, batch_size: int, height: int, width: int, max_targets: int = 4096,
                  loss_scale: Optional[float] = None, input_pairs: bool = False,
                  gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
-                 skip_nonfinite: bool = False, track_grad_norm: bool = False, target_block: Optional["TargetBlock"] = None):
+                 skip_nonfinite: bool = False, track_grad_norm: bool = False, target_block: Optional["TargetBlock"] = None,
+                 optimizer: str = "sgd"):
         """input_pairs: batches arrive as bf16 pixel pairs [B, H, W/2, 8] (DeviceTrainPipeline.make_batch(out_pairs=True)) and
         are copied straight into the network's input buffer - no fp32 NCHW batch, no layout-change pass in the step.
         gradient_clip_val / gradient_clip_algorithm ("norm" | "value"): Lightning's Trainer arguments; the clipping runs
@@ -114,9 +115,21 @@ class GraphedTrainStep:
         momentum untouched and is counted in `skipped_steps`.  track_grad_norm: run the norm reduction without clipping.
         `grad_norm` (total, bias, decay, norm-group norms before clipping) and `skipped_steps` are static device tensors:
         reading them is the caller's synchronisation, the step has none.  target_block: a TargetBlock to read the targets from
-        instead of one of its own (MultiScaleTrainStep: one block for the steps of all its sizes)."""
+        instead of one of its own (MultiScaleTrainStep: one block for the steps of all its sizes).
+        optimizer: "sgd" (default) | "adam" - which fused update the captured step ends with (Engine.sgd_step_device /
+        adam_step_device, the latter for Adam and AdamW); baked in at capture() and guarded like the clip configuration.
+        With "adam", __call__ takes `adam=FusedAdam.hyper()` in place of (lr, momentum, weight_decay): the bias corrections
+        are host values formed from the step count, so EVERY call must bring the hyper of its step.  skip_nonfinite is
+        refused with "adam" (a skipped device step would not hold the host's count back), so is capture(preserve_state=False)
+        (its warm-up steps would move the moments without the count)."""
         if gradient_clip_algorithm not in ("norm", "value"):
             raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected 'norm' or 'value'")
+        if optimizer not in ("sgd", "adam"):
+            raise ValueError(f"optimizer {optimizer!r}: expected 'sgd' or 'adam'")
+        if optimizer == "adam" and skip_nonfinite:
+            raise ValueError("skip_nonfinite with optimizer='adam' is not supported: the bias corrections come from the host's "
+                             "step count, which a step skipped on the device would not hold back")
+        self.optimizer, self._optimizer = optimizer, None      # (_optimizer: what capture() baked in)
         self.gradient_clip_val = None if gradient_clip_val is None else float(gradient_clip_val)
         self.gradient_clip_algorithm = gradient_clip_algorithm
         self.skip_nonfinite, self.track_grad_norm = bool(skip_nonfinite), bool(track_grad_norm)
@@ -171,7 +184,10 @@ class GraphedTrainStep:
         total, lr = self.net.train_step(self.x, self.loss, self.shape, self.targets, self.scale, image_ready=self.input_pairs)
         self.eng.wait_grads()
         self.eng.configure_clip(*self._clip_config())
-        self.eng.sgd_step_device()
+        if self.optimizer == "adam":
+            self.eng.adam_step_device()
+        else:
+            self.eng.sgd_step_device()
         return total, (lr.localization.detach(), lr.objectness.detach(), lr.classification.detach())
 
     def _load(self, images: torch.Tensor, targets):
@@ -186,17 +202,31 @@ class GraphedTrainStep:
         if targets is not None:            # (None: a MultiScaleTrainStep has filled the shared block already)
             self._tb.load(targets)
 
-    def capture(self, images: torch.Tensor, targets, warmup: int = 2, preserve_state: bool = True):
+    def capture(self, images: torch.Tensor, targets, warmup: int = 2, preserve_state: bool = True, adam: Optional[dict] = None):
         """Runs `warmup` eager steps on this batch (allocations, lazy initialisation), then captures the step.
-        preserve_state: parameters, momentum and BatchNorm buffers are restored afterwards, so that capturing
-        does not move the training trajectory."""
+        preserve_state: parameters, momentum (with optimizer="adam": both moments) and BatchNorm buffers are restored
+        afterwards, so that capturing does not move the training trajectory.
+        adam (optimizer="adam"): the hyper the warm-up steps run with; left out, they run with the block the engine holds, or,
+        when it holds none yet, with a neutral one (lr 0)."""
         eng = self.eng
+        if self.optimizer == "adam":
+            if not preserve_state:
+                raise ValueError("capture(preserve_state=False) with optimizer='adam': the warm-up steps would move the moments "
+                                 "without the host's step count")
+            if adam is not None:
+                eng.set_adam_hyper(**adam)
+            elif eng.v_arena is None:
+                eng.set_adam_hyper([0.0] * 3, [(0.9, 0.999)] * 3, [1e-8] * 3, [0.0] * 3, step=1)
         eng.pin_shape(self.B, self.H, self.W)      # the graph bakes this shape's buffer addresses in (Engine.allocate)
         self._pins += 1
         self._load(images, targets)
         self._clip_cfg = self._clip_config()
+        self._optimizer = self.optimizer
         eng.set_clip(self.gradient_clip_val)
         state = (eng.p_arena, eng.m_arena, eng.rm_arena, eng.rv_arena, eng.nbt_arena, eng.clip)     # (clip: the skipped-steps count)
+        adam_steps = eng.adam_steps
+        if self.optimizer == "adam":
+            state = state + (eng.v_arena,)
         keep = [t.clone() for t in state] if preserve_state else None
         side = torch.cuda.Stream(device=eng.device)
         side.wait_stream(torch.cuda.current_stream())
@@ -216,14 +246,19 @@ class GraphedTrainStep:
             for t, k in zip(state, keep):
                 t.copy_(k)
             eng.mark_params_changed()
+        eng.adam_steps = adam_steps               # (the warm-up steps are not steps of the trajectory)
         return self
 
     def __call__(self, images: torch.Tensor, targets, lr: Optional[Sequence[float]] = None,
                  momentum: Optional[Sequence[float]] = None, weight_decay: Optional[Sequence[float]] = None,
-                 grad_scale: float = 1.0, gradient_clip_val=_KEEP, gradient_clip_algorithm: Optional[str] = None):
+                 grad_scale: float = 1.0, gradient_clip_val=_KEEP, gradient_clip_algorithm: Optional[str] = None,
+                 adam: Optional[dict] = None):
         """One replayed step on a new batch.  Returns (total, (box, obj, cls)) - static tensors that the next call
-        overwrites (clone to keep).  gradient_clip_val: a new max_norm / clamp value from this step on."""
-        self._prepare(lr, momentum, weight_decay, grad_scale, gradient_clip_val, gradient_clip_algorithm)
+        overwrites (clone to keep).  gradient_clip_val: a new max_norm / clamp value from this step on.
+        optimizer="adam": `adam=FusedAdam.hyper()` (Engine.set_adam_hyper's keywords: lr, betas, eps, weight_decay per group,
+        step, maximize, decoupled) takes the place of lr / momentum / weight_decay and is required at every call; grad_scale
+        applies as for SGD."""
+        self._prepare(lr, momentum, weight_decay, grad_scale, gradient_clip_val, gradient_clip_algorithm, adam)
         if self.eng.peer is not None:
             self.eng.peer.check()             # a failed SyncBN exchange of an earlier replay: raise, do not train on NaN
         self._load(images, targets)
@@ -240,6 +275,10 @@ class GraphedTrainStep:
 
     def _guard(self, freeze_flags, bn_flags, clip_cfg):
         """what the graph was captured with against what holds now (MultiScaleTrainStep checks every held step per call)"""
+        if self.optimizer != self._optimizer:
+            # the graph ends with the update launch of the optimizer it was captured with
+            raise RuntimeError(f"optimizer changed to {self.optimizer!r} after capture() with {self._optimizer!r}: the captured "
+                               "step holds the old update launch; build a new GraphedTrainStep and capture() again")
         if freeze_flags != self._freeze_flags:
             # the graph replays the backward program of the freeze set it was captured with
             raise RuntimeError("requires_grad changed after capture(): the captured step would train the old freeze set; "
@@ -254,7 +293,7 @@ class GraphedTrainStep:
                                "after capture(): the captured step holds the old launches; build a new GraphedTrainStep and "
                                "capture() again (gradient_clip_val itself may change per step)")
 
-    def _prepare(self, lr, momentum, weight_decay, grad_scale, gradient_clip_val, gradient_clip_algorithm):
+    def _prepare(self, lr, momentum, weight_decay, grad_scale, gradient_clip_val, gradient_clip_algorithm, adam=None):
         """everything of a call before the batch is loaded: the guards, the clip value and the hyper-parameters"""
         if self.graph is None:
             raise RuntimeError("call capture() first")
@@ -264,13 +303,24 @@ class GraphedTrainStep:
             self.gradient_clip_algorithm = gradient_clip_algorithm
         self._guard(self.eng.freeze_flags(), self.eng.bn_mode_flags(), self._clip_config())
         self.eng.set_clip(self.gradient_clip_val)
-        if lr is not None:
+        if self.optimizer == "adam":
+            if adam is None or lr is not None:
+                raise ValueError("optimizer='adam': pass adam=FusedAdam.hyper() at every call (the bias corrections of the step "
+                                 "are host values), not lr / momentum / weight_decay")
+            self.eng.set_adam_hyper(**adam, grad_scale=grad_scale)
+            self.eng.check_adam_freeze()
+        elif adam is not None:
+            raise ValueError("adam=... needs GraphedTrainStep(optimizer='adam')")
+        elif lr is not None:
             self.eng.set_hyper(lr, momentum, weight_decay, grad_scale)
 
     def _replay(self):
         self.graph.replay()
-        self.eng.param_version += 1           # the replayed SGD changed the parameters
-        self.eng.note_sgd_step()
+        self.eng.param_version += 1           # the replayed update changed the parameters
+        if self.optimizer == "adam":
+            self.eng.note_adam_step()
+        else:
+            self.eng.note_sgd_step()
         return self.total, self.parts
 
 

@@ -162,9 +162,17 @@ class MultiScaleTrainStep:
                  loss_scale: Optional[float] = None, input_pairs: bool = False,
                  gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
                  skip_nonfinite: bool = False, track_grad_norm: bool = False, *, scale_range=(0.5, 1.5),
-                 sizes: Optional[Sequence[int]] = None, interval: int = 1, seed: int = 0, max_graphs: Optional[int] = None):
+                 sizes: Optional[Sequence[int]] = None, interval: int = 1, seed: int = 0, max_graphs: Optional[int] = None,
+                 optimizer: str = "sgd"):
+        """optimizer: "sgd" | "adam", passed to every GraphedTrainStep it builds (with "adam" a call takes `adam=` like
+        GraphedTrainStep.__call__)."""
         if gradient_clip_algorithm not in ("norm", "value"):
             raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected 'norm' or 'value'")
+        if optimizer not in ("sgd", "adam"):
+            raise ValueError(f"optimizer {optimizer!r}: expected 'sgd' or 'adam'")
+        if optimizer == "adam" and skip_nonfinite:
+            raise ValueError("skip_nonfinite with optimizer='adam' is not supported (the step count lives on the host)")
+        self.optimizer = optimizer
         if max_graphs is not None and int(max_graphs) < 1:
             raise ValueError(f"max_graphs {max_graphs}: expected >= 1 or None")
         self.net, self.loss = net, loss
@@ -219,11 +227,12 @@ class MultiScaleTrainStep:
     def _new_step(self, h: int, w: int) -> GraphedTrainStep:
         return GraphedTrainStep(self.net, self.loss, self.B, h, w, self.cap, self.loss_scale, True,
                                 self.gradient_clip_val, self.gradient_clip_algorithm, self.skip_nonfinite,
-                                self.track_grad_norm, target_block=self._tb)
+                                self.track_grad_norm, target_block=self._tb, optimizer=self.optimizer)
 
     def __call__(self, images: torch.Tensor, targets, lr: Optional[Sequence[float]] = None,
                  momentum: Optional[Sequence[float]] = None, weight_decay: Optional[Sequence[float]] = None,
-                 grad_scale: float = 1.0, gradient_clip_val=_KEEP, gradient_clip_algorithm: Optional[str] = None):
+                 grad_scale: float = 1.0, gradient_clip_val=_KEEP, gradient_clip_algorithm: Optional[str] = None,
+                 adam: Optional[dict] = None):
         """One step on a new base-size batch at the size the schedule draws.  Returns (total, (box, obj, cls)) - static
         tensors of that size's step, overwritten by its next replay (clone to keep)."""
         eng = self.eng
@@ -256,9 +265,10 @@ class MultiScaleTrainStep:
             buf = eng.image_buffer(self.B, h, w)
             resize_batch(eng.lib, self.x, buf, h, w, boxes_in=self._tb.boxes, boxes_out=self._tb.boxes, n=n)
             if fresh:
-                if lr is not None:
+                if lr is not None and self.optimizer == "sgd":
                     eng.set_hyper(lr, momentum, weight_decay, grad_scale)
-                step.capture(buf, None, preserve_state=True)
+                step.capture(buf, None, preserve_state=True,
+                             adam=None if adam is None else dict(adam, grad_scale=grad_scale))
                 self.steps[(h, w)] = step
                 self.captures += 1
         except torch.cuda.OutOfMemoryError as e:
@@ -268,7 +278,7 @@ class MultiScaleTrainStep:
                 f"out of device memory while building the multi-scale step of size {h} x {w} ({len(self.steps)} sizes are held; every "
                 f"size keeps a full buffer set): narrow scale_range, list fewer sizes, bound max_graphs, or raise interval"
             ) from e
-        step._prepare(lr, momentum, weight_decay, grad_scale, self.gradient_clip_val, self.gradient_clip_algorithm)
+        step._prepare(lr, momentum, weight_decay, grad_scale, self.gradient_clip_val, self.gradient_clip_algorithm, adam)
         if eng.peer is not None:
             eng.peer.check()                  # a failed SyncBN exchange of an earlier replay: raise, do not train on NaN
         return step._replay()

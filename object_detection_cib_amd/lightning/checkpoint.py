@@ -8,7 +8,9 @@ The reference trains a LightningModule `DefaultYolov5Experiment` whose network i
     state_dict         {"net." + key: tensor}  - the network's 360 keys (yv5s), fp32
     optimizer_states   [torch.optim.SGD.state_dict()] for the optimizer SmartOptimizer builds
                        (kod/nn/optim/smart.py:20-60): groups bias_params | decay_params | norm_params, parameters
-                       numbered consecutively group by group in module-walk order, state[i]["momentum_buffer"]
+                       numbered consecutively group by group in module-walk order, state[i]["momentum_buffer"];
+                       for FusedAdam / FusedAdamW torch.optim.Adam.state_dict(): state[i] = {"step" (float32 scalar
+                       tensor), "exp_avg", "exp_avg_sq"}
     lr_schedulers      [LambdaLR.state_dict()]
     epoch, global_step, pytorch-lightning_version
 
@@ -43,8 +45,98 @@ def optimizer_param_order(net: nn.Module) -> Tuple[List[str], List[str], List[st
     return bias, decay, norm
 
 
+def _is_adam(optimizer) -> bool:
+    from ..nn.optim.smart import FusedAdam
+    return isinstance(optimizer, FusedAdam)
+
+
+def adam_param_group(g: Dict, ids: List[int]) -> Dict:
+    """One param_groups entry with the keys of the installed torch.optim.Adam(...).state_dict(), plus name and initial_lr."""
+    ref = torch.optim.Adam([torch.zeros(1)]).state_dict()["param_groups"][0]
+    out = {}
+    for k, default in ref.items():
+        if k != "params":
+            out[k] = g.get(k, default)
+    out["lr"], out["eps"], out["weight_decay"] = float(g["lr"]), float(g["eps"]), float(g["weight_decay"])
+    out["betas"] = (float(g["betas"][0]), float(g["betas"][1]))
+    out["name"] = g["name"]
+    out["initial_lr"] = float(g.get("initial_lr", g["lr"]))
+    out["params"] = ids
+    return out
+
+
+def adam_state_dict(groups, param_groups, shapes: Dict, layout: Dict, exp_avg, exp_avg_sq, steps_taken: int, frozen=()) -> Dict:
+    """torch.optim.Adam.state_dict() layout from flat arenas (any device; a test may pass CPU tensors): per stepped tensor
+    {"step": float32 scalar tensor, "exp_avg", "exp_avg_sq"}; before the first step, and for a tensor frozen from the start,
+    no state - as with torch.  groups: parameter names per group (optimizer_param_order), layout: name -> (offset, numel)."""
+    state, pgs, idx = {}, [], 0
+    for names, g in zip(groups, param_groups):
+        ids = []
+        for n in names:
+            if steps_taken > 0 and n not in frozen:
+                off, numel = layout[n]
+                state[idx] = {"step": torch.tensor(float(steps_taken), dtype=torch.float32),
+                              "exp_avg": exp_avg[off:off + numel].view(shapes[n]).detach().clone().cpu(),
+                              "exp_avg_sq": exp_avg_sq[off:off + numel].view(shapes[n]).detach().clone().cpu()}
+            ids.append(idx)
+            idx += 1
+        pgs.append(adam_param_group(g, ids))
+    return {"state": state, "param_groups": pgs}
+
+
+def _adam_optimizer_state_dict(net, optimizer) -> Dict:
+    groups = optimizer_param_order(net)
+    shapes = {n: tuple(p.shape) for n, p in net.named_parameters()}
+    steps = int(getattr(optimizer, "steps_taken", 0))
+    if steps == 0:
+        return adam_state_dict(groups, optimizer.param_groups, shapes, {}, None, None, 0)
+    eng = net.engine()
+    return adam_state_dict(groups, optimizer.param_groups, shapes, eng.layout, eng.m_arena, eng.v_arena, steps,
+                           eng.adam_frozen or ())
+
+
+def _load_adam_optimizer_state_dict(net, optimizer, sd: Dict):
+    """The reverse of adam_state_dict: moments into the arenas, the step count into the optimizer.  One count serves all
+    tensors, so the stepped tensors must agree on it; tensors without state are the set frozen from the start."""
+    groups = optimizer_param_order(net)
+    params = dict(net.named_parameters())
+    assert len(sd["param_groups"]) == 3, "expected SmartOptimizer's three parameter groups"
+    eng = net.engine()
+    eng.configure_adam()
+    eng.m_arena.zero_()
+    eng.v_arena.zero_()
+    steps, got = set(), set()
+    for names, g_saved, g in zip(groups, sd["param_groups"], optimizer.param_groups):
+        assert len(names) == len(g_saved["params"]), (g_saved.get("name"), len(names), len(g_saved["params"]))
+        for key in ("lr", "betas", "eps", "weight_decay", "initial_lr"):
+            if key in g_saved:
+                g[key] = tuple(g_saved[key]) if key == "betas" else g_saved[key]
+        for n, i in zip(names, g_saved["params"]):
+            st = sd["state"].get(i, sd["state"].get(str(i)))
+            if not st:
+                continue
+            off, numel = eng.layout[n]
+            for key, arena in (("exp_avg", eng.m_arena), ("exp_avg_sq", eng.v_arena)):
+                buf = st[key]
+                assert tuple(buf.shape) == tuple(params[n].shape), (n, key, buf.shape, params[n].shape)
+                arena[off:off + numel].copy_(buf.reshape(-1).to(arena.device, torch.float32))
+            steps.add(int(float(st["step"])))
+            got.add(n)
+    if len(steps) > 1:
+        raise RuntimeError(f"the Adam state holds different step counts {sorted(steps)}: the fused Adam keeps one count for all "
+                           "tensors (a freeze set that changed during training is not supported)")
+    optimizer.steps_taken = steps.pop() if steps else 0
+    eng.adam_steps = optimizer.steps_taken
+    eng.adam_frozen = frozenset(n for n in eng.layout if n not in got) if got else None
+    eng._adam_vals = None
+    return len(got)
+
+
 def optimizer_state_dict(net, optimizer) -> Dict:
-    """torch.optim.SGD.state_dict() layout for a SmartSGD over `net` (momentum read from the engine's arena)."""
+    """torch.optim.SGD.state_dict() layout for a SmartSGD over `net` (momentum read from the engine's arena); for a FusedAdam
+    / FusedAdamW torch.optim.Adam's (both moments and the step count)."""
+    if _is_adam(optimizer):
+        return _adam_optimizer_state_dict(net, optimizer)
     groups = optimizer_param_order(net)
     params = dict(net.named_parameters())
     eng = net.engine() if getattr(optimizer, "steps_taken", 0) > 0 else None
@@ -66,6 +158,8 @@ def optimizer_state_dict(net, optimizer) -> Dict:
 
 
 def load_optimizer_state_dict(net, optimizer, sd: Dict):
+    if _is_adam(optimizer):
+        return _load_adam_optimizer_state_dict(net, optimizer, sd)
     groups = optimizer_param_order(net)
     params = dict(net.named_parameters())
     assert len(sd["param_groups"]) == 3, "expected SmartOptimizer's three parameter groups"

@@ -17,7 +17,7 @@ from .... import _lib
 from ....core.types import FeatureShape
 from ....core.nms import non_max_suppression
 from ....core.label_assignment.yv5 import BatchedTargets
-from ....nn.optim.smart import SmartOptimizer, FusedSGD, CLIP_ALGORITHMS
+from ....nn.optim.smart import SmartOptimizer, FusedSGD, FusedAdam, CLIP_ALGORITHMS
 from ....nn.optim.schedulers import LinearScheduler
 from ...callbacks.map_eval import DeviceMAPEvaluator
 from .layers import get_detections, get_detections_augmented
@@ -46,6 +46,8 @@ class DefaultYolov5Experiment:
     optimizer_warmup_updater, val_nms_conf_threshold, val_nms_iou_threshold); the keyword-only extras stand in for
     what Lightning's Trainer supplies (`trainer.max_epochs`) or are build-side switches.  smart_optimizer /
     lr_scheduler default to the reference's configs (configs/nn/optimizers/smart_sgd.yaml, schedulers/linear.yaml).
+    smart_optimizer over torch.optim.SGD, Adam or AdamW: with the HIP network the optimizer is FusedSGD / FusedAdam / FusedAdamW
+    (nn/optim/smart.py) and every route below - eager, graphed, multi-scale, EMA, clipping - runs its fused update.
     val_augment=True: validation_step runs YOLOv5's test-time augmentation (val.py --augment) - three views of the batch, one
     NMS over the merged predictions.  The merged tensor has 45147 rows at 640 px against 25200, so the NMS key workspace
     roughly doubles: at nc = 80, 45147 * 80 keys need a 4 Mi-key capacity per image, against 2 Mi without it.
@@ -140,7 +142,7 @@ class DefaultYolov5Experiment:
     def configure_optimizers(self):
         if self.optimizer is None:
             self.optimizer = self.smart_optimizer(self.net)
-            if isinstance(self.optimizer, FusedSGD):
+            if isinstance(self.optimizer, (FusedSGD, FusedAdam)):
                 self.optimizer.world_size = self.world_size
                 if self.gradient_clip_val is not None:
                     # (the reference's partial(torch.optim.SGD, ...) knows no such keywords; a partial(FusedSGD, ...) that
@@ -149,7 +151,7 @@ class DefaultYolov5Experiment:
                     self.optimizer.gradient_clip_algorithm = self.gradient_clip_algorithm
                     self.optimizer.track_grad_norm = True          # the grad_norm metric, also under "value"
             elif self.gradient_clip_val is not None and self.graphed:
-                raise RuntimeError("gradient_clip_val with graphed=True needs the HIP network's FusedSGD")
+                raise RuntimeError("gradient_clip_val with graphed=True needs the HIP network's FusedSGD / FusedAdam")
             self.scheduler = self.lr_scheduler(optimizer=self.optimizer, max_epochs=self.max_epochs)
             if self._ema_on:
                 from ....engine.ema import ModelEMA
@@ -167,7 +169,7 @@ class DefaultYolov5Experiment:
     def _clipping(self) -> bool:
         opt = self.optimizer
         return (self.gradient_clip_val is not None
-                or (isinstance(opt, FusedSGD) and (opt.gradient_clip_val is not None or opt.track_grad_norm)))
+                or (isinstance(opt, (FusedSGD, FusedAdam)) and (opt.gradient_clip_val is not None or opt.track_grad_norm)))
 
     def get_metrics_to_display(self):
         return ["box", "cls", "obj"] + (["grad_norm"] if self._clipping() else [])
@@ -224,8 +226,8 @@ class DefaultYolov5Experiment:
         total.backward()
         self._warmup(num_training_batches)
         if self._clipping():
-            if isinstance(self.optimizer, FusedSGD):
-                # clipping is inside FusedSGD.step(); the norm stays a device scalar until the metrics are fetched
+            if isinstance(self.optimizer, (FusedSGD, FusedAdam)):
+                # clipping is inside FusedSGD.step() / FusedAdam.step(); the norm stays a device scalar until the metrics are fetched
                 self.optimizer.step()
                 self.logged["grad_norm"] = self.net.engine().clip[0].clone()
             else:          # a torch network / optimizer: what Lightning's own hook does between backward and step
@@ -314,6 +316,15 @@ class DefaultYolov5Experiment:
                 self.optimizer_warmup_updater(current_step=self.global_step, current_epoch=self.current_epoch,
                                               max_warmup_steps=nw, sch_fn=self.sch_fn, optimizer=self.optimizer)
 
+    def _graphed_optimizer(self) -> str:
+        """which fused update the captured step ends with (GraphedTrainStep(optimizer=...))"""
+        if isinstance(self.optimizer, FusedAdam):
+            return "adam"
+        if isinstance(self.optimizer, FusedSGD):
+            return "sgd"
+        raise RuntimeError(f"graphed=True needs the HIP network's FusedSGD or FusedAdam (torch.optim.SGD / Adam / AdamW through "
+                           f"SmartOptimizer), not {type(self.optimizer).__name__}")
+
     def _optimize_graphed(self, batch, num_training_batches: int):
         from ....engine.graphed import GraphedTrainStep
         images, targets, _ = batch
@@ -326,7 +337,8 @@ class DefaultYolov5Experiment:
                                               gradient_clip_algorithm=opt.gradient_clip_algorithm,
                                               skip_nonfinite=opt.skip_nonfinite, track_grad_norm=opt.track_grad_norm,
                                               scale_range=self.multi_scale_range, interval=self.multi_scale_interval,
-                                              seed=self.multi_scale_seed, max_graphs=self.multi_scale_max_graphs)
+                                              seed=self.multi_scale_seed, max_graphs=self.multi_scale_max_graphs,
+                                              optimizer=self._graphed_optimizer())
             if self._ms_pending is not None:
                 self._gstep.load_state_dict(self._ms_pending)
                 self._ms_pending = None
@@ -337,15 +349,20 @@ class DefaultYolov5Experiment:
                                            gradient_clip_val=opt.gradient_clip_val,
                                            gradient_clip_algorithm=opt.gradient_clip_algorithm,
                                            skip_nonfinite=opt.skip_nonfinite,
-                                           track_grad_norm=opt.track_grad_norm).capture(images, targets)
+                                           track_grad_norm=opt.track_grad_norm,
+                                           optimizer=self._graphed_optimizer()).capture(images, targets)
         self._warmup(num_training_batches)
-        lr, mom, wd = self.optimizer.hyper()
-        total, (box, obj, cls) = self._gstep(images, targets, lr, mom, wd, 1.0 / self.optimizer.world_size,
-                                             gradient_clip_val=self.optimizer.gradient_clip_val)
+        if isinstance(self.optimizer, FusedAdam):
+            total, (box, obj, cls) = self._gstep(images, targets, grad_scale=1.0 / self.optimizer.world_size,
+                                                 gradient_clip_val=self.optimizer.gradient_clip_val, adam=self.optimizer.hyper())
+        else:
+            lr, mom, wd = self.optimizer.hyper()
+            total, (box, obj, cls) = self._gstep(images, targets, lr, mom, wd, 1.0 / self.optimizer.world_size,
+                                                 gradient_clip_val=self.optimizer.gradient_clip_val)
         if self.ema is not None:              # behind the replay, on the same stream, outside the captured graph
             self.ema.update()
         self.optimizer.steps_taken += 1
-        # the replayed graph contains the SGD update: tell torch's bookkeeping that a step happened (LambdaLR.step() checks
+        # the replayed graph contains the optimizer update: tell torch's bookkeeping that a step happened (LambdaLR.step() checks
         # optimizer._step_count to warn about a scheduler stepped before the optimizer)
         self.optimizer._step_count = getattr(self.optimizer, "_step_count", 0) + 1
         self.logged = {"obj": obj, "cls": cls, "box": box}
