@@ -351,6 +351,15 @@ int kodhip_ema_update(const float* const* model_ptrs, float* const* shadow_ptrs,
 /* exchanges the contents of the paired segments (numels in 32-bit words: a pure copy, NaN payloads included, so an int64
  * buffer goes as two words per value); the same tables, rules and refusals as kodhip_ema_update */
 int kodhip_ema_swap(void* const* a_ptrs, void* const* b_ptrs, const long* numels, int nseg, kodStream_t stream);
+/* ---- gradient accumulation (Lightning's accumulate_grad_batches; autograd's `.grad += g`), csrc/accumulate.hip ----
+ * acc <- grad (mode 1: a copy of 32-bit words) or acc <- fl(acc + grad) (mode 0, __fadd_rn, one rounding);
+ * mode 2: ctl[0] != 0 selects the copy, else the add - the form a captured graph holds, ctl written by the caller
+ * outside the graph like `hyper`.  ctl: device, 4 fp32 (16 bytes), only read in mode 2.  NaN, Inf and subnormals as IEEE
+ * fp32.  Bases 16-byte aligned: 16-byte accesses; any 4-byte aligned bases and any n >= 0 are correct; nothing at or beyond
+ * n is touched; n == 0 launches nothing.  Refused (< 0, nothing launched, the text names grad_accumulate): a NULL pointer
+ * with n > 0, negative n, a base that is not 4-byte aligned, an unknown mode, mode 2 with NULL ctl, acc overlapping grad
+ * (or ctl). */
+int kodhip_grad_accumulate(float* acc, const float* grad, long n, int mode, const float* ctl, kodStream_t stream);
 int kodhip_fill_u32(void* p, uint32_t value, long n, kodStream_t stream);
 /* dst (device) <- src (PINNED host memory), bytes % 16 == 0, both 16-byte aligned: a kernel pulling the bytes through the
  * host memory's device mapping - the small per-step tables of the data path (kod/data/detection.py's per-sample results)

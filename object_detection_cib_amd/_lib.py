@@ -99,6 +99,7 @@ SIGNATURES = {
     "kodhip_adam_step": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp]),
     "kodhip_ema_update": (i32, [vp, vp, vp, i32, f32, f32, vp]),
     "kodhip_ema_swap": (i32, [vp, vp, vp, i32, vp]),
+    "kodhip_grad_accumulate": (i32, [vp, vp, i64, i32, vp, vp]),
     "kodhip_fill_u32": (i32, [vp, u32, i64, vp]),
     "kodhip_pull_from_host": (i32, [vp, vp, i64, vp]),
     "kodhip_debug_stamp": (i32, [vp, vp]),

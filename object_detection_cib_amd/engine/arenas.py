@@ -1,5 +1,5 @@
 """Parameter side of the engine: flat fp32 arenas (masters, gradients x 2, momentum), BatchNorm statistic arenas, the
-bf16 MFMA operand packs and the fused SGD and Adam / AdamW steps.
+bf16 MFMA operand packs, the fused SGD and Adam / AdamW steps and the gradient accumulator (accumulate_grad_batches).
 
 Replaces what torch.optim.SGD's foreach kernels and autograd's .grad bookkeeping do for the reference
 (kod/nn/optim/smart.py:36-58, kod/lightning/experiments/yv5_baseline/exp.py:156-185): torch Parameters are views of ONE
@@ -256,6 +256,12 @@ class ArenaMixin:
         self._adam_ring, self._adam_vals = None, None
         self.adam_steps = 0               # Adam steps taken, as the optimizer counts them (set_adam_hyper)
         self.adam_frozen = None           # frozenset of the names frozen at the first Adam step (they own no state)
+        # gradient accumulation (engine/accumulate.py, csrc/accumulate.hip): nothing exists until configure_accumulation(n > 1)
+        self.acc_arena = None             # fp32, the gradient arena's layout: the open window's sum
+        self.acc_ctl = None               # 4 fp32 on the device; [0] != 0: the next accumulate launch copies (a window's first)
+        self._acc_ring, self._acc_first = None, None
+        self.accumulation = None          # AccumulationWindow shared by every captured step of this engine
+        self._update_from_acc = False     # current_grad_arena() is the accumulator (step_accumulated_device)
 
     def _grad_view(self, name, arena=None):
         o, k = self.layout[name]
@@ -393,8 +399,57 @@ class ArenaMixin:
             self._nbt_inc[plan.key] = torch.tensor(plan.train_mask(), dtype=torch.int64, device=self.device)
 
     def current_grad_arena(self):
-        """Arena holding the gradients published by the last backward()."""
+        """Arena holding the gradients published by the last backward() - the gradient operand of every update launch (norm,
+        SGD forms, Adam).  While a closed accumulation window is being consumed (step_accumulated_device) that operand is the
+        accumulator."""
+        if self._update_from_acc:
+            return self.acc_arena
         return self.g_arena[self.g_cur ^ 1]
+
+    # ------------------------------------------------------------------ gradient accumulation
+    def configure_accumulation(self, n: int):
+        """accumulate_grad_batches = n for the captured steps of this engine.  n > 1 allocates, once: the accumulator (the
+        parameter arena's size), the 4-float control block with its staging ring, and the window.  n == 1 allocates nothing."""
+        from .accumulate import AccumulationWindow, check_accumulate_grad_batches
+        n = check_accumulate_grad_batches(n)
+        if n == 1:
+            return None
+        if self.acc_arena is None:
+            self.acc_arena = torch.zeros(self.n_arena, dtype=torch.float32, device=self.device)
+            self.acc_ctl = torch.zeros(4, dtype=torch.float32, device=self.device)
+            self._acc_ring = _StagingRing(4)
+        if self.accumulation is None:
+            self.accumulation = AccumulationWindow(n)
+        elif self.accumulation.n != n:
+            if self.accumulation.flush_needed:
+                raise RuntimeError(f"accumulate_grad_batches changed from {self.accumulation.n} to {n} inside an open window: "
+                                   "flush() first")
+            self.accumulation = AccumulationWindow(n)
+        return self.accumulation
+
+    def set_accumulate_first(self, first: bool):
+        """Upload the control block's flag when it changed - outside any captured graph, like set_hyper."""
+        first = bool(first)
+        if first != self._acc_first:
+            self._acc_ring.upload(self.acc_ctl, (1.0 if first else 0.0, 0.0, 0.0, 0.0))
+            self._acc_first = first
+
+    def accumulate_grads_device(self):
+        """acc_arena <- (copy of | acc_arena +) the gradients of the last backward(), as acc_ctl says: ONE launch - the
+        graph-capturable form, after wait_grads() (data parallel: what is accumulated is the all-reduced gradient)."""
+        self.wait_grads()
+        _lib.check(self.lib.kodhip_grad_accumulate(self.acc_arena.data_ptr(), self.current_grad_arena().data_ptr(), self.n_arena,
+                                                   2, self.acc_ctl.data_ptr(), self._stream()), "grad_accumulate")
+
+    def step_accumulated_device(self, optimizer: str = "sgd"):
+        """sgd_step_device() / adam_step_device() on the accumulator: the update that closes a window."""
+        if self.acc_arena is None:
+            raise RuntimeError("step_accumulated_device() before configure_accumulation(n > 1)")
+        self._update_from_acc = True
+        try:
+            self.adam_step_device() if optimizer == "adam" else self.sgd_step_device()
+        finally:
+            self._update_from_acc = False
 
     # ------------------------------------------------------------------ optimizer
     def set_hyper(self, lr, momentum, weight_decay, grad_scale: float = 1.0):

@@ -11,6 +11,10 @@ run at device speed (bench.py measures exactly this replay).  What makes the ste
 * optimizer hyper-parameters are read from device memory (Engine.set_hyper), so warm-up / LR schedules keep working;
   so is the gradient-clipping value (Engine.set_clip): the norm reduction and the clipped SGD run inside the graph;
 * no host synchronisation anywhere in the step (assigner counts stay on the device).
+
+accumulate_grad_batches = N > 1 (engine/accumulate.py): the captured step ends with one kodhip_grad_accumulate launch instead of
+the update - a device flag, uploaded outside the graph, says whether it opens a window - and the update runs eagerly behind the
+replay that closes a window.
 """
 from __future__ import annotations
 
@@ -106,7 +110,7 @@ class GraphedTrainStep:
                  loss_scale: Optional[float] = None, input_pairs: bool = False,
                  gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
                  skip_nonfinite: bool = False, track_grad_norm: bool = False, target_block: Optional["TargetBlock"] = None,
-                 optimizer: str = "sgd"):
+                 optimizer: str = "sgd", accumulate_grad_batches: int = 1):
         """input_pairs: batches arrive as bf16 pixel pairs [B, H, W/2, 8] (DeviceTrainPipeline.make_batch(out_pairs=True)) and
         are copied straight into the network's input buffer - no fp32 NCHW batch, no layout-change pass in the step.
         gradient_clip_val / gradient_clip_algorithm ("norm" | "value"): Lightning's Trainer arguments; the clipping runs
@@ -121,7 +125,15 @@ class GraphedTrainStep:
         With "adam", __call__ takes `adam=FusedAdam.hyper()` in place of (lr, momentum, weight_decay): the bias corrections
         are host values formed from the step count, so EVERY call must bring the hyper of its step.  skip_nonfinite is
         refused with "adam" (a skipped device step would not hold the host's count back), so is capture(preserve_state=False)
-        (its warm-up steps would move the moments without the count)."""
+        (its warm-up steps would move the moments without the count).
+        accumulate_grad_batches = N (Lightning's Trainer argument; engine/accumulate.py): with N > 1 the captured step ends with
+        ONE kodhip_grad_accumulate launch in place of the update, `loss_scale` defaults to B / N, and the call that closes a
+        window of N micro-batches launches norm / clip / update eagerly behind its replay, on the same stream, reading the
+        accumulator.  `stepped` says whether the last call updated; flush() closes a partial window (an epoch's end).  The
+        window lives in the engine, N is baked in at capture().  N = 1 is the step without any of this."""
+        from .accumulate import check_accumulate_grad_batches
+        self.accumulate, self._accumulate = check_accumulate_grad_batches(accumulate_grad_batches), None
+        self.stepped = False              # the last call (or flush()) ran the optimizer update
         if gradient_clip_algorithm not in ("norm", "value"):
             raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected 'norm' or 'value'")
         if optimizer not in ("sgd", "adam"):
@@ -140,7 +152,8 @@ class GraphedTrainStep:
         dev = self.eng.device
         self.B, self.H, self.W = batch_size, height, width
         self.cap = int(max_targets)
-        self.scale = float(batch_size if loss_scale is None else loss_scale)     # exp.py:104-138: total = B * sum
+        # exp.py:104-138: total = B * sum; under accumulation Lightning's loss / N, formed as one double: B / N
+        self.scale = float(batch_size / self.accumulate if loss_scale is None else loss_scale)
         self.x = torch.zeros((batch_size, 3, height, width), dtype=torch.float32, device=dev)
         # boxes f64 [cap, 4] | labels i64 [cap] | sample ids i32 [cap] as views of ONE device block (TargetBlock)
         self._tb = target_block if target_block is not None else TargetBlock(max_targets, dev, self.eng.lib)
@@ -154,6 +167,7 @@ class GraphedTrainStep:
         self._bn_flags = None
         self.total = None
         self.parts = None
+        self._last_adam = None            # the hyper the last call brought (flush() without one)
         self._pins = 0                    # pins capture() took on this shape, given back by release()
 
     def input_buffer(self) -> torch.Tensor:
@@ -181,14 +195,27 @@ class GraphedTrainStep:
     def _step(self):
         for p in self.params:
             p.grad = None
+        if self.accumulate > 1:
+            # the weight packs are made inside the step (Engine.forward, when the key moved).  The plain step moves the key
+            # itself with its update; this one must hold the pack launch too, for the replay behind an eager update
+            self.eng.mark_params_changed()
         total, lr = self.net.train_step(self.x, self.loss, self.shape, self.targets, self.scale, image_ready=self.input_pairs)
         self.eng.wait_grads()
+        if self.accumulate > 1:           # the update runs behind the replay that closes the window (_close)
+            self.eng.accumulate_grads_device()
+        else:
+            self._update(False)
+        return total, (lr.localization.detach(), lr.objectness.detach(), lr.classification.detach())
+
+    def _update(self, accumulated: bool):
+        """norm / clip / update launches on the current stream: inside the captured step, or behind a closing replay"""
         self.eng.configure_clip(*self._clip_config())
-        if self.optimizer == "adam":
+        if accumulated:
+            self.eng.step_accumulated_device(self.optimizer)
+        elif self.optimizer == "adam":
             self.eng.adam_step_device()
         else:
             self.eng.sgd_step_device()
-        return total, (lr.localization.detach(), lr.objectness.detach(), lr.classification.detach())
 
     def _load(self, images: torch.Tensor, targets):
         if self.input_pairs:
@@ -222,11 +249,18 @@ class GraphedTrainStep:
         self._load(images, targets)
         self._clip_cfg = self._clip_config()
         self._optimizer = self.optimizer
+        self._accumulate = self.accumulate
+        window = eng.configure_accumulation(self.accumulate)
         eng.set_clip(self.gradient_clip_val)
         state = (eng.p_arena, eng.m_arena, eng.rm_arena, eng.rv_arena, eng.nbt_arena, eng.clip)     # (clip: the skipped-steps count)
         adam_steps = eng.adam_steps
         if self.optimizer == "adam":
             state = state + (eng.v_arena,)
+        if window is not None:            # the warm-up steps accumulate: an open window (a size first met inside one) survives
+            state = state + (eng.acc_arena, eng.acc_ctl)
+            pos = window.pos
+            if eng._acc_first is None:
+                eng.set_accumulate_first(window.first)
         keep = [t.clone() for t in state] if preserve_state else None
         side = torch.cuda.Stream(device=eng.device)
         side.wait_stream(torch.cuda.current_stream())
@@ -247,6 +281,11 @@ class GraphedTrainStep:
                 t.copy_(k)
             eng.mark_params_changed()
         eng.adam_steps = adam_steps               # (the warm-up steps are not steps of the trajectory)
+        if window is not None:
+            if keep is not None:
+                window.pos = pos
+            else:
+                window.reset()
         return self
 
     def __call__(self, images: torch.Tensor, targets, lr: Optional[Sequence[float]] = None,
@@ -264,6 +303,28 @@ class GraphedTrainStep:
         self._load(images, targets)
         return self._replay()
 
+    def flush(self, lr: Optional[Sequence[float]] = None, momentum: Optional[Sequence[float]] = None,
+              weight_decay: Optional[Sequence[float]] = None, grad_scale: float = 1.0, gradient_clip_val=_KEEP,
+              adam: Optional[dict] = None) -> bool:
+        """Close a partial window (the last batch of an epoch came before N micro-batches were in): the update on what has
+        been accumulated, with the hyper-parameters given here or, left out, the ones the last call brought.  Does nothing -
+        no launch, no upload - when no window is open.  Returns `stepped`."""
+        self.stepped = False
+        window = self.eng.accumulation if self.accumulate > 1 else None
+        if window is None or not window.flush_needed:
+            return False
+        if adam is None and self.optimizer == "adam":
+            adam, grad_scale = self._last_adam          # (the block the last call uploaded, its grad_scale included)
+        self._prepare(lr, momentum, weight_decay, grad_scale, gradient_clip_val, None, adam)
+        self._close(window)
+        return True
+
+    def _close(self, window):
+        """the per-window work behind the replay (or flush) that closes it"""
+        self._update(True)                    # (param_version, note_sgd_step / note_adam_step: the update launchers' own)
+        window.reset()
+        self.stepped = True
+
     def release(self):
         """Drop the captured graph and give back the pins capture() took on the shape (Engine.unpin_shape): the buffer set
         becomes an ordinary one that the engine may drop.  The caller makes sure that no replay is still running; a later
@@ -275,6 +336,13 @@ class GraphedTrainStep:
 
     def _guard(self, freeze_flags, bn_flags, clip_cfg):
         """what the graph was captured with against what holds now (MultiScaleTrainStep checks every held step per call)"""
+        window = self.eng.accumulation
+        now = self.accumulate if (self.accumulate == 1 or window is None or self.accumulate != self._accumulate) else window.n
+        if now != self._accumulate:
+            # the graph ends with the accumulate launch (N > 1) or the update (N = 1), and its loss scale is B / N; the
+            # window the engine holds must be the one it was captured for
+            raise RuntimeError(f"accumulate_grad_batches changed to {now} after capture() with {self._accumulate}: the captured "
+                               "step holds the old launches and loss scale; build a new GraphedTrainStep and capture() again")
         if self.optimizer != self._optimizer:
             # the graph ends with the update launch of the optimizer it was captured with
             raise RuntimeError(f"optimizer changed to {self.optimizer!r} after capture() with {self._optimizer!r}: the captured "
@@ -307,6 +375,7 @@ class GraphedTrainStep:
             if adam is None or lr is not None:
                 raise ValueError("optimizer='adam': pass adam=FusedAdam.hyper() at every call (the bias corrections of the step "
                                  "are host values), not lr / momentum / weight_decay")
+            self._last_adam = (dict(adam), grad_scale)
             self.eng.set_adam_hyper(**adam, grad_scale=grad_scale)
             self.eng.check_adam_freeze()
         elif adam is not None:
@@ -315,12 +384,25 @@ class GraphedTrainStep:
             self.eng.set_hyper(lr, momentum, weight_decay, grad_scale)
 
     def _replay(self):
+        if self.accumulate > 1:
+            eng = self.eng
+            window = eng.accumulation
+            eng.set_accumulate_first(window.first)
+            self.graph.replay()
+            # the replay moved running statistics and no parameter: the eval constants (keyed on both halves of
+            # freshness_key) are rebuilt, the weight packs (parameter half) are not
+            eng.stats_version += 1
+            self.stepped = False
+            if window.advance():
+                self._close(window)
+            return self.total, self.parts
         self.graph.replay()
         self.eng.param_version += 1           # the replayed update changed the parameters
         if self.optimizer == "adam":
             self.eng.note_adam_step()
         else:
             self.eng.note_sgd_step()
+        self.stepped = True
         return self.total, self.parts
 
 

@@ -163,9 +163,16 @@ class MultiScaleTrainStep:
                  gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
                  skip_nonfinite: bool = False, track_grad_norm: bool = False, *, scale_range=(0.5, 1.5),
                  sizes: Optional[Sequence[int]] = None, interval: int = 1, seed: int = 0, max_graphs: Optional[int] = None,
-                 optimizer: str = "sgd"):
+                 optimizer: str = "sgd", accumulate_grad_batches: int = 1):
         """optimizer: "sgd" | "adam", passed to every GraphedTrainStep it builds (with "adam" a call takes `adam=` like
-        GraphedTrainStep.__call__)."""
+        GraphedTrainStep.__call__).
+        accumulate_grad_batches = N, passed on likewise: the steps of all sizes share the engine's window, a size is drawn per
+        micro-batch as train.py does (`interval` counts micro-batches), and a size met for the first time inside a window is
+        captured without disturbing it.  `stepped` and flush() as on GraphedTrainStep."""
+        from .accumulate import check_accumulate_grad_batches
+        self.accumulate = check_accumulate_grad_batches(accumulate_grad_batches)
+        self.stepped = False
+        self._last = None                 # the step of the last call (flush() closes the window through it)
         if gradient_clip_algorithm not in ("norm", "value"):
             raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected 'norm' or 'value'")
         if optimizer not in ("sgd", "adam"):
@@ -227,7 +234,8 @@ class MultiScaleTrainStep:
     def _new_step(self, h: int, w: int) -> GraphedTrainStep:
         return GraphedTrainStep(self.net, self.loss, self.B, h, w, self.cap, self.loss_scale, True,
                                 self.gradient_clip_val, self.gradient_clip_algorithm, self.skip_nonfinite,
-                                self.track_grad_norm, target_block=self._tb, optimizer=self.optimizer)
+                                self.track_grad_norm, target_block=self._tb, optimizer=self.optimizer,
+                                accumulate_grad_batches=self.accumulate)
 
     def __call__(self, images: torch.Tensor, targets, lr: Optional[Sequence[float]] = None,
                  momentum: Optional[Sequence[float]] = None, weight_decay: Optional[Sequence[float]] = None,
@@ -281,4 +289,17 @@ class MultiScaleTrainStep:
         step._prepare(lr, momentum, weight_decay, grad_scale, self.gradient_clip_val, self.gradient_clip_algorithm, adam)
         if eng.peer is not None:
             eng.peer.check()                  # a failed SyncBN exchange of an earlier replay: raise, do not train on NaN
-        return step._replay()
+        out = step._replay()
+        self.stepped, self._last = step.stepped, step
+        return out
+
+    def flush(self, *args, **kw) -> bool:
+        """GraphedTrainStep.flush: close a partial window; nothing when none is open."""
+        self.stepped = False
+        if self._last is None or self._last.graph is None:        # (no call yet, or the step was evicted with its window closed)
+            window = self.eng.accumulation if self.accumulate > 1 else None
+            if window is None or not window.flush_needed:
+                return False
+            self._last = next(reversed(self.steps.values()))
+        self.stepped = self._last.flush(*args, **kw)
+        return self.stepped

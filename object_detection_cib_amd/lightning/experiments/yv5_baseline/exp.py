@@ -67,7 +67,16 @@ class DefaultYolov5Experiment:
     `ema.update()` after every optimizer step - one kodhip_ema_update launch behind the step, outside any captured graph - and
     validate() runs under `ema.applied()`, i.e. reports the averaged model as train.py does; the network's own weights are
     back, bit for bit, when it returns.  Data parallel: every rank forms the same parameter average without a collective;
-    without SyncBN the running statistics and their averages are per rank."""
+    without SyncBN the running statistics and their averages are per rank.
+    accumulate_grad_batches=N: Lightning's Trainer argument (YOLOv5's `accumulate`; engine/accumulate.py has train.py's recipe
+    as `yolov5_accumulate`).  Every micro-batch runs forward, loss and backward at the scale B / N - `total` is that scaled
+    value, the logged box / obj / cls stay unscaled - and moves the BatchNorm running statistics; warm-up, clipping, the update,
+    `global_step`, `optimizer.steps_taken` and `ema.update()` happen once per window of N, on the summed gradient.  The last
+    batch of an epoch closes the window even when it is partial (fit_epoch does; by hand: step_accumulated()).  graphed=True:
+    the captured step ends with one kodhip_grad_accumulate launch and the update runs behind the replay that closes a window;
+    eager: the gradients accumulate in `.grad`.  Data parallel: every micro-batch all-reduces its gradients as today and the
+    all-reduced gradient is accumulated; Lightning's `no_sync` (one all-reduce per window) is not implemented.  Checkpoints
+    belong at window boundaries: the accumulator is not part of a checkpoint."""
 
     def __init__(self, net, loss, anchor_info: LayerwiseAnchorInfo, smart_optimizer: Optional[SmartOptimizer] = None,
                  lr_scheduler: Optional[Callable] = None,
@@ -79,7 +88,7 @@ class DefaultYolov5Experiment:
                  val_confusion_iou: float = 0.45, val_augment: bool = False, val_metrics: bool = False,
                  val_max_graphs: int = 8, multi_scale: bool = False, multi_scale_range=(0.5, 1.5),
                  multi_scale_interval: int = 1, multi_scale_max_graphs: Optional[int] = None, multi_scale_seed: int = 0,
-                 ema: bool = False, ema_decay: float = 0.9999, ema_tau: float = 2000.0):
+                 ema: bool = False, ema_decay: float = 0.9999, ema_tau: float = 2000.0, accumulate_grad_batches: int = 1):
         if gradient_clip_algorithm not in CLIP_ALGORITHMS:
             raise ValueError(f"gradient_clip_algorithm {gradient_clip_algorithm!r}: expected one of {CLIP_ALGORITHMS}")
         # Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm): handed to the FusedSGD / the captured step
@@ -137,6 +146,11 @@ class DefaultYolov5Experiment:
         # ema: the ModelEMA is built with the optimizer (configure_optimizers); a state loaded before that waits in `_ema_pending`
         self._ema_on, self.ema_decay, self.ema_tau = bool(ema), float(ema_decay), float(ema_tau)
         self.ema, self._ema_pending = None, None
+        # accumulate_grad_batches: the eager route's window (the graphed one lives in the engine, engine/graphed.py)
+        from ....engine.accumulate import AccumulationWindow
+        self._window = AccumulationWindow(accumulate_grad_batches)
+        self.accumulate_grad_batches = self._window.n
+        self._num_training_batches = None
 
     # exp.py:156-162
     def configure_optimizers(self):
@@ -181,7 +195,9 @@ class DefaultYolov5Experiment:
         shape = FeatureShape(width=images.shape[3], height=images.shape[2])
         lr = self.loss(shape, net_result, targets)
         B = images.shape[0]
-        total = B * (lr.localization + lr.classification + lr.objectness)
+        # accumulate_grad_batches = N: Lightning's loss / N, formed as ONE fp32 factor B / N (total / N afterwards would round twice)
+        N = self.accumulate_grad_batches
+        total = (B if N == 1 else B / N) * (lr.localization + lr.classification + lr.objectness)
         self.logged = {"obj": lr.objectness.detach(), "cls": lr.classification.detach(), "box": lr.localization.detach()}
         return total
 
@@ -217,13 +233,49 @@ class DefaultYolov5Experiment:
         if self.ema is not None and self.ema.is_applied:
             raise RuntimeError("optimize() while ema.applied(): the step would train the averaged weights; leave the applied() "
                                "block first")
+        self._num_training_batches = num_training_batches
         if self.graphed:
             return self._optimize_graphed(batch, num_training_batches)
         if self.multi_scale:
             batch = self._multi_scale_batch(batch)
-        self.optimizer.zero_grad(set_to_none=True)
+        if self._window.first:                 # (a window's later micro-batches accumulate into .grad, Engine._publish_grads)
+            self.optimizer.zero_grad(set_to_none=True)
         total = self.training_step(batch)
         total.backward()
+        if self._window.advance():
+            self._optimizer_step(num_training_batches)
+        return total
+
+    def step_accumulated(self):
+        """Close an open accumulation window now (Lightning's is_final_batch rule: the last batch of an epoch steps the optimizer
+        on what has been accumulated, its micro-batches keeping the B / N scale).  fit_epoch calls it; it does nothing when no
+        window is open.  Returns whether an optimizer step ran."""
+        if self.optimizer is None:
+            return False
+        n = self._num_training_batches
+        if self.graphed:
+            if self._gstep is None or self.accumulate_grad_batches == 1:
+                return False
+            eng = self.net.engine()
+            if eng.accumulation is None or not eng.accumulation.flush_needed:
+                return False
+            self._warmup(n)
+            if isinstance(self.optimizer, FusedAdam):
+                self._gstep.flush(grad_scale=1.0 / self.optimizer.world_size, gradient_clip_val=self.optimizer.gradient_clip_val,
+                                  adam=self.optimizer.hyper())
+            else:
+                lr, mom, wd = self.optimizer.hyper()
+                self._gstep.flush(lr, mom, wd, 1.0 / self.optimizer.world_size, gradient_clip_val=self.optimizer.gradient_clip_val)
+            self._graphed_stepped()
+            return True
+        if not self._window.flush_needed:
+            return False
+        self._window.reset()
+        self._optimizer_step(n)
+        return True
+
+    def _optimizer_step(self, num_training_batches: int):
+        """the eager route's per-window work: warm-up hook, clipping, optimizer.step(), EMA, global_step"""
         self._warmup(num_training_batches)
         if self._clipping():
             if isinstance(self.optimizer, (FusedSGD, FusedAdam)):
@@ -244,7 +296,6 @@ class DefaultYolov5Experiment:
         if self.ema is not None:
             self.ema.update()
         self.global_step += 1
-        return total
 
     # ------------------------------------------------------------------ weight EMA
     def ema_state_dict(self) -> Optional[dict]:
@@ -338,7 +389,8 @@ class DefaultYolov5Experiment:
                                               skip_nonfinite=opt.skip_nonfinite, track_grad_norm=opt.track_grad_norm,
                                               scale_range=self.multi_scale_range, interval=self.multi_scale_interval,
                                               seed=self.multi_scale_seed, max_graphs=self.multi_scale_max_graphs,
-                                              optimizer=self._graphed_optimizer())
+                                              optimizer=self._graphed_optimizer(),
+                                              accumulate_grad_batches=self.accumulate_grad_batches)
             if self._ms_pending is not None:
                 self._gstep.load_state_dict(self._ms_pending)
                 self._ms_pending = None
@@ -350,7 +402,8 @@ class DefaultYolov5Experiment:
                                            gradient_clip_algorithm=opt.gradient_clip_algorithm,
                                            skip_nonfinite=opt.skip_nonfinite,
                                            track_grad_norm=opt.track_grad_norm,
-                                           optimizer=self._graphed_optimizer()).capture(images, targets)
+                                           optimizer=self._graphed_optimizer(),
+                                           accumulate_grad_batches=self.accumulate_grad_batches).capture(images, targets)
         self._warmup(num_training_batches)
         if isinstance(self.optimizer, FusedAdam):
             total, (box, obj, cls) = self._gstep(images, targets, grad_scale=1.0 / self.optimizer.world_size,
@@ -359,17 +412,22 @@ class DefaultYolov5Experiment:
             lr, mom, wd = self.optimizer.hyper()
             total, (box, obj, cls) = self._gstep(images, targets, lr, mom, wd, 1.0 / self.optimizer.world_size,
                                                  gradient_clip_val=self.optimizer.gradient_clip_val)
+        self.logged = {"obj": obj, "cls": cls, "box": box}
+        if self._clipping():
+            self.logged["grad_norm"] = self._gstep.grad_norm[0]          # (static, like the loss parts: the last update's norm)
+        if self._gstep.stepped:               # (accumulate_grad_batches > 1: only the call that closed a window)
+            self._graphed_stepped()
+        return total.clone()
+
+    def _graphed_stepped(self):
+        """what follows an optimizer update of the graphed route (every call, or the one that closed an accumulation window)"""
         if self.ema is not None:              # behind the replay, on the same stream, outside the captured graph
             self.ema.update()
         self.optimizer.steps_taken += 1
         # the replayed graph contains the optimizer update: tell torch's bookkeeping that a step happened (LambdaLR.step() checks
         # optimizer._step_count to warn about a scheduler stepped before the optimizer)
         self.optimizer._step_count = getattr(self.optimizer, "_step_count", 0) + 1
-        self.logged = {"obj": obj, "cls": cls, "box": box}
-        if self._clipping():
-            self.logged["grad_norm"] = self._gstep.grad_norm[0]          # (static, like the loss parts)
         self.global_step += 1
-        return total.clone()
 
     def end_epoch(self):
         """Lightning steps the epoch-interval scheduler: LambdaLR sets lr = initial_lr * lr_lambda(epoch)."""
@@ -382,6 +440,7 @@ class DefaultYolov5Experiment:
         _lib.limit_host_threads()      # the epoch loops are the library's own: size torch's host pool to the cgroup share
         with _gc_paused():
             losses = [self.optimize(b, n).detach() for b in batches]
+            self.step_accumulated()        # the epoch's last batch closes a partial accumulation window
         self.end_epoch()
         return torch.stack(losses)
 
