@@ -399,6 +399,19 @@ int kodhip_yolo_loss_iou(const KodLossLevel* levels /* host[3] */, int B, int A,
                          const float* upstream, float* partials, int nslots, float* out, int compute_grad,
                          int iou_kind, float iou_eps, kodStream_t stream);
 
+/* the same with YOLOv5's loss hyper-parameters (hyp.*.yaml fl_gamma / obj_pw, train.py --label-smoothing; cls_pw is pos_weight):
+ * FocalLoss(gamma, alpha) around both BCE terms (fl_gamma 0 = off, else >= 1), class targets cls_pos at the row's label and
+ * cls_neg elsewhere (smooth_BCE: 1 - eps / 2, eps / 2), a pos_weight on the objectness BCE.  The objectness target stays
+ * clamp(iou, 0), not detached: under focal its gradient depends on the cell's surviving (last row's) target.
+ * opt is a host pointer; NULL or neutral (0, any alpha, 1, 0, 1) runs exactly kodhip_yolo_loss_iou - the same kernels, the same bits.
+ * Refused with a status and a message, nothing launched: fl_gamma < 0 or in (0, 1) or not finite, fl_alpha outside (0, 1),
+ * cls_pos outside (0.5, 1], cls_neg outside [0, 0.5), obj_pos_weight <= 0 or not finite.  Same launches as the default path. */
+typedef struct KodLossOptions { float fl_gamma, fl_alpha, cls_pos, cls_neg, obj_pos_weight; } KodLossOptions;
+int kodhip_yolo_loss_ex(const KodLossLevel* levels /* host[3] */, int B, int A, int nc, int cap,
+                        float lam_box, float lam_obj, float lam_cls, const float* pos_weight,
+                        const float* upstream, float* partials, int nslots, float* out, int compute_grad,
+                        int iou_kind, float iou_eps, const KodLossOptions* opt /* host, or NULL */, kodStream_t stream);
+
 /* Aligned IoU family behind kod.core.bbox.iou.IoUCalculator.__call__ (kod/core/bbox/iou.py:77-95,142-268):
  * boxes [m][4] xyxy fp32 -> out [m]; kind 0 iou | 1 giou | 2 diou | 3 ciou (IoUType order, iou.py:9-14).
  * The backward follows autograd's conventions (max/min ties split evenly, clamp(0) passes at 0, CIoU alpha constant). */

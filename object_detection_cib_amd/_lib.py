@@ -30,6 +30,10 @@ class KodLossLevel(C.Structure):
                 ("fh", i32), ("fw", i32), ("balance", f32)]
 
 
+class KodLossOptions(C.Structure):
+    _fields_ = [("fl_gamma", f32), ("fl_alpha", f32), ("cls_pos", f32), ("cls_neg", f32), ("obj_pos_weight", f32)]
+
+
 # name -> (restype, argtypes); mirrors include/kodhip.h one to one (tests/test_abi.py checks both ways)
 SIGNATURES = {
     "kodhip_last_error": (C.c_char_p, []),
@@ -178,6 +182,8 @@ SIGNATURES = {
                                i32, vp]),
     "kodhip_yolo_loss_iou": (i32, [C.POINTER(KodLossLevel), i32, i32, i32, i32, f32, f32, f32, vp, vp, vp, i32, vp,
                                    i32, i32, f32, vp]),
+    "kodhip_yolo_loss_ex": (i32, [C.POINTER(KodLossLevel), i32, i32, i32, i32, f32, f32, f32, vp, vp, vp, i32, vp,
+                                  i32, i32, f32, C.POINTER(KodLossOptions), vp]),
 }
 
 _lib = None

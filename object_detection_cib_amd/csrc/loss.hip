@@ -5,6 +5,8 @@
 //   loss     : kod/lightning/experiments/yv5_baseline/loss.py:65-248 with kod/core/bbox/iou.py:200-246 (CIoU)
 //              including the reference quirks: objectness target = clamp(iou, 0) NOT detached, duplicate
 //              cells = last row wins, empty level => NaN box/cls loss, per-level means.
+//   options  : YOLOv5's remaining loss hyper-parameters (fl_gamma / fl_alpha, label smoothing, obj_pw; the reference has
+//              none of them) as a second instantiation of the rows and cells kernels: kodhip_yolo_loss_ex.
 //
 // Everything is fp32 like the reference (fp64 where the reference is fp64: box -> grid conversion).
 // Duplicate-cell gradient accumulation is done in row order by the cell's last writer (no float atomics),
@@ -177,6 +179,10 @@ struct LossArgs {
   int iou_kind;                        // 0 iou | 1 giou | 2 diou | 3 ciou (IoUCalculator.iou_type, kod/core/bbox/iou.py:9-14)
   float iou_eps;
   int iou_generic;                     // anything but the fused ciou / 1e-7 form: the dual-number row of kodhip_iou.h
+  // KodLossOptions, read by the extended instantiations only (the default ones never touch them)
+  float fl_gamma, fl_alpha;            // focal exponent (0 = off, else >= 1) and its alpha
+  float cls_pos, cls_neg;              // smoothed class targets: at the row's label / elsewhere
+  float obj_pw;                        // objectness pos_weight
 };
 
 __device__ __forceinline__ int cell_of(const LossLevel& L, int A, int cap, int r) {
@@ -207,6 +213,72 @@ __device__ float block_sum_256(float v, float* sm) {
   return s;
 }
 
+// ---- extended loss terms (focal modulation, smoothed class targets, objectness pos_weight): YOLOv5's FocalLoss around
+// binary_cross_entropy_with_logits(x, t, pos_weight = pw), per element
+//   w = 1 + (pw - 1) t, sp = softplus(-x), bce = (1 - t) x + w sp, p = sigmoid(x), q = 1 - p_t = t (1 - p) + (1 - t) p,
+//   af = t al + (1 - t)(1 - al), mf = q^g, L = bce af mf                                   (g == 0: L = bce, no alpha)
+//   dL/dx = af (((1 - t) - w (1 - p)) mf - bce g q^(g-1) (2t - 1) p (1 - p))
+//   dL/dt = (-x + (pw - 1) sp) af mf + bce (2 al - 1) mf - bce af g q^(g-1) (2p - 1)        (objectness: target not detached)
+// One powf gives q^(g-1); g >= 1 keeps it finite at q == 0 and powf(0, 0) == 1 is torch's 0^0 at g == 1.
+struct FocalTerm { float loss, dx, dt; };
+
+__device__ __forceinline__ FocalTerm focal_bce(float x, float t, float pw, float g, float al) {
+  const float e = expf(-fabsf(x));
+  const float sp = log1pf(e) + fmaxf(-x, 0.f);                  // = -log_sigmoid(x)
+  const float r = 1.f / (1.f + e);
+  const float p = x >= 0.f ? r : e * r, omp = x >= 0.f ? e * r : r;       // sigmoid(x), 1 - sigmoid(x): neither cancels
+  const float w = (pw - 1.f) * t + 1.f;
+  const float bce = (1.f - t) * x + w * sp;
+  const float dbx = (1.f - t) - w * omp, dbt = -x + (pw - 1.f) * sp;
+  FocalTerm o;
+  if (g > 0.f) {
+    const float q = t * omp + (1.f - t) * p;
+    const float af = t * al + (1.f - t) * (1.f - al);
+    const float qg1 = powf(q, g - 1.f);
+    const float gq = g * qg1, mf = qg1 * q;
+    o.loss = bce * af * mf;
+    o.dx = af * (dbx * mf - bce * gq * (2.f * t - 1.f) * p * omp);
+    o.dt = dbt * af * mf + bce * (2.f * al - 1.f) * mf - bce * af * gq * (2.f * p - 1.f);
+  } else {
+    o.loss = bce; o.dx = dbx; o.dt = dbt;
+  }
+  return o;
+}
+
+// The IoU value of one assignment row from the cell's four box sigmoids: what the extended rows kernel stores as the row's
+// objectness target (clamped), and what a row that is not its cell's last recomputes for the last row - same function,
+// same operands, same bits as the value in tobj (which another thread of the same launch writes).
+__device__ __forceinline__ float row_iou_value(const LossArgs& a, float s0, float s1, float s2, float s3, float aw, float ah,
+                                               const float* gt) {
+  const float eps = 1e-7f;
+  float px = s0 * 2.f - 0.5f, py = s1 * 2.f - 0.5f;
+  float pw = (s2 * 2.f) * (s2 * 2.f) * aw, ph = (s3 * 2.f) * (s3 * 2.f) * ah;
+  float x1 = px - 0.5f * pw, y1 = py - 0.5f * ph, x2 = px + 0.5f * pw, y2 = py + 0.5f * ph;
+  float gcx = gt[0], gcy = gt[1], gw = gt[2], gh = gt[3];
+  float x1g = gcx - 0.5f * gw, y1g = gcy - 0.5f * gh, x2g = gcx + 0.5f * gw, y2g = gcy + 0.5f * gh;
+  if (a.iou_generic) {
+    const float b1[4] = {x1, y1, x2, y2}, b2[4] = {x1g, y1g, x2g, y2g};
+    return iou_row<0>(b1, b2, a.iou_kind, a.iou_eps).v;
+  }
+  float iw = fminf(x2, x2g) - fmaxf(x1, x1g), ih = fminf(y2, y2g) - fmaxf(y1, y1g);
+  float inter = fmaxf(iw, 0.f) * fmaxf(ih, 0.f);
+  float w1 = x2 - x1, h1 = y2 - y1, w2 = x2g - x1g, h2 = y2g - y1g;
+  float uni = w1 * h1 + w2 * h2 - inter;
+  float iou = inter / (uni + eps);
+  float cw = fmaxf(x2, x2g) - fminf(x1, x1g), chh = fmaxf(y2, y2g) - fminf(y1, y1g);
+  float diag = cw * cw + chh * chh;
+  float ddx = (x1 + x2) / 2.f - (x1g + x2g) / 2.f, ddy = (y1 + y2) / 2.f - (y1g + y2g) / 2.f;
+  float D = (ddx * ddx + ddy * ddy) / (diag + eps);
+  const float c4 = 4.f / (3.14159265358979323846f * 3.14159265358979323846f);
+  float dat = atanf(w2 / (h2 + eps)) - atanf(w1 / (h1 + eps));
+  float v = c4 * dat * dat;
+  float alpha = v / ((1.f - iou) + v + eps);
+  return iou - D - alpha * v;
+}
+
+// EXT = false: the default loss (plain BCE, one-hot class targets).  EXT = true: KodLossOptions - same launch, same
+// outputs, the BCE terms through focal_bce and the objectness-target gradient evaluated at the cell's surviving target.
+template <bool EXT>
 __global__ __launch_bounds__(256) void loss_rows_kernel(LossArgs a) {
   __shared__ float sm[4];
   const int lvl = blockIdx.y;
@@ -259,6 +331,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossArgs a) {
         ciou = iou_row<0>(b1, b2, a.iou_kind, a.iou_eps).v;
       }
     }
+    if constexpr (EXT) ciou = row_iou_value(a, s0, s1, s2, s3, aw, ah, L.gt + r * 4);
     lbox = 1.f - ciou;
     L.tobj[r] = fmaxf(ciou, 0.f);
 
@@ -271,6 +344,14 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossArgs a) {
     const float u_obj = a.upstream ? a.upstream[1] : 1.f;
     const float u_cls = a.upstream ? a.upstream[2] : 1.f;
     const float kcls = a.lam_cls * u_cls * inv_m / (float)a.nc;
+    if constexpr (EXT) {
+      for (int c = 0; c < a.nc; ++c) {
+        const FocalTerm f = focal_bce(pc[c], (c == lab) ? a.cls_pos : a.cls_neg, a.pos_weight ? a.pos_weight[c] : 1.f,
+                                      a.fl_gamma, a.fl_alpha);
+        lcls += f.loss;
+        if (a.compute_grad) G[4 + c] = kcls * f.dx;
+      }
+    } else {
     for (int c = 0; c < a.nc; ++c) {
       float x = pc[c];
       float t = (c == lab) ? 1.f : 0.f;
@@ -281,6 +362,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossArgs a) {
         float sg = 1.f / (1.f + expf(-x));
         G[4 + c] = kcls * ((1.f - t) - lw * (1.f - sg));
       }
+    }
     }
 
     if (a.compute_grad) {
@@ -314,7 +396,15 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossArgs a) {
       if (ciou >= 0.f) {
         float ncells = (float)a.B * a.A * L.fh * L.fw;
         float xo = p[4];
+        if constexpr (EXT) {
+          // d L_obj(cell) / d t at the cell's SURVIVING target: the last row's clamp(iou, 0), recomputed here from this
+          // cell's box sigmoids and the last row's target box (tobj[last] is written by another thread of this launch)
+          const int lr = L.last[cell];
+          const float tl = fmaxf(lr == r ? ciou :row_iou_value(a, s0, s1, s2, s3, L.anc[lr * 2], L.anc[lr * 2 + 1], L.gt + lr * 4), 0.f);
+          up += focal_bce(xo, tl, a.obj_pw, a.fl_gamma, a.fl_alpha).dt * a.lam_obj * u_obj * L.balance / ncells;
+        } else {
         up += -xo * a.lam_obj * u_obj * L.balance / ncells;
+        }
       }
       G[0] = up * d_px * 2.f * s0 * (1.f - s0);
       G[1] = up * d_py * 2.f * s1 * (1.f - s1);
@@ -334,6 +424,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossArgs a) {
 // divergence), then the wave writes the 64 cells' P gradient slots as ONE contiguous run - lane-linear 4-byte stores,
 // slot 4 fetched from the owning lane by a shuffle, zeros elsewhere (round 1 ran one lane per element: every wave paid
 // the transcendental branch for its 4 active lanes, 15 x the arithmetic).
+template <bool EXT>
 __global__ __launch_bounds__(256) void loss_cells_kernel(LossArgs a) {
   __shared__ float sm[4];
   const int lvl = blockIdx.y;
@@ -353,8 +444,14 @@ __global__ __launch_bounds__(256) void loss_cells_kernel(LossArgs a) {
       const float x = L.logits[cell * a.P + 4];
       const int lr = L.last[cell];
       const float t = lr >= 0 ? L.tobj[lr] : 0.f;
+      if constexpr (EXT) {
+        const FocalTerm f = focal_bce(x, t, a.obj_pw, a.fl_gamma, a.fl_alpha);
+        acc += f.loss;
+        g = kobj * f.dx;
+      } else {
       acc += (1.f - t) * x + log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.f);
       g = kobj * (1.f / (1.f + expf(-x)) - t);
+      }
     }
     if (a.compute_grad) {
       const long rest = ncells - c * 64;
@@ -503,6 +600,11 @@ int kodhip_yolo_loss_iou(const KodLossLevel* levels, int B, int A, int nc, int c
                          const float* pos_weight, const float* upstream, float* partials, int nslots, float* out,
                          int compute_grad, int iou_kind, float iou_eps, hipStream_t stream);
 
+struct KodLossOptions { float fl_gamma, fl_alpha, cls_pos, cls_neg, obj_pos_weight; };
+int kodhip_yolo_loss_ex(const KodLossLevel* levels, int B, int A, int nc, int cap, float lam_box, float lam_obj, float lam_cls,
+                        const float* pos_weight, const float* upstream, float* partials, int nslots, float* out,
+                        int compute_grad, int iou_kind, float iou_eps, const KodLossOptions* opt, hipStream_t stream);
+
 int kodhip_yolo_loss(const KodLossLevel* levels /*[3], host*/, int B, int A, int nc, int cap,
                      float lam_box, float lam_obj, float lam_cls, const float* pos_weight,
                      const float* upstream, float* partials, int nslots, float* out, int compute_grad,
@@ -518,9 +620,38 @@ int kodhip_yolo_loss_iou(const KodLossLevel* levels /*[3], host*/, int B, int A,
                          float lam_box, float lam_obj, float lam_cls, const float* pos_weight,
                          const float* upstream, float* partials, int nslots, float* out, int compute_grad,
                          int iou_kind, float iou_eps, hipStream_t stream) {
+  return kodhip_yolo_loss_ex(levels, B, A, nc, cap, lam_box, lam_obj, lam_cls, pos_weight, upstream, partials, nslots, out,
+                             compute_grad, iou_kind, iou_eps, nullptr, stream);
+}
+
+// The same with YOLOv5's loss hyper-parameters (hyp.*.yaml fl_gamma / obj_pw, train.py --label-smoothing; cls_pw is
+// pos_weight): focal modulation of both BCE terms, smoothed class targets, an objectness pos_weight.  opt NULL or neutral
+// (fl_gamma 0, cls_pos 1, cls_neg 0, obj_pos_weight 1) is exactly kodhip_yolo_loss_iou: the default kernels, the same
+// bits.  Otherwise the extended instantiations of the rows and cells kernels run in the same launch sequence.
+int kodhip_yolo_loss_ex(const KodLossLevel* levels /*[3], host*/, int B, int A, int nc, int cap,
+                        float lam_box, float lam_obj, float lam_cls, const float* pos_weight,
+                        const float* upstream, float* partials, int nslots, float* out, int compute_grad,
+                        int iou_kind, float iou_eps, const KodLossOptions* opt /*host*/, hipStream_t stream) {
   KOD_CHECK_ARG(levels && partials && out && B > 0 && A > 0 && nc > 0 && cap > 0, "yolo_loss: bad args");
   KOD_CHECK_ARG(iou_kind >= 0 && iou_kind <= 3 && iou_eps >= 0.f, "yolo_loss: bad IoU kind %d / eps", iou_kind);
   LossArgs a = {};
+  bool ext = false;
+  if (opt) {
+    // gamma in (0, 1): gamma (1 - p_t)^(gamma - 1) is unbounded at p_t == 1 (saturated logits give NaN gradients)
+    KOD_CHECK_ARG(opt->fl_gamma == 0.f || opt->fl_gamma >= 1.f, "yolo_loss: fl_gamma %g must be 0 or >= 1", (double)opt->fl_gamma);
+    KOD_CHECK_ARG(opt->fl_gamma < 1e30f, "yolo_loss: fl_gamma %g is not finite", (double)opt->fl_gamma);
+    KOD_CHECK_ARG(opt->fl_alpha > 0.f && opt->fl_alpha < 1.f, "yolo_loss: fl_alpha %g outside (0, 1)", (double)opt->fl_alpha);
+    KOD_CHECK_ARG(opt->cls_neg >= 0.f && opt->cls_neg < 0.5f && opt->cls_pos > 0.5f && opt->cls_pos <= 1.f,
+                  "yolo_loss: class targets cls_pos %g / cls_neg %g outside (0.5, 1] / [0, 0.5)", (double)opt->cls_pos,
+                  (double)opt->cls_neg);
+    KOD_CHECK_ARG(opt->obj_pos_weight > 0.f && opt->obj_pos_weight < 1e30f, "yolo_loss: obj_pos_weight %g must be positive and finite",
+                  (double)opt->obj_pos_weight);
+    ext = !(opt->fl_gamma == 0.f && opt->cls_pos == 1.f && opt->cls_neg == 0.f && opt->obj_pos_weight == 1.f);
+    if (ext) {
+      a.fl_gamma = opt->fl_gamma; a.fl_alpha = opt->fl_alpha; a.cls_pos = opt->cls_pos; a.cls_neg = opt->cls_neg;
+      a.obj_pw = opt->obj_pos_weight;
+    }
+  }
   a.iou_kind = iou_kind; a.iou_eps = iou_eps; a.iou_generic = !(iou_kind == 3 && iou_eps == 1e-7f);
   long max_cells = 0;
   for (int l = 0; l < 3; ++l) {
@@ -553,9 +684,9 @@ int kodhip_yolo_loss_iou(const KodLossLevel* levels /*[3], host*/, int B, int A,
   }
   hipLaunchKernelGGL(loss_mark_kernel, dim3(nblk_rows, 3), dim3(256), 0, stream, a);
   KOD_LAUNCH_CHECK("loss_mark");
-  hipLaunchKernelGGL(loss_rows_kernel, dim3(nblk_rows, 3), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(ext ? loss_rows_kernel<true> : loss_rows_kernel<false>, dim3(nblk_rows, 3), dim3(256), 0, stream, a);
   KOD_LAUNCH_CHECK("loss_rows");
-  hipLaunchKernelGGL(loss_cells_kernel, dim3(nblk_cells, 3), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(ext ? loss_cells_kernel<true> : loss_cells_kernel<false>, dim3(nblk_cells, 3), dim3(256), 0, stream, a);
   KOD_LAUNCH_CHECK("loss_cells");
   if (compute_grad) {
     hipLaunchKernelGGL(loss_scatter_kernel, dim3(nblk_rows, 3), dim3(256), 0, stream, a);

@@ -4,6 +4,11 @@ Same constructor / call signature / LossResult; assignment + gather + decode + C
 and their analytic backward run as a handful of HIP kernels (csrc/loss.hip).  Reference quirks kept:
 non-detached objectness target, last-writer-wins on duplicate cells, NaN on an empty level, per-level
 means, lambda_obj*(W/640)^2, lambda_cls*nc/80.
+
+Beyond the reference: YOLOv5's remaining loss hyper-parameters as keyword-only constructor arguments - `fl_gamma` /
+`fl_alpha` (FocalLoss around both BCE terms), `label_smoothing` (smooth_BCE class targets) and `obj_pos_weight` (`obj_pw`;
+`weights` is `cls_pw`).  Neutral values make the reference's call; anything else runs the extended instantiations of the
+same kernels (kodhip_yolo_loss_ex) in the same launch sequence.
 """
 from __future__ import annotations
 
@@ -51,12 +56,17 @@ def _run(mod, shape, raws, asg, cap, grads, upstream, work):
     lam_obj = hp.lambda_objectness * ((shape.width / 640) ** 2)          # loss.py:231-233
     lam_cls = hp.lambda_classification * (nc / 80)                        # loss.py:235-237
     pw = mod.weights
-    _lib.check(lib.kodhip_yolo_loss_iou(levels, B, A, nc, cap, hp.lambda_localization, lam_obj, lam_cls,
-                                        pw.data_ptr() if pw is not None else None,
-                                        upstream.data_ptr() if upstream is not None else None,
-                                        work["partials"].data_ptr(), work["nslots"], work["out"].data_ptr(),
-                                        1 if grads is not None else 0, mod.iou_kind, mod.iou_eps,
-                                        torch.cuda.current_stream().cuda_stream), "yolo_loss")
+    args = (levels, B, A, nc, cap, hp.lambda_localization, lam_obj, lam_cls,
+            pw.data_ptr() if pw is not None else None,
+            upstream.data_ptr() if upstream is not None else None,
+            work["partials"].data_ptr(), work["nslots"], work["out"].data_ptr(),
+            1 if grads is not None else 0, mod.iou_kind, mod.iou_eps)
+    opt = getattr(mod, "_options", None)
+    stream = torch.cuda.current_stream().cuda_stream
+    if opt is None:           # neutral options: today's call, today's kernels
+        _lib.check(lib.kodhip_yolo_loss_iou(*args, stream), "yolo_loss")
+    else:
+        _lib.check(lib.kodhip_yolo_loss_ex(*args, opt, stream), "yolo_loss")
 
 
 class _LossFn(torch.autograd.Function):
@@ -92,8 +102,30 @@ class _LossFn(torch.autograd.Function):
 
 class Yolov5Loss(nn.Module):
     def __init__(self, assigner: Yolov5LabelAssigner, hparams: Yolov5LossParams,
-                 iou_calculator: IoUCalculator, weights: list[float] = None):
+                 iou_calculator: IoUCalculator, weights: list[float] = None, *, fl_gamma: float = 0.0,
+                 fl_alpha: float = 0.25, label_smoothing: float = 0.0, obj_pos_weight: float = 1.0):
+        """fl_gamma / fl_alpha: YOLOv5's FocalLoss around both BCE terms (hyp `fl_gamma`; 0 = plain BCE, otherwise >= 1);
+        label_smoothing: train.py's `--label-smoothing` (class targets 1 - s / 2 and s / 2); obj_pos_weight: hyp `obj_pw`
+        (`weights` is `cls_pw`).  Fixed at construction: a captured step bakes them into its kernel arguments."""
         super().__init__()
+        fl_gamma, fl_alpha, label_smoothing, obj_pos_weight = (float(fl_gamma), float(fl_alpha), float(label_smoothing),
+                                                               float(obj_pos_weight))
+        if not (fl_gamma == 0.0 or 1.0 <= fl_gamma < float("inf")):
+            raise ValueError(f"fl_gamma must be 0 (off) or a finite value >= 1, got {fl_gamma}: for 0 < gamma < 1 the derivative "
+                             "gamma * (1 - p_t)^(gamma - 1) is unbounded at p_t == 1 (NaN gradients on saturated logits)")
+        if not 0.0 < fl_alpha < 1.0:
+            raise ValueError(f"fl_alpha must lie in (0, 1), got {fl_alpha}")
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing}")
+        if not 0.0 < obj_pos_weight < float("inf"):
+            raise ValueError(f"obj_pos_weight must be positive and finite, got {obj_pos_weight}")
+        self._fl_gamma, self._fl_alpha = fl_gamma, fl_alpha
+        self._label_smoothing, self._obj_pos_weight = label_smoothing, obj_pos_weight
+        # None = every option neutral: _run makes the default call (kodhip_yolo_loss_iou), the default kernels run
+        self._options = None
+        if fl_gamma != 0.0 or label_smoothing != 0.0 or obj_pos_weight != 1.0:
+            self._options = _lib.KodLossOptions(fl_gamma, fl_alpha, 1.0 - 0.5 * label_smoothing, 0.5 * label_smoothing,
+                                                obj_pos_weight)
         self.assigner = assigner
         self.hparams = hparams
         self.iou_calculator = iou_calculator
@@ -107,6 +139,11 @@ class Yolov5Loss(nn.Module):
         self.iou_eps = float(getattr(iou_calculator, "eps", 1e-7))
         # reference: plain attribute moved to CUDA when available (loss.py:58-61)
         self.weights = torch.tensor(weights, dtype=torch.float32) if weights is not None else None
+
+    fl_gamma = property(lambda self: self._fl_gamma, doc="focal exponent (read-only; 0 = plain BCE)")
+    fl_alpha = property(lambda self: self._fl_alpha, doc="focal alpha (read-only; unused when fl_gamma is 0)")
+    label_smoothing = property(lambda self: self._label_smoothing, doc="class label smoothing (read-only)")
+    obj_pos_weight = property(lambda self: self._obj_pos_weight, doc="objectness pos_weight (read-only)")
 
     @staticmethod
     def _raw(head) -> torch.Tensor:
