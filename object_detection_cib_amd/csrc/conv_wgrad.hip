@@ -59,6 +59,65 @@ __host__ inline int wg_grid(WgradArgs& a) {
 
 __host__ __device__ constexpr int row_bytes(int T) { return (T * 2) % 128 == 0 ? T * 2 + 64 : T * 2; }
 
+// ---- pieces the MFMA kernels below share: each is stated once ------------------------------------------------------------------
+// A split-K block's tile, split and rows [m_begin, m_end) of the reduction; !ok: a block that the grid's rounding added
+struct WgBlock {
+  int tile, split;
+  bool ok;
+  __device__ __forceinline__ explicit WgBlock(const WgradArgs& a) { ok = wg_map(a, blockIdx.x, a.tiles_n * a.tiles_k, tile, split); }
+  __device__ __forceinline__ void rows(const WgradArgs& a, int& m_begin, int& m_end) const {
+    m_begin = split * a.m_per_split;
+    m_end = m_begin + a.m_per_split;
+    if (m_end > a.M) m_end = a.M;
+  }
+};
+
+// XOR swizzle of the LDS-DMA tiles (see the LDS-DMA variant below): LDS slot (row, c') holds 16-byte chunk c = c' ^ swz(row)
+__host__ __device__ constexpr int swz_mask(int row_b) { return row_b % 256 == 0 ? 3 : (row_b % 128 == 0 ? 2 : 0); }
+__device__ __forceinline__ int swz(int row, int mask) { return mask == 3 ? 4 * (row & 3) : (mask == 2 ? 4 * ((row >> 1) & 1) : 0); }
+
+// Transposed-read lane geometry (see file header): rows = reduction index, columns = n or k.  A fragment is two reads, of rows
+// row .. and row + 4 ..
+__device__ __forceinline__ int tr_row_of(int lane) { return 8 * (lane >> 5) + ((lane & 15) >> 2); }
+__device__ __forceinline__ int tr_col_of(int lane) { return 16 * ((lane >> 4) & 1) + 4 * (lane & 3); }
+// byte offset of element (row, col) in a tile of rb-byte rows whose chunks are swizzled with s = swz(row, mask); s = 0: plain rows
+// (the ROW3-X and stem tiles)
+__device__ __forceinline__ int tr_off(int row, int col, int rb, int s) {
+  return row * rb + (((col >> 3) ^ s) << 4) + (col & 7) * 2;
+}
+
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ bf16x8 frag_join(s16x4 lo, s16x4 hi) {
+  const s16x8 t = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(bf16x8, t);
+}
+// One MFMA operand fragment through the builtin (the compiler counts these reads itself): the register-staged kernel's form.
+__device__ __forceinline__ bf16x8 tr_load(const unsigned char* p, int rb) {
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p));
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p + 4 * rb));
+  return frag_join(lo, hi);
+}
+
+template <int R, int C>
+__device__ __forceinline__ void acc_zero(f32x16 (&acc)[R][C]) {
+#pragma unroll
+  for (int i = 0; i < R; ++i)
+#pragma unroll
+    for (int j = 0; j < C; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+}
+// One 32 x 32 MFMA tile D[n][k] into a slab of ld floats per row: a lane holds slab column k (= its tile's first + (lane & 31))
+// of rows n = n_base + 8*(e>>2) + 4*(lane>>5) + (e&3); rows from n_hi on and a column that is not k_ok are not written.
+__device__ __forceinline__ void store_acc_tile(const f32x16& acc, float* slab, int ld, int n_base, int n_hi, int k, bool k_ok) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int n = n_base + 8 * (e >> 2) + 4 * (lane >> 5) + (e & 3);
+    if (n < n_hi && k_ok) slab[(size_t)n * ld + k] = acc[e];
+  }
+}
+
 // Block tile = (WN*RN*32) channels x (WK*RK*32) k, 64*WN*WK threads, 32 reduction rows per step.
 template <int WN, int WK, int RN, int RK>
 __global__ __launch_bounds__(64 * WN * WK) void conv_wgrad_kernel(WgradArgs a) {
@@ -78,15 +137,12 @@ __global__ __launch_bounds__(64 * WN * WK) void conv_wgrad_kernel(WgradArgs a) {
   const int wave = tid >> 6;
   const int wn = wave / WK, wk = wave % WK;
 
-  const int bid = blockIdx.x;
-  const int tiles = a.tiles_n * a.tiles_k;
-  int tile, split;
-  if (!wg_map(a, bid, tiles, tile, split)) return;
-  const int n0 = (tile % a.tiles_n) * TNB;
-  const int k0 = (tile / a.tiles_n) * TKB;
-  const int m_begin = split * a.m_per_split;
-  int m_end = m_begin + a.m_per_split;
-  if (m_end > a.M) m_end = a.M;
+  const WgBlock blk(a);
+  if (!blk.ok) return;
+  const int n0 = (blk.tile % a.tiles_n) * TNB;
+  const int k0 = (blk.tile / a.tiles_n) * TKB;
+  int m_begin, m_end;
+  blk.rows(a, m_begin, m_end);
 
   // fixed per-thread k-chunk decomposition for the X gather
   const int xkc = tid % XC;                 // NT % XC == 0 for all instantiations
@@ -163,16 +219,8 @@ __global__ __launch_bounds__(64 * WN * WK) void conv_wgrad_kernel(WgradArgs a) {
   };
 
   f32x16 acc[RN][RK];
-#pragma unroll
-  for (int i = 0; i < RN; ++i)
-#pragma unroll
-    for (int jj = 0; jj < RK; ++jj)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][jj][e] = 0.f;
-
-  // transposed-read lane geometry (see file header): rows = reduction index, columns = n or k
-  const int tr_row = 8 * (lane >> 5) + ((lane & 15) >> 2);
-  const int tr_col = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  acc_zero(acc);
+  const int tr_row = tr_row_of(lane), tr_col = tr_col_of(lane);
 
   const int nsteps = (m_end - m_begin + 31) / 32;
   if (nsteps > 0) {
@@ -189,23 +237,9 @@ __global__ __launch_bounds__(64 * WN * WK) void conv_wgrad_kernel(WgradArgs a) {
     for (int ks = 0; ks < 2; ++ks) {
       bf16x8 yf[RN], xf[RK];
 #pragma unroll
-      for (int i = 0; i < RN; ++i) {
-        const unsigned char* p = Ys + (ks * 16 + tr_row) * SY + ((wn * RN + i) * 32 + tr_col) * 2;
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p));
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p + 4 * SY));
-        typedef short s16x8 __attribute__((ext_vector_type(8)));
-        s16x8 t = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        yf[i] = __builtin_bit_cast(bf16x8, t);
-      }
+      for (int i = 0; i < RN; ++i) yf[i] = tr_load(Ys + (ks * 16 + tr_row) * SY + ((wn * RN + i) * 32 + tr_col) * 2, SY);
 #pragma unroll
-      for (int jj = 0; jj < RK; ++jj) {
-        const unsigned char* p = Xs + (ks * 16 + tr_row) * SX + ((wk * RK + jj) * 32 + tr_col) * 2;
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p));
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p + 4 * SX));
-        typedef short s16x8 __attribute__((ext_vector_type(8)));
-        s16x8 t = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        xf[jj] = __builtin_bit_cast(bf16x8, t);
-      }
+      for (int jj = 0; jj < RK; ++jj) xf[jj] = tr_load(Xs + (ks * 16 + tr_row) * SX + ((wk * RK + jj) * 32 + tr_col) * 2, SX);
 #pragma unroll
       for (int i = 0; i < RN; ++i)
 #pragma unroll
@@ -216,18 +250,13 @@ __global__ __launch_bounds__(64 * WN * WK) void conv_wgrad_kernel(WgradArgs a) {
     __syncthreads();
   }
 
-  // D[n][k]: k = lane & 31, n = 8*(e>>2) + 4*(lane>>5) + (e&3)
-  float* slab = a.part + (size_t)split * a.N * a.Kp;
+  float* slab = a.part + (size_t)blk.split * a.N * a.Kp;
 #pragma unroll
   for (int i = 0; i < RN; ++i)
 #pragma unroll
     for (int jj = 0; jj < RK; ++jj) {
-      int k = k0 + (wk * RK + jj) * 32 + (lane & 31);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        int n = n0 + (wn * RN + i) * 32 + 8 * (e >> 2) + 4 * (lane >> 5) + (e & 3);
-        if (n < a.N && k < a.Kp) slab[(size_t)n * a.Kp + k] = acc[i][jj][e];
-      }
+      const int k = k0 + (wk * RK + jj) * 32 + (lane & 31);
+      store_acc_tile(acc[i][jj], slab, a.Kp, n0 + (wn * RN + i) * 32, a.N, k, k < a.Kp);
     }
 }
 
@@ -239,11 +268,69 @@ __global__ __launch_bounds__(64 * WN * WK) void conv_wgrad_kernel(WgradArgs a) {
 // unpadded; the transposed fragment reads stay conflict-free through an XOR of the 16-byte chunk index with the row
 // (applied on the source side: LDS slot (row, c') holds chunk c = c' ^ swz(row)).  Padding / ragged rows / ragged
 // channels are out-of-range buffer offsets, which the buffer unit zero-fills.
-__host__ __device__ constexpr int swz_mask(int row_b) { return row_b % 256 == 0 ? 3 : (row_b % 128 == 0 ? 2 : 0); }
-__device__ __forceinline__ int swz(int row, int mask) { return mask == 3 ? 4 * (row & 3) : (mask == 2 ? 4 * ((row >> 1) & 1) : 0); }
-
 template <int N>
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// DMA instruction t of a dY tile (RBY-byte rows) fills LDS bytes [1024 t, 1024 t + 1024), 16 per lane: the lane's tile row,
+// whether its 8 dY columns (ny0 .. of the block, below ny_hi; the chunk un-swizzled on the source side) exist, and the byte
+// offset of its source at the split's first step.
+template <int RBY>
+__device__ __forceinline__ void dy_slot_setup(const WgradArgs& a, int t, int lane, int m_begin, int ny0, int ny_hi, int& row, bool& ok,
+                                              uint32_t& off) {
+  const int L = t * 1024 + lane * 16;
+  row = L / RBY;
+  const int pc = (L % RBY) >> 4;
+  const int c = pc ^ swz(row, swz_mask(RBY));
+  ok = (ny0 + c * 8) < ny_hi;
+  off = (uint32_t)(((long)(m_begin + row) * a.ldy + a.ycoff + ny0 + c * 8) * 2);
+}
+// A slot that streams rows in order (dY; X of a pointwise conv): this step's offset, then on by one tile's rows.
+__device__ __forceinline__ uint32_t stream_slot_next(uint32_t& off, uint32_t step) {
+  const uint32_t vo = off;
+  off += step;
+  return vo;
+}
+
+// The ring step's wait: tile st must have landed (then the barrier), while the NST - 1 tiles issued ahead stay in flight where they
+// can.  vmcnt counts this wave's own DMA instructions, oldest first; a tile is my_slots of them (SLOTS, or SLOTS - 1 for the waves
+// that the instruction count does not reach in the last round), and the immediate must be a constant - hence the pairs.
+//   newer >= NST - 2: the steady state.  NST - 1 tiles are outstanding, all but the oldest may stay: (NST - 2) tiles.
+//   newer == 1, NST > 3: the ring drains, nothing was issued in the last steps; exactly one newer tile is outstanding.
+//   otherwise: the last tile (newer == 0), or a depth in between of a ring deeper than 4 (not counted out): everything.
+template <int NST, int SLOTS>
+__device__ __forceinline__ void ring_wait(int newer, int my_slots) {
+  if (newer >= NST - 2) {
+    if (my_slots == SLOTS) wait_vm<(NST - 2) * SLOTS>(); else wait_vm<(NST - 2) * (SLOTS - 1)>();
+  } else if (newer == 1 && NST > 3) {
+    if (my_slots == SLOTS) wait_vm<SLOTS>(); else wait_vm<SLOTS - 1>();
+  } else {
+    wait_vm<0>();
+  }
+}
+
+// ---- the fragment step of the ring kernels, as inline asm -----------------------------------------------------------------------
+// Fragment reads are issued as inline asm: the compiler cannot tell which ring stage a ds_read touches and would otherwise drain
+// every outstanding LDS-DMA (s_waitcnt vmcnt(0)) in front of them, which serialises the ring.  An asm read is invisible to the
+// compiler's wait counting, so a step is: every tr_read of the step (all k-groups up front), then per k-group frag_wait, frag_pin
+// of each of the group's registers, and only then frag_join and the MFMAs.  Only the order of these volatile statements and the
+// pins keep the MFMAs behind the data.
+__device__ __forceinline__ void tr_read(s16x4& lo, s16x4& hi, uint32_t addr, int rb) {
+  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(addr) : "memory");
+  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(hi) : "v"(addr + 4 * rb) : "memory");
+}
+// Wait for k-group ks of KS, PER reads each (LDS returns in order; the counter saturates at 15): the first group waits for its
+// share only, the last for everything.  The rungs are constants; the third covers KS = 2 (both ring kernels as instantiated: there
+// the ladder is "0 for the last group, min(PER, 15) for the first"), the fourth is the KS = 4 build (WG_RS = 64).
+template <int KS, int PER>
+__device__ __forceinline__ void frag_wait(int ks) {
+  if (ks == KS - 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  else if ((KS - 1 - ks) * PER >= 15) asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory");
+  else if (ks == KS - 2) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(PER < 15 ? PER : 15) : "memory");
+  else asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(2 * PER < 15 ? 2 * PER : 15) : "memory");
+}
+// the registers are operands of an empty asm so that the MFMAs cannot be hoisted above the wait
+__device__ __forceinline__ void frag_pin(s16x4& lo, s16x4& hi) { asm volatile("" : "+v"(lo), "+v"(hi)); }
+
 // GM = how the X gather address of a step is produced: 1 pointwise (1x1 / stride 1 / no padding: a plain strided
 // stream like dY, no address arithmetic in the loop), 0 two magic divisions per step (any geometry).  A compile-time
 // choice: the loop is instruction-issue-bound (rocprofv3: MFMA pipe utilisation 12 %), a run-time switch would keep
@@ -269,21 +356,18 @@ __global__ __launch_bounds__(64 * WN * WK) void conv_wgrad_dma_kernel(WgradArgs 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wn = wave / WK, wk = wave % WK;
 
-  const int bid = blockIdx.x;
-  const int tiles = a.tiles_n * a.tiles_k;
-  int tile, split;
-  if (!wg_map(a, bid, tiles, tile, split)) return;
+  const WgBlock blk(a);
+  if (!blk.ok) return;
   // slab rows n0 .. of this block; dY columns ny0 .. of its layer (dual form: the second half of the n tiles reads dy2)
-  const int nt = tile % a.tiles_n;
+  const int nt = blk.tile % a.tiles_n;
   const bool half2 = a.n_half && nt >= (a.tiles_n >> 1);
   const int n0 = half2 ? a.n_half + (nt - (a.tiles_n >> 1)) * TNB : nt * TNB;
   const int ny0 = half2 ? n0 - a.n_half : n0;
   const int ny_hi = a.n_half ? a.n_half : a.N;                       // dY columns of one layer
   const int n_hi = (a.n_half && !half2) ? a.n_half : a.N;            // slab rows this block may write
-  const int k0 = (tile / a.tiles_n) * TKB;
-  const int m_begin = split * a.m_per_split;
-  int m_end = m_begin + a.m_per_split;
-  if (m_end > a.M) m_end = a.M;
+  const int k0 = (blk.tile / a.tiles_n) * TKB;
+  int m_begin, m_end;
+  blk.rows(a, m_begin, m_end);
   const int HWo = a.Ho * a.Wo;
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -310,12 +394,7 @@ __global__ __launch_bounds__(64 * WN * WK) void conv_wgrad_dma_kernel(WgradArgs 
     if (!ROLE_STATIC && t >= NI) continue;
     ++my_slots;
     if (ROLE_STATIC ? (i < NIY / NW) : (t < NIY)) {
-      const int L = t * 1024 + lane * 16;
-      const int row = L / RBY, pc = (L % RBY) >> 4;
-      const int c = pc ^ swz(row, MY);
-      s_row[i] = row;
-      s_ok[i] = (ny0 + c * 8) < ny_hi;
-      s_off[i] = (uint32_t)(((long)(m_begin + row) * a.ldy + a.ycoff + ny0 + c * 8) * 2);
+      dy_slot_setup<RBY>(a, t, lane, m_begin, ny0, ny_hi, s_row[i], s_ok[i], s_off[i]);
     } else {
       const int L = (t - NIY) * 1024 + lane * 16;
       const int row = L / RBX, pc = (L % RBX) >> 4;
@@ -347,11 +426,9 @@ __global__ __launch_bounds__(64 * WN * WK) void conv_wgrad_dma_kernel(WgradArgs 
       bool ok = s_ok[i] && m < m_end;
       const bool is_y = ROLE_STATIC ? (i < NIY / NW) : (t < NIY);
       if (is_y) {
-        vo = s_off[i];
-        s_off[i] += ystep;
+        vo = stream_slot_next(s_off[i], ystep);
       } else if (pointwise) {
-        vo = s_off[i];
-        s_off[i] += xstep;
+        vo = stream_slot_next(s_off[i], xstep);
       } else {
         // q = m / d with magic = ceil(2^32 / d): the estimate is q or q + 1 for any 31-bit m
         uint32_t b = magic_hwo ? __umulhi((uint32_t)m, magic_hwo) : (uint32_t)m;
@@ -379,93 +456,49 @@ __global__ __launch_bounds__(64 * WN * WK) void conv_wgrad_dma_kernel(WgradArgs 
   };
 
   f32x16 acc[RN][RK];
-#pragma unroll
-  for (int i = 0; i < RN; ++i)
-#pragma unroll
-    for (int jj = 0; jj < RK; ++jj)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][jj][e] = 0.f;
+  acc_zero(acc);
 
-  const int tr_row = 8 * (lane >> 5) + ((lane & 15) >> 2);
-  const int tr_col = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  const int tr_row = tr_row_of(lane), tr_col = tr_col_of(lane);
   const int sy = swz(tr_row, MY), sx = swz(tr_row, MX);    // the rows a lane reads differ by multiples of 4 only
   const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
   uint32_t yoff[RN], xoff[RK];
 #pragma unroll
-  for (int i = 0; i < RN; ++i) {
-    const int col = (wn * RN + i) * 32 + tr_col;
-    yoff[i] = (uint32_t)(tr_row * RBY + (((col >> 3) ^ sy) << 4) + (col & 7) * 2);
-  }
+  for (int i = 0; i < RN; ++i) yoff[i] = (uint32_t)tr_off(tr_row, (wn * RN + i) * 32 + tr_col, RBY, sy);
 #pragma unroll
-  for (int jj = 0; jj < RK; ++jj) {
-    const int col = (wk * RK + jj) * 32 + tr_col;
-    xoff[jj] = (uint32_t)(tr_row * RBX + (((col >> 3) ^ sx) << 4) + (col & 7) * 2);
-  }
+  for (int jj = 0; jj < RK; ++jj) xoff[jj] = (uint32_t)tr_off(tr_row, (wk * RK + jj) * 32 + tr_col, RBX, sx);
 
   const int nsteps = (m_end - m_begin + RS - 1) / RS;
 #pragma unroll
   for (int p = 0; p < NST - 1; ++p)
     if (p < nsteps) issue(p);
   for (int st = 0; st < nsteps; ++st) {
-    // tile st must have landed; up to NST-2 newer tiles (my_slots instructions each, SLOTS or SLOTS-1) stay in flight
-    const int newer = nsteps - 1 - st;
-    if (newer >= NST - 2) {
-      if (my_slots == SLOTS) wait_vm<(NST - 2) * SLOTS>(); else wait_vm<(NST - 2) * (SLOTS - 1)>();
-    } else if (newer == 1 && NST > 3) {
-      if (my_slots == SLOTS) wait_vm<SLOTS>(); else wait_vm<SLOTS - 1>();
-    } else {
-      wait_vm<0>();
-    }
+    ring_wait<NST, SLOTS>(nsteps - 1 - st, my_slots);
     __builtin_amdgcn_s_barrier();
 #ifndef WG_ABL_NOISSUE
     if (st + NST - 1 < nsteps) issue((st + NST - 1) % NST);
 #endif
-    // Fragment reads are issued as inline asm: the compiler cannot tell which ring stage a ds_read touches and
-    // would otherwise drain every outstanding LDS-DMA (s_waitcnt vmcnt(0)) in front of them, which serialises the
-    // ring.  Both k-halves are read up front; the first MFMA group waits for its half only (LDS returns in order).
     const uint32_t ys = lds_base + (uint32_t)((st % NST) * STAGE);
     const uint32_t xs = ys + RS * RBY;
     s16x4 ylo[KS][RN], yhi[KS][RN], xlo[KS][RK], xhi[KS][RK];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
 #pragma unroll
-      for (int i = 0; i < RN; ++i) {
-        const uint32_t p = ys + yoff[i] + (uint32_t)(ks * 16 * RBY);
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(ylo[ks][i]) : "v"(p) : "memory");
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(yhi[ks][i]) : "v"(p + 4 * RBY) : "memory");
-      }
+      for (int i = 0; i < RN; ++i) tr_read(ylo[ks][i], yhi[ks][i], ys + yoff[i] + (uint32_t)(ks * 16 * RBY), RBY);
 #pragma unroll
-      for (int jj = 0; jj < RK; ++jj) {
-        const uint32_t p = xs + xoff[jj] + (uint32_t)(ks * 16 * RBX);
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(xlo[ks][jj]) : "v"(p) : "memory");
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(xhi[ks][jj]) : "v"(p + 4 * RBX) : "memory");
-      }
+      for (int jj = 0; jj < RK; ++jj) tr_read(xlo[ks][jj], xhi[ks][jj], xs + xoff[jj] + (uint32_t)(ks * 16 * RBX), RBX);
     }
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      // wait for this k-group's reads (LDS returns in order; the counter saturates at 15); the registers are
-      // operands of the empty asm below so that the MFMAs cannot be hoisted above the wait
-      constexpr int PER = 2 * (RN + RK);
-      if (ks == KS - 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      else if ((KS - 1 - ks) * PER >= 15) asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory");
-      else if (ks == KS - 2) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(PER < 15 ? PER : 15) : "memory");
-      else asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(2 * PER < 15 ? 2 * PER : 15) : "memory");
+      frag_wait<KS, 2 * (RN + RK)>(ks);
 #pragma unroll
-      for (int i = 0; i < RN; ++i) asm volatile("" : "+v"(ylo[ks][i]), "+v"(yhi[ks][i]));
+      for (int i = 0; i < RN; ++i) frag_pin(ylo[ks][i], yhi[ks][i]);
 #pragma unroll
-      for (int jj = 0; jj < RK; ++jj) asm volatile("" : "+v"(xlo[ks][jj]), "+v"(xhi[ks][jj]));
-      typedef short s16x8 __attribute__((ext_vector_type(8)));
+      for (int jj = 0; jj < RK; ++jj) frag_pin(xlo[ks][jj], xhi[ks][jj]);
       bf16x8 yf[RN], xf[RK];
 #pragma unroll
-      for (int i = 0; i < RN; ++i) {
-        s16x8 t = {ylo[ks][i][0], ylo[ks][i][1], ylo[ks][i][2], ylo[ks][i][3], yhi[ks][i][0], yhi[ks][i][1], yhi[ks][i][2], yhi[ks][i][3]};
-        yf[i] = __builtin_bit_cast(bf16x8, t);
-      }
+      for (int i = 0; i < RN; ++i) yf[i] = frag_join(ylo[ks][i], yhi[ks][i]);
 #pragma unroll
-      for (int jj = 0; jj < RK; ++jj) {
-        s16x8 t = {xlo[ks][jj][0], xlo[ks][jj][1], xlo[ks][jj][2], xlo[ks][jj][3], xhi[ks][jj][0], xhi[ks][jj][1], xhi[ks][jj][2], xhi[ks][jj][3]};
-        xf[jj] = __builtin_bit_cast(bf16x8, t);
-      }
+      for (int jj = 0; jj < RK; ++jj) xf[jj] = frag_join(xlo[ks][jj], xhi[ks][jj]);
 #pragma unroll
       for (int i = 0; i < RN; ++i)
 #pragma unroll
@@ -477,18 +510,13 @@ __global__ __launch_bounds__(64 * WN * WK) void conv_wgrad_dma_kernel(WgradArgs 
 #endif
     }
   }
-  // D[n][k]: k = lane & 31, n = 8*(e>>2) + 4*(lane>>5) + (e&3)
-  float* slab = a.part + (size_t)split * a.N * a.Kp;
+  float* slab = a.part + (size_t)blk.split * a.N * a.Kp;
 #pragma unroll
   for (int i = 0; i < RN; ++i)
 #pragma unroll
     for (int jj = 0; jj < RK; ++jj) {
-      int k = k0 + (wk * RK + jj) * 32 + (lane & 31);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        int n = n0 + (wn * RN + i) * 32 + 8 * (e >> 2) + 4 * (lane >> 5) + (e & 3);
-        if (n < n_hi && k < a.Kp) slab[(size_t)n * a.Kp + k] = acc[i][jj][e];
-      }
+      const int k = k0 + (wk * RK + jj) * 32 + (lane & 31);
+      store_acc_tile(acc[i][jj], slab, a.Kp, n0 + (wn * RN + i) * 32, n_hi, k, k < a.Kp);
     }
 }
 
@@ -529,15 +557,12 @@ __global__ __launch_bounds__(64 * WN * 3 * WC) void conv_wgrad_row3_kernel(Wgrad
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wc = wave % WC, kh = (wave / WC) % 3, wn = wave / (3 * WC);
 
-  const int bid = blockIdx.x;
-  const int tiles = a.tiles_n * a.tiles_k;
-  int tile, split;
-  if (!wg_map(a, bid, tiles, tile, split)) return;
-  const int n0 = (tile % a.tiles_n) * TNB;
-  const int c0 = (tile / a.tiles_n) * (WC * 32);
-  const int m_begin = split * a.m_per_split;
-  int m_end = m_begin + a.m_per_split;
-  if (m_end > a.M) m_end = a.M;
+  const WgBlock blk(a);
+  if (!blk.ok) return;
+  const int n0 = (blk.tile % a.tiles_n) * TNB;
+  const int c0 = (blk.tile / a.tiles_n) * (WC * 32);
+  int m_begin, m_end;
+  blk.rows(a, m_begin, m_end);
   const int W = a.Ws, H = a.Hs, HW = a.Hs * a.Ws, BHW = a.B * HW;
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -559,12 +584,7 @@ __global__ __launch_bounds__(64 * WN * 3 * WC) void conv_wgrad_row3_kernel(Wgrad
     if (t >= NI) continue;
     ++my_slots;
     if (t < NIY) {
-      const int L = t * 1024 + lane * 16;
-      const int row = L / RBY, pc = (L % RBY) >> 4;
-      const int c = pc ^ swz(row, MY);
-      s_row[i] = row;
-      s_ok[i] = (n0 + c * 8) < a.N;
-      s_off[i] = (uint32_t)(((long)(m_begin + row) * a.ldy + a.ycoff + n0 + c * 8) * 2);
+      dy_slot_setup<RBY>(a, t, lane, m_begin, n0, a.N, s_row[i], s_ok[i], s_off[i]);
     } else {
       const int tx = t - NIY;
       const int xt = tx / 3, part = tx - xt * 3;
@@ -592,8 +612,7 @@ __global__ __launch_bounds__(64 * WN * 3 * WC) void conv_wgrad_row3_kernel(Wgrad
       bool ok = s_ok[i];
       if (t < NIY) {
         ok = ok && (mb + s_row[i]) < m_end;
-        vo = s_off[i];
-        s_off[i] += ystep;
+        vo = stream_slot_next(s_off[i], ystep);
       } else {
         const int p = s_p[i];
         s_p[i] += RS;
@@ -622,26 +641,16 @@ __global__ __launch_bounds__(64 * WN * 3 * WC) void conv_wgrad_row3_kernel(Wgrad
   };
 
   f32x16 acc[RN][3];
-#pragma unroll
-  for (int i = 0; i < RN; ++i)
-#pragma unroll
-    for (int kw = 0; kw < 3; ++kw)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][kw][e] = 0.f;
+  acc_zero(acc);
 
-  const int tr_row = 8 * (lane >> 5) + ((lane & 15) >> 2);
-  const int tr_col = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  const int tr_row = tr_row_of(lane), tr_col = tr_col_of(lane);
   const int sy = swz(tr_row, MY);
   const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
   uint32_t yoff[RN], xoff[3];
 #pragma unroll
-  for (int i = 0; i < RN; ++i) {
-    const int col = (wn * RN + i) * 32 + tr_col;
-    yoff[i] = (uint32_t)(tr_row * RBY + (((col >> 3) ^ sy) << 4) + (col & 7) * 2);
-  }
+  for (int i = 0; i < RN; ++i) yoff[i] = (uint32_t)tr_off(tr_row, (wn * RN + i) * 32 + tr_col, RBY, sy);
 #pragma unroll
-  for (int kw = 0; kw < 3; ++kw)
-    xoff[kw] = (uint32_t)(RS * RBY + (kh * WC + wc) * XT_BYTES + (tr_row + kw) * RBX + ((tr_col >> 3) << 4) + (tr_col & 7) * 2);
+  for (int kw = 0; kw < 3; ++kw) xoff[kw] = (uint32_t)(RS * RBY + (kh * WC + wc) * XT_BYTES + tr_off(tr_row + kw, tr_col, RBX, 0));
 
   const int nsteps = (m_end - m_begin + RS - 1) / RS;
   int ox_step = m_begin % W;                // ox of the step's first row (wave-uniform)
@@ -649,14 +658,7 @@ __global__ __launch_bounds__(64 * WN * 3 * WC) void conv_wgrad_row3_kernel(Wgrad
   for (int p = 0; p < NST - 1; ++p)
     if (p < nsteps) issue(p);
   for (int st = 0; st < nsteps; ++st) {
-    const int newer = nsteps - 1 - st;
-    if (newer >= NST - 2) {
-      if (my_slots == SLOTS) wait_vm<(NST - 2) * SLOTS>(); else wait_vm<(NST - 2) * (SLOTS - 1)>();
-    } else if (newer == 1 && NST > 3) {
-      if (my_slots == SLOTS) wait_vm<SLOTS>(); else wait_vm<SLOTS - 1>();
-    } else {
-      wait_vm<0>();
-    }
+    ring_wait<NST, SLOTS>(nsteps - 1 - st, my_slots);
     __builtin_amdgcn_s_barrier();
     if (st + NST - 1 < nsteps) issue((st + NST - 1) % NST);
     // rows of this step on the left / right image border (taps kw = 0 / kw = 2 must not see their flattened neighbour)
@@ -671,28 +673,17 @@ __global__ __launch_bounds__(64 * WN * 3 * WC) void conv_wgrad_row3_kernel(Wgrad
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
 #pragma unroll
-      for (int i = 0; i < RN; ++i) {
-        const uint32_t p = sb + yoff[i] + (uint32_t)(ks * 16 * RBY);
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(ylo[ks][i]) : "v"(p) : "memory");
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(yhi[ks][i]) : "v"(p + 4 * RBY) : "memory");
-      }
+      for (int i = 0; i < RN; ++i) tr_read(ylo[ks][i], yhi[ks][i], sb + yoff[i] + (uint32_t)(ks * 16 * RBY), RBY);
 #pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        const uint32_t p = sb + xoff[kw] + (uint32_t)(ks * 16 * RBX);
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(xlo[ks][kw]) : "v"(p) : "memory");
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(xhi[ks][kw]) : "v"(p + 4 * RBX) : "memory");
-      }
+      for (int kw = 0; kw < 3; ++kw) tr_read(xlo[ks][kw], xhi[ks][kw], sb + xoff[kw] + (uint32_t)(ks * 16 * RBX), RBX);
     }
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      constexpr int PER = 2 * (RN + 3);
-      if (ks == KS - 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      else asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(PER < 15 ? PER : 15) : "memory");
+      frag_wait<KS, 2 * (RN + 3)>(ks);
 #pragma unroll
-      for (int i = 0; i < RN; ++i) asm volatile("" : "+v"(ylo[ks][i]), "+v"(yhi[ks][i]));
+      for (int i = 0; i < RN; ++i) frag_pin(ylo[ks][i], yhi[ks][i]);
 #pragma unroll
-      for (int kw = 0; kw < 3; ++kw) asm volatile("" : "+v"(xlo[ks][kw]), "+v"(xhi[ks][kw]));
-      typedef short s16x8 __attribute__((ext_vector_type(8)));
+      for (int kw = 0; kw < 3; ++kw) frag_pin(xlo[ks][kw], xhi[ks][kw]);
       typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
       if ((inv0 | inv2) != 0) {      // wave-uniform: border rows in this step (1 step in W / 32 for the wide layers)
         const int sh = ks * 16 + 8 * (lane >> 5);
@@ -710,15 +701,9 @@ __global__ __launch_bounds__(64 * WN * 3 * WC) void conv_wgrad_row3_kernel(Wgrad
       }
       bf16x8 yf[RN], xf[3];
 #pragma unroll
-      for (int i = 0; i < RN; ++i) {
-        s16x8 t = {ylo[ks][i][0], ylo[ks][i][1], ylo[ks][i][2], ylo[ks][i][3], yhi[ks][i][0], yhi[ks][i][1], yhi[ks][i][2], yhi[ks][i][3]};
-        yf[i] = __builtin_bit_cast(bf16x8, t);
-      }
+      for (int i = 0; i < RN; ++i) yf[i] = frag_join(ylo[ks][i], yhi[ks][i]);
 #pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        s16x8 t = {xlo[ks][kw][0], xlo[ks][kw][1], xlo[ks][kw][2], xlo[ks][kw][3], xhi[ks][kw][0], xhi[ks][kw][1], xhi[ks][kw][2], xhi[ks][kw][3]};
-        xf[kw] = __builtin_bit_cast(bf16x8, t);
-      }
+      for (int kw = 0; kw < 3; ++kw) xf[kw] = frag_join(xlo[ks][kw], xhi[ks][kw]);
 #pragma unroll
       for (int i = 0; i < RN; ++i)
 #pragma unroll
@@ -726,20 +711,14 @@ __global__ __launch_bounds__(64 * WN * 3 * WC) void conv_wgrad_row3_kernel(Wgrad
           acc[i][kw] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(yf[i], xf[kw], acc[i][kw], 0, 0, 0);
     }
   }
-  // D[n][k]: k = lane & 31, n = 8*(e>>2) + 4*(lane>>5) + (e&3); slab column k = (kh*3 + kw) * Cin + channel
-  float* slab = a.part + (size_t)split * a.N * a.Kp;
+  // slab column k = (kh*3 + kw) * Cin + channel
+  float* slab = a.part + (size_t)blk.split * a.N * a.Kp;
   const int ch = c0 + wc * 32 + (lane & 31);
 #pragma unroll
   for (int i = 0; i < RN; ++i)
 #pragma unroll
-    for (int kw = 0; kw < 3; ++kw) {
-      const int k = (kh * 3 + kw) * a.Cin + ch;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int n = n0 + (wn * RN + i) * 32 + 8 * (e >> 2) + 4 * (lane >> 5) + (e & 3);
-        if (n < a.N && ch < a.Cin) slab[(size_t)n * a.Kp + k] = acc[i][kw][e];
-      }
-    }
+    for (int kw = 0; kw < 3; ++kw)
+      store_acc_tile(acc[i][kw], slab, a.Kp, n0 + (wn * RN + i) * 32, a.N, (kh * 3 + kw) * a.Cin + ch, ch < a.Cin);
 }
 
 // grad[n][ci][kh][kw] = scale * sum_s part[s][n][k(kh,kw,ci)]   (stem: k = (kh, kw', dx, c4), see pack)
@@ -855,7 +834,6 @@ struct WgradKnobs {
   int row3;            // KODHIP_WGRAD_ROW3: 0 = off, 1 (default) = where it measured faster, 2 = every eligible layer
   int slots;           // KODHIP_WGRAD_SLOTS: resident-block target of the generic and dual forms (default 512)
   int row3_slots;      // KODHIP_WGRAD_ROW3_SLOTS: resident-wave target of the ROW3 form (default 3072)
-  int stem_tw;         // KODHIP_STEM_BWD_TW: 80 (default) | 160
   int stem_blocks;     // KODHIP_STEM_BWD_BLOCKS: block target of the fused stem backward (0 = every resident slot of the chip)
 };
 const WgradKnobs& wgrad_knobs() {
@@ -869,8 +847,6 @@ const WgradKnobs& wgrad_knobs() {
     if (v.slots < 8) v.slots = 512;
     v.row3_slots = num(getenv("KODHIP_WGRAD_ROW3_SLOTS"), 3072);
     if (v.row3_slots < 96) v.row3_slots = 3072;
-    v.stem_tw = num(getenv("KODHIP_STEM_BWD_TW"), 80);
-    if (v.stem_tw != 80 && v.stem_tw != 160) v.stem_tw = 80;
     v.stem_blocks = num(getenv("KODHIP_STEM_BWD_BLOCKS"), 0);
     if (v.stem_blocks < 1) v.stem_blocks = 0;
     return v;
@@ -1012,14 +988,14 @@ struct StemBwdArgs {
 
 // staged pairs per kernel row: TW + 2 used, and PRW * 16 B = 128 mod 256 so that the two kernel rows a 4-tap column group
 // touches land on disjoint LDS banks
-__host__ __device__ constexpr int stem_prw(int TW) { return TW == 160 ? 168 : 88; }
+__host__ __device__ constexpr int stem_prw(int TW) { return TW + 8; }
 __host__ __device__ constexpr int stem_xb(int TW) { return (6 * stem_prw(TW) * 16 + 1023) / 1024 * 1024; }
 
 // NT = 32-channel output tiles per block: 1 for N <= 32 (yv5n / yv5s), 2 for N <= 64 (yv5m: 48, yv5l: 64) - the dA / y
 // tile rows are then 128 B (two-way bank conflicts in the transposing reads of dY, accepted) and every wave runs two MFMAs
 // per staged X fragment.
 template <int TW, int NT>
-__global__ __launch_bounds__(320, NT == 2 ? 3 : (TW == 160 ? 3 : 5)) void conv_stem_bwd_fused_kernel(StemBwdArgs a) {
+__global__ __launch_bounds__(320, NT == 2 ? 3 : 5) void conv_stem_bwd_fused_kernel(StemBwdArgs a) {
   constexpr int PRW = stem_prw(TW), NW = 5;
   constexpr int CH = 4 * NT, RBG = 64 * NT;              // 16-byte chunks / bytes per dA (dY) / y tile row
   constexpr int XB = stem_xb(TW), GB = TW * RBG;         // X runs | dA tile (becomes dY) | y tile
@@ -1027,6 +1003,7 @@ __global__ __launch_bounds__(320, NT == 2 ? 3 : (TW == 160 ? 3 : 5)) void conv_s
   constexpr int NIX = XB / 1024, NIG = GB / 1024, NI = NIX + 2 * NIG;     // DMA instructions per tile (1 KB each)
   constexpr int ITEMS = TW * CH / 320;                   // 16-byte (pixel, 8-channel chunk) items per thread
   static_assert(GB % 1024 == 0 && TW * CH % 320 == 0 && 320 % CH == 0, "tile must fill whole DMA instructions / thread items");
+  static_assert(PRW * 16 % 256 == 128, "kernel rows must alternate LDS bank halves");
   __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * STAGE];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1095,21 +1072,17 @@ __global__ __launch_bounds__(320, NT == 2 ? 3 : (TW == 160 ? 3 : 5)) void conv_s
     }
   };
 
-  f32x16 acc[NT];
-#pragma unroll
-  for (int n = 0; n < NT; ++n)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[n][e] = 0.f;
+  f32x16 acc[NT][1];           // (one tile column per wave: the shape acc_zero and store_acc_tile take)
+  acc_zero(acc);
 
-  // fragment addresses (transposing reads, lane geometry of conv_wgrad_dma_kernel): rows = reduction index m
-  const int tr_row = 8 * (lane >> 5) + ((lane & 15) >> 2);
-  const int tr_col = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  // fragment addresses (transposing reads): rows = reduction index m; an X "row" is one staged pair, 16 bytes = 8 slab columns
+  const int tr_row = tr_row_of(lane), tr_col = tr_col_of(lane);
   const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
-  const uint32_t yoff = (uint32_t)(XB + tr_row * RBG + tr_col * 2);
+  const uint32_t yoff = (uint32_t)(XB + tr_off(tr_row, tr_col, RBG, 0));
   int tap = wave * 4 + (tr_col >> 3);
   if (tap > 17) tap = 17;                                   // slab columns 144 .. 159 are padding (never reduced)
   const int tkh = tap / 3, tkw = tap - tkh * 3;
-  const uint32_t xoff = (uint32_t)((tkh * PRW + tkw + tr_row) * 16 + (tr_col & 7) * 2);
+  const uint32_t xoff = (uint32_t)tr_off(tkh * PRW + tkw + tr_row, tr_col & 7, 16, 0);
 
   if (t_begin < t_end) stage(t_begin, 0);
   int buf = 0;
@@ -1153,37 +1126,25 @@ __global__ __launch_bounds__(320, NT == 2 ? 3 : (TW == 160 ? 3 : 5)) void conv_s
       s16x4 ylo[NT], yhi[NT], xlo, xhi;
       const uint32_t px = sb + xoff + (uint32_t)(ks * 16 * 16);
 #pragma unroll
-      for (int n = 0; n < NT; ++n) {
-        const uint32_t py = sb + yoff + (uint32_t)(ks * 16 * RBG + n * 64);
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(ylo[n]) : "v"(py) : "memory");
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(yhi[n]) : "v"(py + 4 * RBG) : "memory");
-      }
-      asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(xlo) : "v"(px) : "memory");
-      asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(xhi) : "v"(px + 4 * 16) : "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      asm volatile("" : "+v"(xlo), "+v"(xhi));
-      typedef short s16x8 __attribute__((ext_vector_type(8)));
-      const s16x8 tx = {xlo[0], xlo[1], xlo[2], xlo[3], xhi[0], xhi[1], xhi[2], xhi[3]};
+      for (int n = 0; n < NT; ++n) tr_read(ylo[n], yhi[n], sb + yoff + (uint32_t)(ks * 16 * RBG + n * 64), RBG);
+      tr_read(xlo, xhi, px, 16);
+      frag_wait<1, 2 * (NT + 1)>(0);
+      frag_pin(xlo, xhi);
+      const bf16x8 xf = frag_join(xlo, xhi);
 #pragma unroll
       for (int n = 0; n < NT; ++n) {
-        asm volatile("" : "+v"(ylo[n]), "+v"(yhi[n]));
-        const s16x8 ty = {ylo[n][0], ylo[n][1], ylo[n][2], ylo[n][3], yhi[n][0], yhi[n][1], yhi[n][2], yhi[n][3]};
-        acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ty), __builtin_bit_cast(bf16x8, tx), acc[n], 0, 0, 0);
+        frag_pin(ylo[n], yhi[n]);
+        acc[n][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_join(ylo[n], yhi[n]), xf, acc[n][0], 0, 0, 0);
       }
     }
     buf ^= 1;
   }
 
-  // D[n][k]: k = 32 wave + (lane & 31), n = 32 tile + 8 (e >> 2) + 4 (lane >> 5) + (e & 3)
+  // every block writes its whole slab: 32 NT rows (rows past N are zero) x 160 columns, wave w columns 32 w ..
   float* slab = a.part + (size_t)blockIdx.x * (32 * NT) * 160;
-  const int k = wave * 32 + (lane & 31);
 #pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int n = nt * 32 + 8 * (e >> 2) + 4 * (lane >> 5) + (e & 3);
-      slab[(size_t)n * 160 + k] = acc[nt][e];
-    }
+  // (no bounds here: n_hi = every row of the slab, k_ok = true, both folded away)
+  for (int nt = 0; nt < NT; ++nt) store_acc_tile(acc[nt][0], slab, 160, nt * 32, 32 * NT, wave * 32 + (lane & 31), true);
 }
 
 template <int WN, int RN, int WC>
@@ -1248,19 +1209,19 @@ int wgrad_partial(WgradArgs& a, const char* who, const void* x, const void* dy, 
   return KOD_EARG;
 }
 
-// The fused stem backward's launch (conv_stem_bwd_fused_kernel): row-aligned tiles of TW output pixels dealt to `blocks` blocks,
-// a slab of slab_rows x 160 floats per block.
+// The fused stem backward's launch (conv_stem_bwd_fused_kernel): row-aligned tiles of STEM_TW output pixels dealt to `blocks`
+// blocks, a slab of slab_rows x 160 floats per block.
 // tile width: 80 pixels (four 5-wave blocks per CU; measured 336 us at B = 64 / 640 px against 443 us for 160-pixel tiles
-// with two blocks per CU); KODHIP_STEM_BWD_TW = 80 | 160 is the A/B knob (the two-tile form, N > 32, exists for 80-pixel tiles only)
-struct StemBwdPlan { int TW, tiles_per_row, tiles, blocks, tiles_per_block, slab_rows; };
+// with two blocks per CU, which were retired with their knob)
+constexpr int STEM_TW = 80;
+struct StemBwdPlan { int tiles_per_row, tiles, blocks, tiles_per_block, slab_rows; };
 StemBwdPlan stem_bwd_plan(int B, int H, int Wp, int N) {
   const WgradKnobs& kn = wgrad_knobs();
   StemBwdPlan p;
-  p.TW = (N > 32 || Wp <= 80) ? 80 : kn.stem_tw;
-  p.tiles_per_row = cdiv(Wp, p.TW);
+  p.tiles_per_row = cdiv(Wp, STEM_TW);
   const long tiles = (long)B * (H / 2) * p.tiles_per_row;
-  // KODHIP_STEM_BWD_BLOCKS: A/B knob; default: every resident slot of the chip (2 / 2 / 4 blocks per CU)
-  const int want = kn.stem_blocks ? kn.stem_blocks : (N > 32 ? 512 : (p.TW == 160 ? 512 : 1024));
+  // KODHIP_STEM_BWD_BLOCKS: A/B knob; default: every resident slot of the chip (two-tile form 2, else 4 blocks per CU)
+  const int want = kn.stem_blocks ? kn.stem_blocks : (N > 32 ? 512 : 1024);
   p.tiles = (int)tiles;
   p.blocks = cdiv(tiles, cdiv(tiles, want));
   p.tiles_per_block = cdiv(tiles, p.blocks);
@@ -1353,9 +1314,8 @@ int kodhip_stem_bwd_fused(const void* x, const void* dA, int lda, int dacoff, co
   a.x_bytes = (uint32_t)xb; a.da_bytes = (uint32_t)gb; a.y_bytes = (uint32_t)yb;
   const StemBwdPlan p = stem_bwd_plan(B, H, Wp, N);
   a.tiles_per_row = p.tiles_per_row; a.tiles = p.tiles; a.tiles_per_block = p.tiles_per_block;
-  if (N > 32) hipLaunchKernelGGL((conv_stem_bwd_fused_kernel<80, 2>), dim3(p.blocks), dim3(320), 0, stream, a);
-  else if (p.TW == 160) hipLaunchKernelGGL((conv_stem_bwd_fused_kernel<160, 1>), dim3(p.blocks), dim3(320), 0, stream, a);
-  else hipLaunchKernelGGL((conv_stem_bwd_fused_kernel<80, 1>), dim3(p.blocks), dim3(320), 0, stream, a);
+  if (N > 32) hipLaunchKernelGGL((conv_stem_bwd_fused_kernel<STEM_TW, 2>), dim3(p.blocks), dim3(320), 0, stream, a);
+  else hipLaunchKernelGGL((conv_stem_bwd_fused_kernel<STEM_TW, 1>), dim3(p.blocks), dim3(320), 0, stream, a);
   KOD_LAUNCH_CHECK("stem_bwd_fused");
   return launch_wgrad_reduce((const float*)partials, grad, p.blocks, p.slab_rows, N, 144, 160, 8, 18, 1, gscale, nullptr, 1 << 30, stream);
 }

@@ -16,7 +16,7 @@ from typing import Dict
 # knobs libkodhip.so reads with getenv (csrc/*.hip, csrc/*.h), and the few the package reads outside EngineOptions
 NATIVE_KNOBS = ("KODHIP_NO_FAST", "KODHIP_FORCE_BM", "KODHIP_FORCE_BN", "KODHIP_S2_SEPARATE", "KODHIP_S2_FOLD_MAXC",
                 "KODHIP_ROW3", "KODHIP_WGRAD_DMA", "KODHIP_WGRAD_SLOTS", "KODHIP_WGRAD_ROW3", "KODHIP_WGRAD_ROW3_SLOTS",
-                "KODHIP_STEM_BWD_BLOCKS", "KODHIP_STEM_BWD_TW", "KODHIP_STEM_BWD_STREAM", "KODHIP_DEBUG_STAMPS", "KODHIP_LIB",
+                "KODHIP_STEM_BWD_BLOCKS", "KODHIP_STEM_BWD_STREAM", "KODHIP_DEBUG_STAMPS", "KODHIP_LIB",
                 "KODHIP_BN_U", "KODHIP_BN_GRID", "KODHIP_BN_BLOCK", "KODHIP_BN_LDS")
 
 

@@ -479,6 +479,40 @@ def test_wgrad_every_launch_configuration(geo, cfg):
     assert torch.equal(g3, grad), "scalar slab reduction differs from the 16-byte route"
 
 
+# 1x1 / stride 2: the smallest geometry that sends a narrow-K tile (Kp = 32) through the LDS-DMA kernel's two-division X gather
+# (conv_wgrad_dma_kernel<1, 1, 1, 1, .., GM = 0>: launch_cfg takes GM = 1 for 1x1 / stride 1 / no padding only, and every other case
+# with Kp <= 64 in this file is such a layer).  10 x 6 -> 5 x 3 outputs: 30 rows, one ragged 32-row stage whose gather skips every
+# second pixel and every second image row.
+WGRAD_S2PW = ((2, 16, 10, 6, 32, 1, 2, 0), (32, 32))
+
+
+def check_s2pw_plan():
+    got = wgrad_plan(*WGRAD_S2PW[0])
+    assert (got["tn"], got["tk"], got["row3"]) == (*WGRAD_S2PW[1], 0), got
+    assert got["dma"] == (0 if WG_NO_DMA else 1), got
+    return got
+
+
+def test_wgrad_strided_pointwise_plan(built):
+    check_s2pw_plan()
+
+
+@gpu
+def test_wgrad_strided_pointwise_narrow_k():
+    """Bit for bit, contiguous and as channel slices of sentinel-filled buffers, scale 1 and 2^-7."""
+    geo = WGRAD_S2PW[0]
+    B, Cin, H, W, N, k, s, p = geo
+    got = check_s2pw_plan()
+    x, dy, dw = wref(geo)
+    tailv = torch.full((64,), FS, dtype=torch.float64)
+    grad, splits = wgrad_launch(x, dy, dw.shape, s, p)
+    assert splits == got["splits"], splits
+    assert torch.equal(grad.double(), torch.cat([dw.reshape(-1), tailv])), f"{geo}: {first_mismatch(grad[:-64].view(dw.shape), dw)}"
+    g2, _ = wgrad_launch(x, dy, dw.shape, s, p, 2.0 ** -7, ld_in=Cin + 24, ci=8, ld_dy=N + 24, cdy=16)
+    want = torch.cat([dw.reshape(-1) * 2.0 ** -7, tailv])
+    assert torch.equal(g2.double(), want), f"{geo} sliced: {first_mismatch(g2[:-64].view(dw.shape), dw * 2.0 ** -7)}"
+
+
 # 3x3 / stride 1 / pad 1 with whole 32-channel chunks: (Cin, N) -> ROW3 <WN, RN, WC>; by default only N <= 32 (and Cin >= 256) take it,
 # the others under KODHIP_WGRAD_ROW3=2 (the child run).  2 x 20 x 12 images: 480 rows, rows of 12 pixels against 32-row stages.
 WGRAD_ROW3 = [((32, 32), (1, 1, 1)), ((64, 32), (1, 1, 2)), ((32, 64), (1, 2, 1)), ((64, 64), (1, 2, 2)), ((32, 96), (2, 2, 1)), ((64, 96), (2, 2, 2))]

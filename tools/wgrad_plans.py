@@ -28,8 +28,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KNOBS = ("KODHIP_WGRAD_DMA", "KODHIP_WGRAD_ROW3", "KODHIP_WGRAD_SLOTS", "KODHIP_WGRAD_ROW3_SLOTS", "KODHIP_STEM_BWD_TW",
-         "KODHIP_STEM_BWD_BLOCKS")
+KNOBS = ("KODHIP_WGRAD_DMA", "KODHIP_WGRAD_ROW3", "KODHIP_WGRAD_SLOTS", "KODHIP_WGRAD_ROW3_SLOTS", "KODHIP_STEM_BWD_BLOCKS")
 SETTINGS = {
     "default": {},
     "row3_off": {"KODHIP_WGRAD_ROW3": "0"},
@@ -37,7 +36,6 @@ SETTINGS = {
     "dma_none": {"KODHIP_WGRAD_DMA": "none"},
     "slots_256": {"KODHIP_WGRAD_SLOTS": "256"},
     "row3_slots_1536": {"KODHIP_WGRAD_ROW3_SLOTS": "1536"},
-    "stem_tw_160": {"KODHIP_STEM_BWD_TW": "160"},
 }
 CONV_KNOBS = ("KODHIP_FORCE_BN", "KODHIP_FORCE_BM", "KODHIP_ROW3", "KODHIP_NO_FAST", "KODHIP_S2_SEPARATE", "KODHIP_S2_FOLD_MAXC",
               "KODHIP_NO_BNRED")
