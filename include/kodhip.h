@@ -467,6 +467,40 @@ int kodhip_frame_desc_bytes(void);
 int kodhip_letterbox_frames(const void* descs /* device [B] */, float* out_f32 /* [B,3,H,W] or NULL */,
                             void* out_pairs /* bf16 [B,H,W/2,8] or NULL */, int B, int H, int W, kodStream_t stream);
 
+/* ---- second-stage crops (csrc/crops.hip; YOLOv5 utils/general.py apply_classifier, utils/plots.py save_one_box): the pixels
+ *      inside N detection boxes, cut out of frames that are read where they lie and resized to out_h x out_w.  Two launches, no
+ *      host synchronisation between them; both check their arguments before launching (B and N 1..65535, out_h and out_w
+ *      1..1024) and take `frames`: device [B] records of kodhip_frame_desc_bytes() bytes, of which only the planes, pitches,
+ *      format, h, w and the six colour integers are read.
+ *
+ * kodhip_crop_plan, one thread per crop: crop n takes row rows + row_index[n] * row_stride (row_stride >= 4 floats; x1, y1, x2, y2
+ * come first - a [B, max_det, 6] buffer with gaps and a dense [N, 6] one both work) of frame frame_index[n].  The rectangle in
+ * fp32, every operation rounded once: cx = (x1 + x2) / 2, w = x2 - x1 (likewise y); square: w = h = max(w, h); w = w * gain + pad;
+ * x1' = cx - w / 2, x2' = cx + w / 2; clamped to [0, W] and [0, H] of the frame; x0 = int(x1'), cw = int(x2') - x0 (toward zero).
+ * cw < 1 or ch < 1, a non-finite coordinate (or a NaN edge of an overflowed box), a negative row index or a frame index
+ * outside [0, B) make the crop EMPTY: valid = 0, the rectangle (0, 0, 0, 0), nothing is read for it.  Geometry in double: mode 0
+ * (stretch, cv2.resize(cutout, (out_w, out_h))): nh = out_h, nw = out_w, top = left = 0; mode 1 (letterbox):
+ * r = min(out_h / ch, out_w / cw), nh = clamp(rint(ch * r), 1, out_h) (half to even), likewise nw, top = (out_h - nh) / 2,
+ * left = (out_w - nw) / 2; scale_y = 1.0 / (nh / (double)ch), scale_x likewise.  gain finite and > 0, pad finite and >= 0.
+ * crops: device [N] records of kodhip_crop_desc_bytes() bytes (core/crops.py CROP_DESC: int frame, valid, x0, y0, w, h, nh, nw,
+ * top, left; double scale_x, scale_y); rects: int32 [N, 4] (x0, y0, cw, ch) in the frame's pixels, or NULL.
+ *
+ * kodhip_crop_batch, grid (ceil(out_h * out_w / 256), N), one thread per output pixel: OpenCV's fixed-point INTER_LINEAR of
+ * kodhip_letterbox_batch applied to the cutout ALONE (coefficients from cw / ch, taps clamped to the cutout's edges; the origin
+ * is added only where a pixel is fetched, so a 4:2:0 cutout at an odd origin takes chroma sample (r >> 1, c >> 1) of the
+ * absolute position), the copy path when nh == ch and nw == cw, 114 for letterbox borders and for every pixel of an empty
+ * crop.  out_f32 [N, 3, out_h, out_w]: (float)p / 255.f, then with mean_std (HOST float[6]: mean r g b, std r g b in the
+ * output's channel order; std finite and non-zero) (v - mean[c]) / std[c], a true division; out_u8 [N, out_h, out_w, 3];
+ * at least one of the two.  bgr != 0 swaps the channel order of both.  Only bytes inside a frame's rows are read, with byte
+ * loads; nothing depends on alignment. */
+int kodhip_crop_desc_bytes(void);
+int kodhip_crop_plan(const void* frames /* device [B] */, int B, const float* rows, int row_stride, const int* row_index /* [N] */,
+                     const int* frame_index /* [N] */, int N, int out_h, int out_w, int mode, int square, float gain, float pad,
+                     void* crops /* device [N] */, int* rects /* [N, 4] or NULL */, kodStream_t stream);
+int kodhip_crop_batch(const void* frames /* device [B] */, int B, const void* crops /* device [N] */, int N,
+                      float* out_f32 /* or NULL */, unsigned char* out_u8 /* or NULL */, int out_h, int out_w, int bgr,
+                      const float* mean_std /* host [6] or NULL */, kodStream_t stream);
+
 /* ---- evaluation post-process (kod/lightning/experiments/yv5_baseline/layers.py:55-155, exp.py:70-102;
  *      kod/core/nms.py:9-75 + torchvision.ops.nms) -------------------------------------------------- */
 typedef struct KodDecodeLevel { const float* raw; int h, w, stride; float anchor_w[3], anchor_h[3]; } KodDecodeLevel;

@@ -136,6 +136,9 @@ SIGNATURES = {
     "kodhip_letterbox_batch": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "kodhip_frame_desc_bytes": (i32, []),
     "kodhip_letterbox_frames": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "kodhip_crop_desc_bytes": (i32, []),
+    "kodhip_crop_plan": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp]),
+    "kodhip_crop_batch": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, C.POINTER(f32), vp]),
     "kodhip_decode": (i32, [C.POINTER(KodDecodeLevel), vp, i32, i32, i32, vp]),
     "kodhip_nms": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, f32, vp]),
     "kodhip_tta_view": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]),

@@ -17,7 +17,7 @@ void kodhip_set_error(const char* fmt, ...) {
 
 const char* kodhip_last_error(void) { return g_err; }
 
-int kodhip_version(void) { return 116; }
+int kodhip_version(void) { return 117; }
 
 // Returns the number of visible HIP devices (0 when there is no GPU); never throws.
 int kodhip_device_count(void) {

@@ -22,43 +22,58 @@ __device__ __forceinline__ void lin_coeff(int d, double scale, int n_src, bool c
   w1 = sat16(f * 2048.f);
 }
 
-// The two pixels of output pair xp of row dy of the resized image (d.nh x d.nw, `left` columns into the canvas); px keeps
-// what it holds (the pad) where the image does not reach.  Desc: a record with h, w, nh, nw, left, scale_x, scale_y (ValDesc,
-// KodFrameDesc).  Src: the source image - src.rows(r0, r1) names the two source rows of this thread (both in [0, h)), then
-// src.px(i, c) is pixel (row i = 0 | 1, column c in [0, w)) as u8 r | g << 8 | b << 16 (higher bits are ignored).
-template <typename Desc, typename Src>
-__device__ __forceinline__ void letterbox_pair(const Desc& d, int dy, int xp, Src src, int px[2][3]) {
-  const bool copy = d.nh == d.h && d.nw == d.w;
-  int r0 = dy, r1 = dy, b0 = 0, b1 = 0;
+// The body in two steps, for a record Desc with h, w, nh, nw, scale_x, scale_y (ValDesc, KodFrameDesc, crops.hip's view of a
+// cutout) and a source Src - src.rows(r0, r1) names the two source rows of this thread (both in [0, h)), then src.px(i, c) is
+// pixel (row i = 0 | 1, column c in [0, w)) as u8 r | g << 8 | b << 16 (higher bits are ignored).
+//
+// letterbox_rows: row dy of the resized image -> its source rows and their 11-bit weights (the copy path: the row itself).
+template <typename Desc>
+__device__ __forceinline__ void letterbox_rows(const Desc& d, bool copy, int dy, int& r0, int& r1, int& b0, int& b1) {
+  r0 = dy; r1 = dy; b0 = 0; b1 = 0;
   if (!copy) {
     int sy;
     lin_coeff(dy, d.scale_y, d.h, false, sy, b0, b1);
     r0 = min(max(sy, 0), d.h - 1);
     r1 = min(max(sy + 1, 0), d.h - 1);
   }
+}
+
+// letterbox_px: column dx in [0, nw) of that row -> the pixel's three channels
+template <typename Desc, typename Src>
+__device__ __forceinline__ void letterbox_px(const Desc& d, bool copy, int dx, int b0, int b1, const Src& src, int px[3]) {
+  if (copy) {
+    const unsigned p = src.px(0, dx);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) px[c] = (p >> (8 * c)) & 255;
+  } else {
+    int sx, a0, a1;
+    lin_coeff(dx, d.scale_x, d.w, true, sx, a0, a1);
+    const int sx1 = min(sx + 1, d.w - 1);
+    const unsigned p00 = src.px(0, sx), p01 = src.px(0, sx1);
+    const unsigned p10 = src.px(1, sx), p11 = src.px(1, sx1);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int S0 = (int)((p00 >> (8 * c)) & 255) * a0 + (int)((p01 >> (8 * c)) & 255) * a1;
+      const int S1 = (int)((p10 >> (8 * c)) & 255) * a0 + (int)((p11 >> (8 * c)) & 255) * a1;
+      const int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
+      px[c] = min(max(v, 0), 255);
+    }
+  }
+}
+
+// The two pixels of output pair xp of row dy of the resized image (d.nh x d.nw, `left` columns into the canvas); px keeps
+// what it holds (the pad) where the image does not reach.
+template <typename Desc, typename Src>
+__device__ __forceinline__ void letterbox_pair(const Desc& d, int dy, int xp, Src src, int px[2][3]) {
+  const bool copy = d.nh == d.h && d.nw == d.w;
+  int r0, r1, b0, b1;
+  letterbox_rows(d, copy, dy, r0, r1, b0, b1);
   src.rows(r0, r1);
 #pragma unroll
   for (int k = 0; k < 2; ++k) {             // (`left` may be odd: each pixel of the pair decides for itself)
     const int dx = 2 * xp + k - d.left;
     if (dx < 0 || dx >= d.nw) continue;
-    if (copy) {
-      const unsigned p = src.px(0, dx);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) px[k][c] = (p >> (8 * c)) & 255;
-    } else {
-      int sx, a0, a1;
-      lin_coeff(dx, d.scale_x, d.w, true, sx, a0, a1);
-      const int sx1 = min(sx + 1, d.w - 1);
-      const unsigned p00 = src.px(0, sx), p01 = src.px(0, sx1);
-      const unsigned p10 = src.px(1, sx), p11 = src.px(1, sx1);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int S0 = (int)((p00 >> (8 * c)) & 255) * a0 + (int)((p01 >> (8 * c)) & 255) * a1;
-        const int S1 = (int)((p10 >> (8 * c)) & 255) * a0 + (int)((p11 >> (8 * c)) & 255) * a1;
-        const int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
-        px[k][c] = min(max(v, 0), 255);
-      }
-    }
+    letterbox_px(d, copy, dx, b0, b1, src, px[k]);
   }
 }
 

@@ -22,7 +22,7 @@ from .device_pipeline import letterbox_table
 RGB24, BGR24, NV12, I420 = 0, 1, 2, 3
 FORMATS = {"rgb": RGB24, "bgr": BGR24, "nv12": NV12, "i420": I420}
 
-# csrc/video.hip KodFrameDesc (the size is asserted through kodhip_frame_desc_bytes)
+# csrc/kodhip_frame.h KodFrameDesc (the size is asserted through kodhip_frame_desc_bytes)
 FRAME_DESC = np.dtype([("plane0", "<u8"), ("plane1", "<u8"), ("plane2", "<u8"), ("pitch0", "<i4"), ("pitch12", "<i4"),
                        ("format", "<i4"), ("h", "<i4"), ("w", "<i4"), ("nh", "<i4"), ("nw", "<i4"), ("top", "<i4"), ("left", "<i4"),
                        ("scale_x", "<f8"), ("scale_y", "<f8"), ("yoff", "<i4"), ("cy", "<i4"), ("cvr", "<i4"), ("cvg", "<i4"),
@@ -230,6 +230,16 @@ class Frame:
             raise ValueError(f"image {index}: frame on {dev}, the detector on {torch.device(device)}")
 
 
+def check_images(images, device=None):
+    """every item a numpy HWC uint8 image or a `Frame` (checked by itself; its planes in host memory or on `device`); raises
+    ValueError("image <index>: ...")"""
+    for i, im in enumerate(images):
+        if isinstance(im, Frame):
+            im.check(i, device)
+        elif not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
+            raise ValueError(f"image {i}: expected an HWC uint8 array with 3 channels")
+
+
 def wrap_frames(images) -> List[Frame]:
     """a call's items as Frames: numpy HWC arrays become `Frame.rgb`"""
     return [im if isinstance(im, Frame) else Frame.rgb(im) for im in images]
@@ -254,20 +264,29 @@ def upload_frames(frames: Sequence[Frame], device, stager) -> List[Frame]:
     return out
 
 
+def frame_records(frames: Sequence[Frame], first_index: int = 0) -> np.ndarray:
+    """FRAME_DESC records that describe the frames alone - plane addresses, pitches, format, size and matrix; the letterbox
+    geometry is left at zero (`frame_table` fills it in; kodhip_crop_plan / kodhip_crop_batch never read it).  Host arithmetic
+    only; raises ValueError("image <first_index + k>: ...") for a bad frame."""
+    for k, f in enumerate(frames):
+        f.check(first_index + k)
+    descs = np.zeros(len(frames), dtype=FRAME_DESC)
+    for d, f in zip(descs, frames):
+        for j, t in enumerate(f.planes):
+            d[f"plane{j}"] = t.data_ptr()
+        d["pitch0"], d["pitch12"] = f.pitches
+        d["format"], d["h"], d["w"] = f.format, f.h, f.w
+        d["yoff"], d["cy"], d["cvr"], d["cvg"], d["cug"], d["cub"] = f.coeffs
+    return descs
+
+
 def frame_table(frames: Sequence[Frame], image_size: int, first_index: int = 0, canvas=None):
     """(FRAME_DESC records, KodLetterbox rows float32 [n, 6]) of frames letterboxed at image_size: `letterbox_table`'s geometry
     for their shapes (canvas None: the image_size square; (H, W): that canvas) plus each frame's plane addresses, pitches,
     format and matrix.  Host arithmetic only; raises ValueError("image <first_index + k>: ...") for a bad frame."""
-    for k, f in enumerate(frames):
-        f.check(first_index + k)
+    descs = frame_records(frames, first_index)
     geo, boxes = letterbox_table([(f.h, f.w) for f in frames], image_size, first_index, canvas)
-    descs = np.zeros(len(frames), dtype=FRAME_DESC)
-    for d, g, f in zip(descs, geo, frames):
+    for d, g in zip(descs, geo):
         for name in ("h", "w", "nh", "nw", "top", "left", "scale_x", "scale_y"):
             d[name] = g[name]
-        for j, t in enumerate(f.planes):
-            d[f"plane{j}"] = t.data_ptr()
-        d["pitch0"], d["pitch12"] = f.pitches
-        d["format"] = f.format
-        d["yoff"], d["cy"], d["cvr"], d["cvg"], d["cug"], d["cub"] = f.coeffs
     return descs, boxes

@@ -17,6 +17,9 @@ letterboxes every chunk onto the smallest canvas of multiples of 32 that holds i
 Every front end but TiledDetector also takes `Frame` items (data/frames.py): video frames that are already on the device - packed
 RGB / BGR with a row pitch, NV12 surfaces, I420 planes - or host NV12 / I420 arrays; a call that holds one goes through
 kodhip_letterbox_frames (csrc/video.hip), which reads the frames where they lie.  A call of numpy images only is untouched.
+`Detector.detect_crops` (AugmentedDetector's too) also returns the pixels inside the boxes at one fixed size - kodhip_crop_plan /
+kodhip_crop_batch (csrc/crops.hip, core/crops.py) on each chunk's sources while they are still on the device - and
+`ClassifiedDetector` runs those crops through a second-stage classifier (YOLOv5 apply_classifier).
 """
 from __future__ import annotations
 
@@ -27,24 +30,15 @@ import numpy as np
 import torch
 
 from . import _lib
+from .core.crops import CropOptions, launch_crops, pool_frames, split_rows
 from .core.nms import _key_cap, _workspace, fuse_detections, merge_detections, non_max_suppression
 from .core.tracking import ByteTracker, Tracks
 from .core.types import FeatureShape
 from .data.device_pipeline import VAL_DESC, ImagePool, _Stager, letterbox_table                 # noqa: F401  (re-exported)
-from .data.frames import FRAME_DESC, Frame, frame_table, upload_frames, wrap_frames
+from .data.frames import FRAME_DESC, Frame, check_images as _check_images, frame_records, frame_table, upload_frames, wrap_frames
 from .engine.graphed import GraphCache
 from .engine.rect import rect_canvas, rect_order
 from .engine.tiles import tile_plan
-
-
-def _check_images(images, device=None):
-    """every item a numpy HWC uint8 image or a `Frame` (data/frames.py: checked by itself; its planes in host memory or on
-    `device`)"""
-    for i, im in enumerate(images):
-        if isinstance(im, Frame):
-            im.check(i, device)
-        elif not (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
-            raise ValueError(f"image {i}: expected an HWC uint8 array with 3 channels")
 
 
 def _has_frames(images) -> bool:
@@ -158,12 +152,13 @@ class Detector:
                 m.training = was
         return get_detections(FeatureShape(width=x.shape[3], height=x.shape[2]), res, self.anchor_info)
 
-    def _letterboxed(self, images, sort: bool = False):
+    def _letterboxed(self, images, sort: bool = False, keep: Optional[list] = None):
         """The input half of a call: checks, all geometry (a bad image raises here, before anything is uploaded or launched),
         then chunk after chunk of batch_size images uploaded and letterboxed -> (order, iterator of (real images of the chunk,
         x fp32 [B, 3, H, W], the padded chunk's KodLetterbox rows)).  sort: in rectangular mode the images are taken sorted by
         aspect ratio (every chunk then holds alike shapes) and `order` holds their positions for `_caller_order`; otherwise
-        None."""
+        None.  keep: a list that receives every chunk's sources on the device as the chunk is letterboxed (an ImagePool or the
+        list of uploaded Frames), for a caller that reads them again (detect_crops)."""
         images = list(images)
         _check_images(images, self.device)
         shapes = [im.shape[:2] for im in images]
@@ -176,7 +171,7 @@ class Detector:
         if _has_frames(images):            # one Frame sends the whole call through kodhip_letterbox_frames
             images = wrap_frames(images)
         chunks = (images[c * self.B:(c + 1) * self.B] for c in range(len(tables)))
-        return order, ((len(chunk), *self._letterbox(chunk, *table)) for chunk, table in zip(chunks, tables))
+        return order, ((len(chunk), *self._letterbox(chunk, *table, keep=keep)) for chunk, table in zip(chunks, tables))
 
     def _detect(self, batches):
         """`_letterboxed`'s chunks through forward and NMS -> (real images of the chunk, the padded chunk's PackedDetections),
@@ -193,7 +188,7 @@ class Detector:
         """images, in the given order, in chunks of batch_size through letterbox, forward and NMS"""
         return self._detect(self._letterboxed(images)[1])
 
-    def _letterbox(self, chunk, canvas, descs, boxes):
+    def _letterbox(self, chunk, canvas, descs, boxes, keep: Optional[list] = None):
         """one chunk on the device: the upload of its images and the letterbox launch -> (x fp32 [B, 3, H, W] on `canvas`,
         the KodLetterbox rows of the padded chunk).  Frames: planes in host memory go up in one pinned upload, the others are
         read where they lie (kodhip_letterbox_frames); numpy images go into an ImagePool (kodhip_letterbox_batch)."""
@@ -211,6 +206,8 @@ class Detector:
             src = ImagePool(chunk, self.device)
             descs["off"] = src.offsets
             launch, name = functools.partial(lib.kodhip_letterbox_batch, src.data.data_ptr()), "letterbox_batch"
+        if keep is not None:
+            keep.append(src)
         if n < B:              # pad with the last record: the batch keeps its shape, the copies are dropped by the caller
             descs = np.concatenate((descs, np.repeat(descs[-1:], B - n)))
             boxes = np.concatenate((boxes, np.repeat(boxes[-1:], B - n, axis=0)))
@@ -224,6 +221,62 @@ class Detector:
         order, batches = self._letterboxed(images, sort=True)
         return _caller_order(order, [r for n, out in self._detect(batches) for r in out[:n]])
 
+    def _crop_chunks(self, images, opts: CropOptions):
+        """`__call__`'s chunks, each followed by plan + crop over its kept rows while the chunk's sources are still on the
+        device -> (order, iterator of (the real images' [n_i, 6] rows, rows per image that were cropped, `launch_crops`'s
+        result or None for a chunk without rows))"""
+        kept: list = []
+        order, batches = self._letterboxed(images, sort=True, keep=kept)
+
+        def chunks():
+            for n, out in self._detect(batches):
+                src = kept.pop()
+                assert not kept
+                frames = (pool_frames(src) if isinstance(src, ImagePool) else src)[:n]
+                counts = [len(r) if opts.max_crops is None else min(len(r), opts.max_crops) for r in out[:n]]
+                res = None
+                if sum(counts):
+                    max_det = int(out.packed.shape[1])
+                    row_index = np.concatenate([b * max_det + np.arange(c, dtype=np.int32) for b, c in enumerate(counts)])
+                    frame_index = np.repeat(np.arange(n, dtype=np.int32), counts)
+                    res = launch_crops(self._stager.upload(frame_records(frames)), n, out.packed, int(out.packed.shape[2]), row_index,
+                                       frame_index, opts, self._stager)
+                yield list(out[:n]), counts, res
+        return order, chunks()
+
+    @torch.no_grad()
+    def detect_crops(self, images, size=(224, 224), **crop_options) -> "CropDetections":
+        """`__call__` plus the pixels inside the boxes: the list `det(images)` returns (same boxes, same order - the caller's,
+        also in rectangular mode) with `.crops[i]` fp32 [n_i, 3, h, w], `.rects[i]` int32 [n_i, 4] (x0, y0, cw, ch in image i's
+        pixels), `.valid[i]` bool [n_i] and, with out_u8=True, `.u8[i]` uint8 [n_i, h, w, 3].  size and the keyword options are
+        `core.crops.crop_detections`'s (mode, square, gain, pad, max_crops, bgr, mean, std, out_u8; with max_crops = k the
+        crops belong to an image's first k rows).  Per chunk: letterbox, forward, NMS, then kodhip_crop_plan +
+        kodhip_crop_batch on the chunk's sources - the numpy images' pool or the frames where they lie; the boxes stay on
+        the device in between."""
+        opts = CropOptions(size, **crop_options)
+        order, chunks = self._crop_chunks(images, opts)
+        dev = self.device
+        rows, crops, u8, rects, valid = [], [], [], [], []
+        for dets, counts, res in chunks:
+            rows.extend(dets)
+            if res is None:
+                res = (torch.empty((0, 3, opts.h, opts.w), dtype=torch.float32, device=dev),
+                       torch.empty((0, opts.h, opts.w, 3), dtype=torch.uint8, device=dev) if opts.out_u8 else None,
+                       torch.empty((0, 4), dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.bool, device=dev))
+            for dst, t in zip((crops, u8, rects, valid), res):
+                dst.extend(split_rows(t, counts) or [None] * len(counts))
+        back = lambda items: _caller_order(order, items)
+        return CropDetections(back(rows), back(crops), back(u8) if opts.out_u8 else None, back(rects), back(valid))
+
+
+class CropDetections(list):
+    """What `Detector.detect_crops` returns: `Detector.__call__`'s list of per-image [n, 6] tensors, which also carries the
+    per-image crops, rectangles and valid flags (core.crops.CropResult's fields; u8 is None without out_u8)."""
+
+    def __init__(self, items, crops, u8, rects, valid):
+        super().__init__(items)
+        self.crops, self.u8, self.rects, self.valid = crops, u8, rects, valid
+
 
 class AugmentedDetector(Detector):
     """Detector with test-time augmentation (YOLOv5 detect.py `--augment`): same constructor, same call, same results format.
@@ -236,6 +289,73 @@ class AugmentedDetector(Detector):
     against 2 Mi without augmentation."""
 
     augment = True
+
+
+class ClassifiedDetections(list):
+    """What `ClassifiedDetector` returns: the per-image [n, 6] tensors, with `.cls2[i]` int64 [n]: the classifier's class of
+    every returned row (-1: the row's crop was empty)."""
+
+    def __init__(self, items, cls2):
+        super().__init__(items)
+        self.cls2 = cls2
+
+
+class ClassifiedDetector(Detector):
+    """det = ClassifiedDetector(net, anchor_info, ..., classifier=model, crop_size=(224, 224), mode="filter"); results = det(images)
+
+    Detector with a second-stage classifier (YOLOv5 utils/general.py apply_classifier): the constructor is Detector's plus,
+    by keyword, `classifier` - any callable that takes crops fp32 [n, 3, h, w] and returns scores [n, K], called under
+    torch.no_grad() in pieces of at most `classifier_batch` - `crop_size`, `mode` and the crop options of
+    `core.crops.crop_detections` (`crop_mode` is its `mode`; square, gain, pad, bgr, mean, std; apply_classifier's values by
+    default).  `augment=True` runs the detector with test-time augmentation (AugmentedDetector's forward).  Every chunk's
+    crops are cut on the device (`Detector.detect_crops`'s path) and classified before the next chunk is read.
+    mode "filter": YOLOv5's rule - a row stays when its class equals the classifier's argmax; rows with an empty crop are
+    dropped.  mode "annotate": every row stays.  Either way the result carries `.cls2` (the argmax per returned row; -1 for
+    an empty crop)."""
+
+    def __init__(self, net, anchor_info, *args, classifier, crop_size=(224, 224), mode: str = "filter", classifier_batch: int = 256,
+                 crop_mode: str = "stretch", square: bool = True, gain: float = 1.3, pad: float = 30, bgr: bool = False, mean=None,
+                 std=None, augment: bool = False, **kwargs):
+        if not callable(classifier):
+            raise ValueError("classifier: expected a callable taking [n, 3, h, w] crops and returning [n, K] scores")
+        if mode not in ("filter", "annotate"):
+            raise ValueError(f"mode {mode!r}: expected 'filter' or 'annotate'")
+        if int(classifier_batch) < 1:
+            raise ValueError(f"classifier_batch {classifier_batch}: expected >= 1")
+        self.crop_options = CropOptions(crop_size, crop_mode, square, gain, pad, None, bgr, mean, std)
+        super().__init__(net, anchor_info, *args, **kwargs)
+        self.classifier, self.mode, self.classifier_batch, self.augment = classifier, mode, int(classifier_batch), bool(augment)
+
+    def _classify(self, crops: torch.Tensor) -> torch.Tensor:
+        """argmax of the classifier's scores, int64 [n]"""
+        parts = []
+        for s in range(0, len(crops), self.classifier_batch):
+            piece = crops[s:s + self.classifier_batch]
+            scores = self.classifier(piece)
+            if not (torch.is_tensor(scores) and scores.dim() == 2 and scores.shape[0] == len(piece) and scores.shape[1] >= 1):
+                raise ValueError(f"classifier: returned {tuple(scores.shape) if torch.is_tensor(scores) else type(scores).__name__} "
+                                 f"for {len(piece)} crops (expected [{len(piece)}, K] scores)")
+            parts.append(scores.argmax(dim=1))
+        return torch.cat(parts)
+
+    @torch.no_grad()
+    def __call__(self, images: Sequence[np.ndarray]) -> ClassifiedDetections:
+        order, chunks = self._crop_chunks(images, self.crop_options)
+        rows, cls2 = [], []
+        for dets, counts, res in chunks:
+            if res is None:
+                rows.extend(dets)
+                cls2.extend(torch.empty(0, dtype=torch.int64, device=self.device) for _ in dets)
+                continue
+            crops, _, _, valid = res
+            c2 = torch.where(valid, self._classify(crops), torch.full_like(valid, -1, dtype=torch.int64))
+            for r, c in zip(dets, split_rows(c2, counts)):
+                if self.mode == "filter":
+                    keep = c == r[:, 5].long()                      # (an empty crop's -1 equals no class)
+                    r, c = r[keep], c[keep]
+                rows.append(r)
+                cls2.append(c)
+        return ClassifiedDetections(_caller_order(order, rows), _caller_order(order, cls2))
 
 
 class EnsembleDetector:
